@@ -13,6 +13,15 @@ Inputs are generated in HBM before the timed region. Consecutive steps alternate
 between two streams and two output sets, as a caller streaming batches runs them: one
 launch's drain (its last waves leaving the SIMDs) overlaps the next launch's start.
 
+A plain run (`--gpus 1 --steps K --warmup W`) does what that figure needs and no more: it sets
+up, settles the clock, runs W untimed and K timed steps and prints the line (`value`,
+`ms_per_step`, the HBM roofline at the steps' launch period). `--dump-outputs DIR` also writes
+what the last timed step computed as DIR/<name>.npy; the inputs are seeded, so two builds can
+be compared output for output. Everything below that is more than the headline -- the launch
+timed on its own (`kernel_ms`), config C5, the other configs, precisions and output sets, the
+PMC passes, the host path, the facade's latency, the CPU baselines, and at N > 1 the RCCL
+gather -- is measured only with `--full`.
+
 Multi-GPU (--gpus N): one process per GPU under torchrun (the driver's launch; --gpus must
 equal WORLD_SIZE), or one process driving devices 0..N-1 without it; never fewer GPUs than
 asked (the run fails instead). Each rank extracts its own 262,144-frame shard of one global
@@ -105,6 +114,17 @@ def parse(argv=None):
                     help="N = 1: skip the secondary timing with every output (spectra too) and 40 mel bands")
     ap.add_argument("--no-pmc", action="store_true",
                     help="N = 1: skip the live rocprofv3 --pmc passes (HBM traffic, VALU instruction mix)")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline steps, measure everything else the line can carry: the serialised launches "
+                         "behind kernel_ms and the rooflines, config C5, the other configs, precisions and output sets, "
+                         "the PMC passes, the host path, the facade's latency and the CPU baselines (N = 1), the RCCL "
+                         "gather (N > 1); the --no-* options above then leave single legs out. Without it a run sets "
+                         "up, settles, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32; one "
+                         "file per output array, local devices' shards concatenated in device order; a torchrun rank r > 0 "
+                         "writes DIR/<name>.rank<r>.npy). At most 64 MB in all: a larger record is cut down to a "
+                         "fixed, seeded sample of its frames, whose indices are DIR/frame_index.npy")
     return ap.parse_args(argv)
 
 
@@ -430,11 +450,13 @@ def pmc_live(n, F, precision):
     return read + write, valu, note
 
 
-def run_mode(step, devs, steps, warmup, dist):
+def run_mode(step, devs, steps, warmup, dist, serial=True, after_timed=None):
     """W untimed steps, then exactly `steps` timed ones bracketed by a barrier and a device
     synchronisation on both sides, pipelined over two streams (pipelined()); HIP events on the
     launch stream around the whole timed region give the launch period (no events between the
-    steps: an event pair per step cost 1-2 % of the step time, tools/step_overlap.py). Then an
+    steps: an event pair per step cost 1-2 % of the step time, tools/step_overlap.py).
+    `after_timed`, if given, is called once the timed steps have drained (--dump-outputs reads
+    the last step's outputs there). With `serial` (--full) then an
     untimed single-stream pass with an event pair around each launch (the spread of single
     launches), and one more of 20 launches back to back on one stream with one event pair around
     them all: the mean launch duration (plus the small dispatch gap between serialised launches),
@@ -457,24 +479,27 @@ def run_mode(step, devs, steps, warmup, dist):
         dist.barrier()
     elapsed = time.perf_counter() - t0
     period = e0.elapsed_time(e1) / steps
-    # the launch on its own (serialised on one stream), untimed by the step clock
-    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(20)]
-    for a, b in ev:
-        a.record(s0)
-        step(0)  # every local device's stream 0: serialised behind the previous launch
-        b.record(s0)
-    devs.sync()
-    iso = [a.elapsed_time(b) for a, b in ev]
-    es0, es1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    es0.record(s0)
-    for _ in range(20):
-        step(0)
-    es1.record(s0)
-    devs.sync()
-    serial = es0.elapsed_time(es1) / 20
-    stats = {"period_ms": period, "launch_serial_ms": serial, "launch_alone_mean_ms": float(np.mean(iso)),
-             "launch_alone_median_ms": float(np.median(iso)), "launch_alone_min_ms": float(np.min(iso)),
-             "launch_alone_max_ms": float(np.max(iso))}
+    if after_timed:
+        after_timed()
+    stats = {"period_ms": period}
+    if serial:
+        # the launch on its own (serialised on one stream), untimed by the step clock
+        ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(20)]
+        for a, b in ev:
+            a.record(s0)
+            step(0)  # every local device's stream 0: serialised behind the previous launch
+            b.record(s0)
+        devs.sync()
+        iso = [a.elapsed_time(b) for a, b in ev]
+        es0, es1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        es0.record(s0)
+        for _ in range(20):
+            step(0)
+        es1.record(s0)
+        devs.sync()
+        stats.update({"launch_serial_ms": es0.elapsed_time(es1) / 20, "launch_alone_mean_ms": float(np.mean(iso)),
+                      "launch_alone_median_ms": float(np.median(iso)), "launch_alone_min_ms": float(np.min(iso)),
+                      "launch_alone_max_ms": float(np.max(iso))})
     if dist:
         t = torch.tensor([elapsed], dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -482,22 +507,53 @@ def run_mode(step, devs, steps, warmup, dist):
         # per-GPU step times reported separately (HIP events on each rank's stream)
         allr = [None] * dist.get_world_size()
         dist.all_gather_object(allr, stats)
-        stats = {"rank0": stats, "per_rank_period_ms": [r["period_ms"] for r in allr],
-                 "per_rank_launch_alone_ms": [r["launch_alone_mean_ms"] for r in allr],
-                 "per_rank_launch_serial_ms": [r["launch_serial_ms"] for r in allr]}
+        stats = {"rank0": stats, "per_rank_period_ms": [r["period_ms"] for r in allr]}
+        if serial:
+            stats.update({"per_rank_launch_alone_ms": [r["launch_alone_mean_ms"] for r in allr],
+                          "per_rank_launch_serial_ms": [r["launch_serial_ms"] for r in allr]})
     return elapsed, period, stats
 
 
-def measure_shards(wl, devs, args, dist, feats=FEATURES):
-    """The shards alone: every local device extracts its own shard (no data-path collective)."""
+DUMP_BYTES = 64 * 1000 * 1000  # --dump-outputs: the most one run writes, over all its ranks
+DUMP_SEED = 0x64756D70
+
+
+def dump_outputs(path, per_device, F, share=1, suffix=""):
+    """--dump-outputs: the output arrays of one step (a dict of device tensors per local device,
+    F frames each) as path/<name><suffix>.npy in float32, the devices' shards concatenated in
+    device order. A record larger than this process's share of DUMP_BYTES is cut down to a
+    fixed, seeded sample of its frames (the same for every array; the sorted frame numbers are
+    written as frame_index<suffix>.npy, float64)."""
+    os.makedirs(path, exist_ok=True)
+    total = len(per_device) * F
+    row_bytes = sum(4 * t[0].numel() for t in per_device[0].values())
+    keep = int(DUMP_BYTES // share // row_bytes)
+    idx = None
+    if keep < total:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(total, size=keep, replace=False))
+        np.save(os.path.join(path, "frame_index%s.npy" % suffix), idx.astype(np.float64))
+    for name in per_device[0]:
+        a = np.concatenate([o[name].detach().cpu().numpy() for o in per_device]).astype(np.float32, copy=False)
+        np.save(os.path.join(path, "%s%s.npy" % (name, suffix)), a if idx is None else a[idx])
+
+
+def measure_shards(wl, devs, args, dist, feats=FEATURES, dump=None):
+    """The shards alone: every local device extracts its own shard (no data-path collective).
+    `dump`, if a list, receives the last timed step's outputs (a dict of device tensors per local
+    device) once the timed steps have drained."""
     sets = {d: [wl.plans[d].alloc_outputs(wl.F, feats, device="cuda:%d" % d) for _ in range(2)] for d in devs.devs}
 
     def step(k):
         for d in devs.devs:
             wl.plans[d].extract_device(wl.frames[d].data_ptr(), wl.F, sets[d][k & 1][1], devs.stream(d, k).cuda_stream)
+
+    def last():  # step k writes output set k & 1; copies on the device, for the caller to write out afterwards
+        dump.extend({k: t.clone() for k, t in sets[d][(args.steps - 1) & 1][0].items()} for d in devs.devs)
+        devs.sync()
     devs.sync()
     settle(step, devs, args.settle_ms, dist)
-    return run_mode(step, devs, args.steps, args.warmup, dist)
+    return run_mode(step, devs, args.steps, args.warmup, dist, serial=args.full,
+                    after_timed=last if dump is not None else None)
 
 
 def measure_gather(wl, devs, args, dist, mode, rank, world, gpus, out):
@@ -607,8 +663,9 @@ def gather_exit_code(args, statuses):
 
 
 def launch_ms(stats):
-    """Rank 0's mean launch duration (run_mode: 20 launches serialised on one stream, one event pair)."""
-    return (stats["rank0"] if "rank0" in stats else stats)["launch_serial_ms"]
+    """Rank 0's mean launch duration (run_mode: 20 launches serialised on one stream, one event pair);
+    None where those launches were not run (a run without --full)."""
+    return (stats["rank0"] if "rank0" in stats else stats).get("launch_serial_ms")
 
 
 def shard_fields(gpus, F, n, el, km, stats, steps, bytes_per_frame):
@@ -693,17 +750,22 @@ def main():
     # (MGX_GROUP_TRANSPORT=ipc: the cross-process rehearsal of the gather, whose ranks may share a GPU --
     # the chunks move through IPC-mapped buffers instead of RCCL, which refuses two ranks on one device)
     ipc_rehearsal = os.environ.get("MGX_GROUP_TRANSPORT") == "ipc"
-    gather_on = gpus > 1 and not args.no_gather and (not shared or ipc_rehearsal)
+    gather_on = args.full and gpus > 1 and not args.no_gather and (not shared or ipc_rehearsal)
     head = Workload(n, F, devs, first, args.precision)
-    el_s, km_s, stats_s = measure_shards(head, devs, args, dist)
+    last_outputs = [] if args.dump_outputs else None
+    el_s, km_s, stats_s = measure_shards(head, devs, args, dist, dump=last_outputs)
     value_s = gpus * F * args.steps / el_s
+    if last_outputs:
+        dump_outputs(args.dump_outputs, last_outputs, F, share=world if dist else 1,
+                     suffix=".rank%d" % rank if dist and rank else "")
+        del last_outputs[:]
     gather = {"status": "not run", "chunks": args.chunks or "auto"} if gather_on else None
     line_box = {}
     failed = []
 
     # C5 (BASELINE configs[4]): the shards first (no collective), its gather after the headline's
     c5 = None
-    if not args.no_c5:
+    if args.full and not args.no_c5:
         w5 = Workload(C5_N, args.c5_frames, devs, first, args.precision)
         el5, km5, st5 = measure_shards(w5, devs, args, dist)
         c5 = c5_field(gpus, args.c5_frames, el5, km5, st5, args.steps, gather_on, args.chunks)
@@ -713,7 +775,7 @@ def main():
             c5["mfcc_exact"] = mfcc_exact_of(c5, timed_launches(
                 args, devs, capi.Plan(buffer_size=C5_N, precision=args.precision, mfcc_reference=True, device=d0),
                 FEATURES, 4 * C5_N + 4 * OUT_FLOATS, w5.frames[d0]))
-    if mode == "one":
+    if args.full and mode == "one":
         line_box.update(secondary(args, head.plans[devs.devs[0]], head.frames[devs.devs[0]], devs, n, F))
 
     def emit_line(gather_status=None, target=None):
@@ -888,9 +950,10 @@ def build_line(args, gpus, mode, placement, F, n, value_s, el_s, km_s, stats_s, 
     # one stream between one event pair (what rocprofv3 --stats reports per dispatch); the launch
     # period of the pipelined timed steps (value) is reported beside it
     alone_ms = launch_ms(stats_s)
-    kernel_ms = alone_ms
+    # a run without --full has no serialised launches: its rooflines rest on the timed steps' launch period
+    kernel_ms = alone_ms if alone_ms is not None else km_s
     achieved = F * bytes_per_frame / (kernel_ms * 1e-3) / 1e9
-    traffic, valu, traffic_note = extras.get("pmc") or (None, None, "not measured (--no-pmc or N > 1)")
+    traffic, valu, traffic_note = extras.get("pmc") or (None, None, "not measured (no --full, --no-pmc or N > 1)")
     if valu is not None:
         # the faithful path is FP64-VALU bound. Issue costs per wave64
         # instruction measured by tools/ubench/op_rates.hip (profiles/r01_op_rates.log):
@@ -942,7 +1005,10 @@ def build_line(args, gpus, mode, placement, F, n, value_s, el_s, km_s, stats_s, 
                      "kernel_ms_source": "mean launch duration: 20 launches back to back on one stream after "
                                          "the timed steps, HIP events around them (step_event_ms.launch_serial_ms; "
                                          "launch_alone_* = an event pair around each launch, which adds ~1 %); "
-                                         "rocprofv3 --stats of bench.py --single-stream: profiles/",
+                                         "rocprofv3 --stats of bench.py --single-stream: profiles/"
+                                         if alone_ms is not None else
+                                         "period_ms, the launch period of the timed steps: the launch on its own is "
+                                         "timed by a --full run",
                      "period_ms": km_s,
                      "period_source": ("launch period of the timed steps: HIP events around the timed region / steps"
                                        + (" (one stream)" if args.single_stream else " (steps pipelined over two streams)")),

@@ -293,3 +293,47 @@ def test_bench_line_carries_fp64_roofline_and_all_core_cpu_baseline(monkeypatch)
     assert cb["cores"] == min(bench.CPU_THREADS, allc) and cb["all_cores"]["cores"] == allc
     assert cb["all_cores"]["value"] == 1000.0 * allc and "schedulable_cpus" in cb["all_cores"]
     assert (1024, "all", allc) in calls and cb["one_thread"] == 1000.0
+
+
+def test_plain_run_is_the_headline_alone():
+    """Without --full the benchmark times its steps and nothing else: no serialised launches, so
+    the line's rooflines rest on the timed steps' launch period, and none of the secondary fields
+    is there; `ms_per_step` is the wall time of one timed step."""
+    import types
+
+    import bench
+    p = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert not p.full and p.dump_outputs is None and p.steps == 7 and p.warmup == 2
+    assert bench.parse(["--full", "--dump-outputs", "d"]).full and bench.parse(["--dump-outputs", "d"]).dump_outputs == "d"
+    args = types.SimpleNamespace(steps=7, warmup=2, precision="faithful", single_stream=False)
+    F, el = 262144, 7 * 0.6e-3  # seconds of the 7 timed steps
+    line = bench.build_line(args, 1, "one", [], F, 1024, F * 7 / el, el, 0.58, {"period_ms": 0.58}, None, {})
+    assert line["steps"] == 7 and abs(line["ms_per_step"] - 0.6) < 1e-9 and line["unit"] == "frames/s"
+    assert line["higher_is_better"] is True and line["dtype"].startswith("f64") and "bufferSize=1024" in line["metric"]
+    r = line["roofline"]
+    assert r["kernel_ms"] == 0.58 and r["frac"] == r["frac_pipelined"] and "--full" in r["kernel_ms_source"]
+    for k in ("c5", "c2", "c3", "c4", "fast_mode", "mfcc_exact", "every_output", "host_path", "latency",
+              "cpu_baseline", "valu", "gather"):
+        assert k not in line, k
+
+
+def test_dump_outputs_writes_float32_within_its_budget(tmp_path, monkeypatch):
+    """--dump-outputs: one float32 .npy per output array, local devices' shards concatenated; a
+    record over the budget is cut to one seeded sample of its frames, the same from run to run."""
+    import bench
+    F = 100
+    outs = [{"rms": torch.arange(F, dtype=torch.float32) + 1000 * d,
+             "mfcc": (torch.arange(F * 13, dtype=torch.float32) + 1000 * d).view(F, 13)} for d in range(2)]
+    bench.dump_outputs(str(tmp_path / "a"), outs, F)
+    rms, mfcc = np.load(tmp_path / "a" / "rms.npy"), np.load(tmp_path / "a" / "mfcc.npy")
+    assert sorted(os.listdir(tmp_path / "a")) == ["mfcc.npy", "rms.npy"]
+    assert rms.dtype == mfcc.dtype == np.float32 and rms.shape == (200,) and mfcc.shape == (200, 13)
+    assert rms[0] == 0 and rms[100] == 1000 and mfcc[199, 12] == F * 13 - 1 + 1000
+    monkeypatch.setattr(bench, "DUMP_BYTES", 14 * 4 * 60)  # room for 60 of the 200 frames; 30 for one of two ranks
+    for run in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / run), outs, F, share=2, suffix=".rank1")
+    idx = np.load(tmp_path / "b" / "frame_index.rank1.npy")
+    assert idx.shape == (30,) and np.all(np.diff(idx) > 0) and idx.dtype == np.float64
+    sub = np.load(tmp_path / "b" / "mfcc.rank1.npy")
+    assert np.array_equal(sub, mfcc[idx.astype(int)]) and np.array_equal(sub, np.load(tmp_path / "c" / "mfcc.rank1.npy"))
+    assert np.array_equal(np.load(tmp_path / "b" / "rms.rank1.npy"), rms[idx.astype(int)])

@@ -63,14 +63,19 @@ def test_parse_rejects_encodings(capi):
 
 
 def test_parse_matches_reference_wavs(capi):
-    """The three reference recordings: the header values tools/gen_golden.js recorded."""
+    """The three reference recordings: the header values tools/gen_golden.js recorded. Each file is
+    rebuilt from its stored header (tests/golden/wav/<name>.head: every byte before the samples) and
+    its recorded length, the samples zeroed: the header walk stops at the data chunk and never reads
+    them."""
+    import json
     import os
     m = golden_io.manifest()["wav"]
-    base = "/root/reference/audio"
-    if not os.path.isdir(base):
-        pytest.skip("reference audio not present (GPU box)")
+    base = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "wav")
+    sizes = json.load(open(os.path.join(base, "sizes.json")))["file_bytes"]
     for name, w in m.items():
-        data = open(os.path.join(base, name + ".wav"), "rb").read()
+        head = open(os.path.join(base, name + ".head"), "rb").read()
+        assert len(head) == w["dataOffset"], name
+        data = head + bytes(sizes[name] - len(head))
         info = capi.wav_parse(data)
         assert info["sample_frames"] == w["samples"], name
         assert info["data_offset"] == w["dataOffset"], name

@@ -13,7 +13,7 @@ timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.
 tail -1 $O/smoke.log
 if [ -z "$NO_BENCH" ]; then
   echo "[check] bench"
-  timeout -k 10 600 python bench.py > $O/bench.log 2>&1 || { tail -20 $O/bench.log; exit 1; }
+  timeout -k 10 600 python bench.py --full > $O/bench.log 2>&1 || { tail -20 $O/bench.log; exit 1; }
   tail -1 $O/bench.log | python3 -c "import json,sys; d=json.loads(sys.stdin.read()); print(d['value'], d['roofline']['kernel_ms'], d['roofline']['frac'], d['roofline']['traffic']); print('c5', d['c5'].get('kernel_ms'), d['c5'].get('roofline_frac'), 'mfcc_exact', d['mfcc_exact'].get('cost_vs_value_kernel'))"
 fi
 echo "[check] done"

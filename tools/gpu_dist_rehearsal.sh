@@ -11,7 +11,7 @@ mkdir -p $O && cd $R
 run() {  # port tag args...
   local port=$1 tag=$2; shift 2
   timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port $port \
-    bench.py --gpus 2 --allow-shared-gpu "$@" > $O/$tag.log 2>&1
+    bench.py --full --gpus 2 --allow-shared-gpu "$@" > $O/$tag.log 2>&1
 }
 run 29533 nogather --steps 20 --warmup 5 --no-gather || { tail -20 $O/nogather.log; exit 1; }
 tail -1 $O/nogather.log | cut -c1-300

@@ -33,7 +33,7 @@ step rehearsal
 run() {  # port tag args...
   local port=$1 tag=$2; shift 2
   timeout -k 10 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port $port \
-    bench.py --gpus 2 --allow-shared-gpu --steps 20 --warmup 5 --no-cpu-baseline "$@" > $O/$tag.log 2>&1
+    bench.py --full --gpus 2 --allow-shared-gpu --steps 20 --warmup 5 --no-cpu-baseline "$@" > $O/$tag.log 2>&1
 }
 summ() { tail -1 $O/$1.log | python3 -c "import json,sys; d=json.loads(sys.stdin.read()); g=d['gather']; c=d['c5']; print('$1', 'shards', round(d['value']/1e6,1), 'M/s gather', g.get('status'), round((g.get('value') or 0)/1e6,1), 'vs_shards', round(g.get('vs_shards') or 0,3), 'ms/step', round(g.get('ms_per_step') or 0,3), '| c5 value', round((c.get('value') or 0)/1e6,1), 'shards_value', round(c['shards_value']/1e6,1), 'vs', round(c['gather'].get('vs_shards') or 0,3))"; }
 rm -f /tmp/r6trace_*

@@ -5,7 +5,7 @@ bench run, after its clock-settle and warmup launches). With parts > 1 (a step o
 bench is that many launches: mgx_extract_device's parts on two streams), the step spans of
 the matching kernel too: first start to last end of each group of `parts` dispatches, over
 the last k steps -- the figure the bench's per-step HIP events measure.
-With skip > 0 the last `skip` dispatches are left out first (bench.py's single-stream
+With skip > 0 the last `skip` dispatches are left out first (bench.py --full's single-stream
 launches after its timed steps: 20 with an event pair each, then 20 back to back, skip = 40), and for extract kernels the launch period of the k
 dispatches before them is printed: (last end - first start) / k -- what bench.py's events
 around its pipelined timed region measure (consecutive launches overlap by the drain).
