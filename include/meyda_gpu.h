@@ -21,6 +21,8 @@
  *   mgx_wav_parse,       decodeAudioData + getChannelData(0)        lib/bufferLoader.js:23,
  *   mgx_pcm_decode_device,                                          src/meyda.js:72
  *   mgx_extract_host_pcm
+ *   mgx_extract_signal_* the same over one contiguous signal whose   src/meyda.js:69-91 (disjoint
+ *                        buffers start every `hop` samples           buffers only: hop = N)
  *   mgx_group_*          several devices, RCCL gather of the        src/meyda.js:17-97 (one plan
  *                        per-frame records to the root device       per device), :69-91 (buffers
  *                                                                   are independent: shardable)
@@ -249,6 +251,51 @@ int mgx_pcm_decode_device(const void* pcm, uint64_t sample_frames, uint32_t form
  * (no read past the caller's buffer). `pcm` needs no alignment. */
 int mgx_extract_host_pcm(mgx_plan* plan, const void* pcm, uint64_t pcm_bytes, uint64_t sample_frames,
                          uint32_t format, uint32_t channels, uint32_t channel, const mgx_outputs* outputs);
+
+/* ---- Overlapping buffers of one contiguous signal (hop size) ----------------------
+ * Replaces, in a host application, the loop that slices a decoded signal into buffers
+ * `hop` samples apart and hands each to the reference (what later Meyda releases call
+ * hopSize; the snapshot's ScriptProcessor, src/meyda.js:69-91, only delivers disjoint
+ * buffers, hop = buffer_size). The buffers are never materialised: the kernel reads
+ * buffer f at samples + f * hop, so the signal is the whole input footprint.
+ *
+ * A signal of S samples gives F = (S < N) ? 0 : (S - N) / hop + 1 buffers, buffer f being
+ * samples [f * hop, f * hop + N); a trailing partial buffer is dropped, as everywhere in
+ * this ABI. hop = 0 is MGX_E_INVALID_ARGUMENT; hop > N (samples skipped) is legal; F = 0
+ * returns MGX_OK and writes nothing. Outputs are laid out exactly as for
+ * mgx_extract_device / mgx_extract_host with num_frames = F, and every output equals, bit
+ * for bit, what mgx_extract_device gives on the same F buffers stored densely. The
+ * kernel's loads past the last buffer are clamped to buffer F - 1 (its samples
+ * [(F - 1) * hop, (F - 1) * hop + N)): nothing beyond that buffer is read, so none of the
+ * up to hop - 1 samples of the dropped tail are. Multi-device groups (mgx_group_*) take
+ * dense buffers only. */
+
+/* F of the formula above. Host only (no device). */
+int mgx_signal_frames(uint64_t num_samples, uint32_t buffer_size, uint32_t hop, uint64_t* num_frames);
+
+/* mgx_extract_device over a device-resident signal: asynchronous on `stream`, with the same
+ * per-stream scratch, first-call rule and graph-capture property. `samples` needs only float
+ * (4-byte) alignment. */
+int mgx_extract_signal_device(mgx_plan* plan, const float* samples, uint64_t num_samples, uint32_t hop,
+                              const mgx_outputs* outputs, void* stream);
+
+/* mgx_extract_host over a host signal; F = 1 behaves as mgx_extract_host on the first N
+ * samples. Each sample crosses PCIe once per chunk it belongs to, not once per buffer: a
+ * chunk of K buffers copies its span of (K - 1) * hop + N samples into the staging slot of
+ * the dense path and is extracted there at stride hop, so neighbouring chunks re-send only
+ * the N - hop samples they share. The slots stay the dense path's (65,536 * N floats): for
+ * hop > N a chunk holds as many buffers as its span allows there (fewer, down to one for a
+ * hop beyond the slot), and a batch small enough for the one-launch path (512 buffers)
+ * gathers its buffers densely into the pinned input buffer instead. */
+int mgx_extract_signal_host(mgx_plan* plan, const float* samples, uint64_t num_samples, uint32_t hop,
+                            const mgx_outputs* outputs);
+
+/* mgx_extract_host_pcm at a hop: decodeAudioData + getChannelData(channel) + the slicing
+ * loop. Each chunk's span of raw PCM crosses PCIe and is decoded once on the device. The
+ * `pcm_bytes` rule of mgx_extract_host_pcm holds: a short buffer is refused before any copy. */
+int mgx_extract_signal_host_pcm(mgx_plan* plan, const void* pcm, uint64_t pcm_bytes, uint64_t sample_frames,
+                                uint32_t format, uint32_t channels, uint32_t channel, uint32_t hop,
+                                const mgx_outputs* outputs);
 
 /* ---- Multi-device groups -------------------------------
  * Replaces nothing in the reference (single-threaded browser code); it exists because

@@ -243,6 +243,10 @@ typedef struct {
   uint64_t pcm_bytes;
   uint64_t pcm_frames;
   uint32_t pcm_format, pcm_channels, pcm_channel;
+  /* hop > 0 (extractSignal, extractWav with a hop): `frames` is one contiguous signal of nsamples samples (or
+   * the PCM's channel), cut into nframes = mgx_signal_frames() buffers that start every hop samples */
+  uint32_t hop;
+  uint64_t nsamples;
   mgx_outputs out;
   /* The outputs are written straight into JS ArrayBuffers (napi_create_arraybuffer), held by
    * references until the result object takes them. (External ArrayBuffers over malloc'd memory
@@ -334,6 +338,49 @@ static int job_prepare(napi_env env, job* j, napi_value frames_v, napi_value fea
   return job_alloc(env, j, feats);
 }
 
+/* hopSize: a positive integer that fits the C ABI's uint32. Plans created with `devices` (a group) take
+ * dense buffers only (include/meyda_gpu.h). */
+static int hop_of(napi_env env, job* j, napi_value v, uint32_t* hop) {
+  napi_valuetype t = napi_undefined;
+  double d = 0;
+  napi_typeof(env, v, &t);
+  if (t == napi_number) napi_get_value_double(env, v, &d);
+  if (t != napi_number || !(d >= 1) || d > 4294967295.0 || d != (double)(uint64_t)d) {
+    napi_throw_range_error(env, NULL, "hop must be a positive integer");
+    return 0;
+  }
+  if (j->box->group) {
+    napi_throw_error(env, NULL, "a hop is not supported on a plan created with `devices`: device groups take dense buffers only");
+    return 0;
+  }
+  *hop = (uint32_t)d;
+  return 1;
+}
+
+/* extractSignal(plan, samples, hop, features): one contiguous Float32Array, read in place at stride hop. */
+static int job_prepare_signal(napi_env env, job* j, napi_value samples_v, napi_value hop_v, napi_value feats) {
+  bool is_ta = false;
+  napi_typedarray_type tt = napi_int8_array;
+  size_t len = 0, off = 0;
+  void* data = NULL;
+  napi_value ab;
+  napi_is_typedarray(env, samples_v, &is_ta);
+  if (is_ta) napi_get_typedarray_info(env, samples_v, &tt, &len, &data, &ab, &off);
+  if (!is_ta || tt != napi_float32_array) {
+    napi_throw_type_error(env, NULL, "samples must be a Float32Array");
+    return 0;
+  }
+  if (!hop_of(env, j, hop_v, &j->hop)) return 0;
+  j->frames = (const float*)data;
+  j->nsamples = len;
+  int rc = mgx_signal_frames(len, j->box->desc.buffer_size, j->hop, &j->nframes);
+  if (rc) {
+    throw_mgx(env, rc);
+    return 0;
+  }
+  return job_alloc(env, j, feats);
+}
+
 /* Wanted outputs for j->nframes frames. */
 static int job_alloc(napi_env env, job* j, napi_value feats) {
   const uint32_t n = j->box->desc.buffer_size;
@@ -399,7 +446,7 @@ static int bytes_of(napi_env env, napi_value v, const unsigned char** data, size
   return 0;
 }
 
-static int job_prepare_wav(napi_env env, job* j, napi_value wav_v, napi_value feats, napi_value chan_v) {
+static int job_prepare_wav(napi_env env, job* j, napi_value wav_v, napi_value feats, napi_value chan_v, napi_value hop_v) {
   const unsigned char* data = NULL;
   size_t len = 0;
   if (!bytes_of(env, wav_v, &data, &len)) return 0;
@@ -428,6 +475,16 @@ static int job_prepare_wav(napi_env env, job* j, napi_value wav_v, napi_value fe
   j->pcm_channels = wi.channels;
   j->pcm_channel = ch;
   j->nframes = wi.sample_frames / j->box->desc.buffer_size;
+  napi_valuetype ht = napi_undefined;
+  if (hop_v) napi_typeof(env, hop_v, &ht);
+  if (ht != napi_undefined) {  /* the trailing hop: the buffers that start every hop samples */
+    if (!hop_of(env, j, hop_v, &j->hop)) return 0;
+    rc = mgx_signal_frames(wi.sample_frames, j->box->desc.buffer_size, j->hop, &j->nframes);
+    if (rc) {
+      throw_mgx(env, rc);
+      return 0;
+    }
+  }
   return job_alloc(env, j, feats);
 }
 
@@ -439,6 +496,11 @@ static void job_run(job* j) {
   }
   if (j->box->group)
     j->rc = mgx_group_extract_host(j->box->group, j->frames, j->nframes, &j->out);
+  else if (j->hop && j->pcm)
+    j->rc = mgx_extract_signal_host_pcm(j->box->plan, j->pcm, j->pcm_bytes, j->pcm_frames, j->pcm_format, j->pcm_channels,
+                                        j->pcm_channel, j->hop, &j->out);
+  else if (j->hop)
+    j->rc = mgx_extract_signal_host(j->box->plan, j->frames, j->nsamples, j->hop, &j->out);
   else if (j->pcm)
     j->rc = mgx_extract_host_pcm(j->box->plan, j->pcm, j->pcm_bytes, j->pcm_frames, j->pcm_format, j->pcm_channels,
                                  j->pcm_channel, &j->out);
@@ -473,12 +535,23 @@ static napi_value job_result(napi_env env, job* j) {
   return obj;
 }
 
-static napi_value extract_common(napi_env env, napi_callback_info info, int wav) {
-  size_t argc = 4;
-  napi_value argv[4];
+/* kind: the input of an extraction job */
+enum { IN_FRAMES = 0, IN_WAV = 1, IN_SIGNAL = 2 };
+
+static int job_prepare_kind(napi_env env, job* j, int kind, size_t argc, napi_value* argv) {
+  if (kind == IN_WAV) return job_prepare_wav(env, j, argv[1], argv[2], argc > 3 ? argv[3] : NULL, argc > 4 ? argv[4] : NULL);
+  if (kind == IN_SIGNAL) return job_prepare_signal(env, j, argv[1], argv[2], argv[3]);
+  return job_prepare(env, j, argv[1], argv[2]);
+}
+
+static napi_value extract_common(napi_env env, napi_callback_info info, int kind) {
+  size_t argc = 5;
+  napi_value argv[5];
   CHECK(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
-  if (argc < 3) {
-    napi_throw_type_error(env, NULL, wav ? "extractWav(plan, wavBytes, features[, channel])" : "extract(plan, frames, features)");
+  if (argc < (kind == IN_SIGNAL ? 4u : 3u)) {
+    napi_throw_type_error(env, NULL, kind == IN_WAV ? "extractWav(plan, wavBytes, features[, channel[, hop]])"
+                                   : kind == IN_SIGNAL ? "extractSignal(plan, samples, hop, features)"
+                                                       : "extract(plan, frames, features)");
     return NULL;
   }
   job j;
@@ -489,8 +562,7 @@ static napi_value extract_common(napi_env env, napi_callback_info info, int wav)
     napi_throw_error(env, NULL, "plan is busy with an async extraction");
     return NULL;
   }
-  if (!(wav ? job_prepare_wav(env, &j, argv[1], argv[2], argc > 3 ? argv[3] : NULL)
-            : job_prepare(env, &j, argv[1], argv[2]))) {
+  if (!job_prepare_kind(env, &j, kind, argc, argv)) {
     job_free_buffers(env, &j);
     return NULL;
   }
@@ -595,8 +667,9 @@ static napi_value extract_into(napi_env env, napi_callback_info info) {
   return argv[3];
 }
 
-static napi_value extract_sync(napi_env env, napi_callback_info info) { return extract_common(env, info, 0); }
-static napi_value extract_wav_sync(napi_env env, napi_callback_info info) { return extract_common(env, info, 1); }
+static napi_value extract_sync(napi_env env, napi_callback_info info) { return extract_common(env, info, IN_FRAMES); }
+static napi_value extract_wav_sync(napi_env env, napi_callback_info info) { return extract_common(env, info, IN_WAV); }
+static napi_value extract_signal_sync(napi_env env, napi_callback_info info) { return extract_common(env, info, IN_SIGNAL); }
 
 static void async_execute(napi_env env, void* data) {
   (void)env;
@@ -623,13 +696,14 @@ static void async_complete(napi_env env, napi_status status, void* data) {
   if (box->finalized) plan_box_free(box);
 }
 
-static napi_value extract_async_common(napi_env env, napi_callback_info info, int wav) {
-  size_t argc = 4;
-  napi_value argv[4];
+static napi_value extract_async_common(napi_env env, napi_callback_info info, int kind) {
+  size_t argc = 5;
+  napi_value argv[5];
   CHECK(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
-  if (argc < 3) {
-    napi_throw_type_error(env, NULL, wav ? "extractWavAsync(plan, wavBytes, features[, channel])"
-                                         : "extractAsync(plan, frames, features)");
+  if (argc < (kind == IN_SIGNAL ? 4u : 3u)) {
+    napi_throw_type_error(env, NULL, kind == IN_WAV ? "extractWavAsync(plan, wavBytes, features[, channel[, hop]])"
+                                   : kind == IN_SIGNAL ? "extractSignalAsync(plan, samples, hop, features)"
+                                                       : "extractAsync(plan, frames, features)");
     return NULL;
   }
   job* j = (job*)calloc(1, sizeof *j);
@@ -640,8 +714,7 @@ static napi_value extract_async_common(napi_env env, napi_callback_info info, in
     napi_throw_error(env, NULL, "plan is busy with an async extraction");
     return NULL;
   }
-  if (!(wav ? job_prepare_wav(env, j, argv[1], argv[2], argc > 3 ? argv[3] : NULL)
-            : job_prepare(env, j, argv[1], argv[2]))) {
+  if (!job_prepare_kind(env, j, kind, argc, argv)) {
     job_free_buffers(env, j);
     free(j);
     return NULL;
@@ -657,8 +730,32 @@ static napi_value extract_async_common(napi_env env, napi_callback_info info, in
   return promise;
 }
 
-static napi_value extract_async(napi_env env, napi_callback_info info) { return extract_async_common(env, info, 0); }
-static napi_value extract_wav_async(napi_env env, napi_callback_info info) { return extract_async_common(env, info, 1); }
+static napi_value extract_async(napi_env env, napi_callback_info info) { return extract_async_common(env, info, IN_FRAMES); }
+static napi_value extract_wav_async(napi_env env, napi_callback_info info) { return extract_async_common(env, info, IN_WAV); }
+static napi_value extract_signal_async(napi_env env, napi_callback_info info) { return extract_async_common(env, info, IN_SIGNAL); }
+
+/* signalFrames(numSamples, bufferSize, hop): mgx_signal_frames (host only). */
+static napi_value signal_frames(napi_env env, napi_callback_info info) {
+  size_t argc = 3;
+  napi_value argv[3], r;
+  CHECK(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  double v[3] = {0, 0, 0};
+  for (size_t i = 0; i < 3; ++i) {
+    napi_valuetype t = napi_undefined;
+    if (i < argc) napi_typeof(env, argv[i], &t);
+    if (t == napi_number) napi_get_value_double(env, argv[i], &v[i]);
+    if (t != napi_number || !(v[i] >= 0) || v[i] > 9007199254740992.0 || v[i] != (double)(uint64_t)v[i] ||
+        (i > 0 && v[i] > 4294967295.0)) {
+      napi_throw_range_error(env, NULL, "signalFrames(numSamples, bufferSize, hop): non-negative integers");
+      return NULL;
+    }
+  }
+  uint64_t f = 0;
+  int rc = mgx_signal_frames((uint64_t)v[0], (uint32_t)v[1], (uint32_t)v[2], &f);
+  if (rc) return throw_mgx(env, rc);
+  CHECK(napi_create_double(env, (double)f, &r));
+  return r;
+}
 
 static napi_value wav_parse(napi_env env, napi_callback_info info) {
   size_t argc = 1;
@@ -782,6 +879,9 @@ static napi_value init(napi_env env, napi_value exports) {
       {"extractAsync", NULL, extract_async, NULL, NULL, NULL, napi_enumerable, NULL},
       {"extractWav", NULL, extract_wav_sync, NULL, NULL, NULL, napi_enumerable, NULL},
       {"extractWavAsync", NULL, extract_wav_async, NULL, NULL, NULL, napi_enumerable, NULL},
+      {"extractSignal", NULL, extract_signal_sync, NULL, NULL, NULL, napi_enumerable, NULL},
+      {"extractSignalAsync", NULL, extract_signal_async, NULL, NULL, NULL, napi_enumerable, NULL},
+      {"signalFrames", NULL, signal_frames, NULL, NULL, NULL, napi_enumerable, NULL},
       {"wavParse", NULL, wav_parse, NULL, NULL, NULL, napi_enumerable, NULL},
       {"hostTables", NULL, host_tables, NULL, NULL, NULL, napi_enumerable, NULL},
       {"isPowerOfTwo", NULL, is_pow2, NULL, NULL, NULL, napi_enumerable, NULL},

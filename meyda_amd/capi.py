@@ -34,6 +34,8 @@ EXPORTS = ["mgx_plan_desc_init", "mgx_plan_create", "mgx_plan_destroy", "mgx_pla
            "mgx_get_host_tables", "mgx_is_power_of_two", "mgx_feature_index", "mgx_feature_name",
            "mgx_feature_info", "mgx_device_count", "mgx_abi_version", "mgx_last_error",
            "mgx_wav_parse", "mgx_pcm_decode_device", "mgx_extract_host_pcm",
+           "mgx_signal_frames", "mgx_extract_signal_device", "mgx_extract_signal_host",
+           "mgx_extract_signal_host_pcm",
            "mgx_shard_range", "mgx_packed_layout", "mgx_comm_unique_id", "mgx_group_create",
            "mgx_group_create_rank", "mgx_group_create_loopback", "mgx_group_create_loopback_rccl", "mgx_group_destroy",
            "mgx_group_info", "mgx_group_comm_info", "mgx_group_extract_device", "mgx_group_extract_host"]
@@ -134,6 +136,14 @@ def lib():
         L.mgx_extract_host_pcm.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32,
                                            ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(Outputs)]
         u64p = ctypes.POINTER(ctypes.c_uint64)
+        L.mgx_signal_frames.argtypes = [ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, u64p]
+        L.mgx_extract_signal_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32,
+                                                ctypes.POINTER(Outputs), ctypes.c_void_p]
+        L.mgx_extract_signal_host.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32,
+                                              ctypes.POINTER(Outputs)]
+        L.mgx_extract_signal_host_pcm.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64,
+                                                  ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
+                                                  ctypes.POINTER(Outputs)]
         L.mgx_shard_range.argtypes = [ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, u64p, u64p]
         L.mgx_packed_layout.argtypes = [ctypes.POINTER(PlanDesc), ctypes.c_uint32, ctypes.c_uint64, u64p]
         L.mgx_packed_layout.restype = ctypes.c_uint64
@@ -197,6 +207,13 @@ def host_tables(**kw):
                                                   "bark_limits", "mel_bins", "dct")])
     check(lib().mgx_get_host_tables(ctypes.byref(d), ctypes.byref(ht)))
     return t
+
+
+def signal_frames(num_samples, n, hop):
+    """Buffers of `n` samples, `hop` apart, in a signal of `num_samples` (mgx_signal_frames; host only)."""
+    f = ctypes.c_uint64()
+    check(lib().mgx_signal_frames(num_samples, n, hop, ctypes.byref(f)))
+    return f.value
 
 
 def device_count():
@@ -277,7 +294,32 @@ class Plan:
         self.extract_device(frames.data_ptr(), frames.shape[0], o, stream)
         return out
 
+    def extract_signal_device(self, samples_ptr, num_samples, hop, outputs, stream=None):
+        """Launch on a device signal cut every `hop` samples (async; outputs sized for signal_frames())."""
+        check(lib().mgx_extract_signal_device(self._h, ctypes.c_void_p(samples_ptr), num_samples, hop,
+                                              ctypes.byref(outputs), ctypes.c_void_p(stream or 0)))
+
+    def extract_signal_torch(self, samples, hop, features, stream=None):
+        """samples: a 1-D float32 CUDA tensor (any 4-byte alignment). Returns a dict of device tensors over
+        the signal_frames(len(samples), N, hop) overlapping buffers; the buffers are not materialised."""
+        import torch
+        assert samples.is_cuda and samples.dtype == torch.float32 and samples.is_contiguous() and samples.dim() == 1
+        S = samples.shape[0]
+        out, o = self.alloc_outputs(signal_frames(S, self.n, hop), features, device=samples.device)
+        if stream is None:
+            stream = torch.cuda.current_stream(samples.device).cuda_stream
+        self.extract_signal_device(samples.data_ptr(), S, hop, o, stream)
+        return out
+
     # ------------------------------------------------------------------ host
+    def extract_signal(self, samples, hop, features):
+        """Host numpy signal in / numpy out, buffers every `hop` samples (stages the signal, not the buffers)."""
+        samples = np.ascontiguousarray(samples, dtype=np.float32)
+        assert samples.ndim == 1
+        out, o = self._host_outputs(signal_frames(samples.size, self.n, hop), features)
+        check(lib().mgx_extract_signal_host(self._h, samples.ctypes.data, samples.size, hop, ctypes.byref(o)))
+        return out
+
     def extract(self, frames, features):
         """Host numpy in / numpy out (stages through the device)."""
         frames = np.ascontiguousarray(frames, dtype=np.float32)
@@ -287,23 +329,30 @@ class Plan:
         check(lib().mgx_extract_host(self._h, frames.ctypes.data, F, ctypes.byref(o)))
         return out
 
-    def extract_pcm(self, pcm, sample_frames, fmt, channels, channel=0, features=()):
+    def extract_pcm(self, pcm, sample_frames, fmt, channels, channel=0, features=(), hop=None):
         """Raw interleaved PCM (bytes / numpy buffer) in host memory -> features of the
-        floor(sample_frames / N) buffers of `channel` (decoded on the device)."""
+        floor(sample_frames / N) buffers of `channel` (decoded on the device); with `hop`, of the
+        signal_frames(sample_frames, N, hop) buffers that start every `hop` samples."""
         buf = np.frombuffer(pcm, dtype=np.uint8) if not isinstance(pcm, np.ndarray) else pcm.view(np.uint8)
         buf = np.ascontiguousarray(buf)
         fmt = PCM_FORMATS[fmt] if isinstance(fmt, str) else fmt
-        F = sample_frames // self.n
-        out, o = self._host_outputs(F, features)
-        check(lib().mgx_extract_host_pcm(self._h, buf.ctypes.data, buf.size, sample_frames, fmt, channels, channel,
-                                         ctypes.byref(o)))
+        if hop is None:
+            out, o = self._host_outputs(sample_frames // self.n, features)
+            check(lib().mgx_extract_host_pcm(self._h, buf.ctypes.data, buf.size, sample_frames, fmt, channels, channel,
+                                             ctypes.byref(o)))
+            return out
+        out, o = self._host_outputs(signal_frames(sample_frames, self.n, hop), features)
+        check(lib().mgx_extract_signal_host_pcm(self._h, buf.ctypes.data, buf.size, sample_frames, fmt, channels,
+                                                channel, hop, ctypes.byref(o)))
         return out
 
-    def extract_wav(self, wav_bytes, features, channel=0):
-        """A whole .wav file (bytes) -> features of its full buffers (channel `channel`)."""
+    def extract_wav(self, wav_bytes, features, channel=0, hop=None):
+        """A whole .wav file (bytes) -> features of its full buffers (channel `channel`), disjoint or,
+        with `hop`, every `hop` samples."""
         info = wav_parse(wav_bytes)
         data = np.frombuffer(wav_bytes, dtype=np.uint8)[info["data_offset"]:info["data_offset"] + info["data_bytes"]]
-        return self.extract_pcm(data, info["sample_frames"], info["pcm_format"], info["channels"], channel, features)
+        return self.extract_pcm(data, info["sample_frames"], info["pcm_format"], info["channels"], channel, features,
+                                hop=hop)
 
     def _host_outputs(self, F, features):
         n = self.n

@@ -293,6 +293,13 @@ struct KlTab {
 // The HBM-bound time-only features ran 12 % faster with them on a 1 GiB batch (5.9 TB/s) and the
 // all-feature launch 1.2 % (profiles/r05_prologue_ab.txt); a smaller batch keeps plain loads, because
 // then it stays in the MALL between launches of the same frames (C2's 128 MiB: 12 % slower with nt).
+// A signal launch (KernelArgs::frame_stride != N, mgx_extract_signal_*) reads frame f at f * stride: below N
+// the frames overlap and a line is read by up to ceil(N / stride) frames -- mostly the 4 consecutive frames
+// of a wave's batch and the 16 of a workgroup, close together in time. Those keep plain loads whatever the
+// signal's size (plan.cpp): N = 1024, 262,144 frames at hop 512 / 256, the time-only set 0.136 / 0.119 ms
+// plain against 0.163 / 0.149 ms nt (dense 0.178), all features -1.8 / -3.0 % plain, +0.5 / -0.8 % nt
+// (profiles/signal_hop.txt). At stride >= N the dense rule holds, by the samples touched (hop = N, 1 GiB,
+// time-only: plain +9.5 %).
 // A spectrum output element (amplitude, power, complex: 2-8 KB per frame, written once and never
 // read back): a non-temporal store, which streams past the caches instead of filling them (every
 // output at N = 1024: -8.1..-8.8 % per launch; C2's 1 GiB batch -0.7 %, outputs identical; the same
@@ -2075,6 +2082,8 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(RES ? 
   const void* const img_p = ap->t.lds_image;
   // (INL: the launch's one frame in the kernarg segment, KernelArgsInline::frame)
   const float* const frames_p = INL ? inline_frame_ptr() : ap->frames;
+  // (the samples from one frame's start to the next: N, or a signal launch's hop)
+  const uint64_t fstride = ap->frame_stride;
   const float* const win_p = ap->t.window;
   const int* const klist_p = ap->t.klist;
   // ... with one word of every other 64-byte line of the arguments in the same burst, so the scalar cache
@@ -2083,7 +2092,7 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(RES ? 
   static_assert(sizeof(KernelArgs) <= 8 * 64, "the argument lines touched below");
   const auto kw = reinterpret_cast<const __attribute__((address_space(4))) uint32_t*>(ap);
   const uint32_t t2 = kw[32], t3 = kw[48], t4 = kw[64], t5 = kw[80], t6 = kw[96], t7 = kw[(sizeof(KernelArgs) - 4) / 4];
-  asm volatile("" ::"s"(nf), "s"(nr32), "s"(nimg), "s"(grid), "s"(img_p), "s"(frames_p), "s"(win_p), "s"(klist_p), "s"(t2),
+  asm volatile("" ::"s"(nf), "s"(nr32), "s"(nimg), "s"(grid), "s"(img_p), "s"(frames_p), "s"(fstride), "s"(win_p), "s"(klist_p), "s"(t2),
                "s"(t3), "s"(t4), "s"(t5), "s"(t6), "s"(t7));
 
   int lp[G::NPASS];
@@ -2173,8 +2182,10 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(RES ? 
     uint64_t f = b * FPW + j;
     f = f < nf ? f : nf - 1;
     // (wave-uniform, uniform_ptr: the lane's offset is added at each load)
+    // (the frame's start: a 64-bit scalar product with the launch's stride, KernelArgs::frame_stride -- the
+    // clamped index keeps the last load inside frame nf - 1, the signal's last whole frame)
     const float* base = INL ? inline_frame_ptr() : args_ptr()->frames;
-    return (GF)uniform_ptr(gbl(base) + f * (uint64_t)N);
+    return (GF)uniform_ptr(gbl(base) + f * args_ptr()->frame_stride);
   };
   auto load = [&](float (&xv)[CH], uint64_t b, int j) {
     ld_frame<CHAIN>(xv, frame_ptr(b, j), (unsigned)lane, ntf);
@@ -2201,7 +2212,7 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(RES ? 
   }
   if constexpr (G::PREFETCH && !INL) {  // (load(xn, b0, 0) with the burst's frame pointer)
     const uint64_t f = b0 * FPW < nf ? b0 * FPW : nf - 1;
-    ld_frame<CHAIN>(xn, (GF)uniform_ptr(gbl(frames_p) + f * (uint64_t)N), (unsigned)lane, ntf);
+    ld_frame<CHAIN>(xn, (GF)uniform_ptr(gbl(frames_p) + f * fstride), (unsigned)lane, ntf);
   }
   // the output pointers, then the image's chunks
   if (threadIdx.x < MGX_NUM_SCALARS) reinterpret_cast<void**>(smem + LY::kc_off)[threadIdx.x] = kp;

@@ -60,6 +60,11 @@ struct DevTables {
 struct KernelArgs {
   const float* frames;
   uint64_t num_frames;
+  // Samples between the starts of consecutive frames: frame f is frames[f * frame_stride .. + N). N for
+  // dense frames (every launch but a signal launch); the hop of mgx_extract_signal_* (any value >= 1:
+  // below N the frames overlap, above it samples are skipped). In the arguments' first line, beside the
+  // frame pointer it multiplies into (kernels.hip frame_ptr).
+  uint64_t frame_stride;
   DevTables t;
   mgx_outputs out;
   double sample_rate;
@@ -79,7 +84,7 @@ struct KernelArgs {
   int need_energy;       // rms or energy: the wave sum of the squares (SUB kernel)
   int need_zcr;          // zcr: the sign-change ballots (SUB kernel)
   int scal_defer;        // the scalars by windows (scalar_pass): a spectrum is computed and a scalar requested
-  int nt_frames;         // the frames read with non-temporal loads: the batch is larger than the MALL (kernels.hip ld_frame)
+  int nt_frames;         // the frames read with non-temporal loads: the samples read are more than the MALL holds (kernels.hip ld_frame)
   // Small host batches (plan.cpp extract_host_small): every wave counts itself in done_count at
   // its end, after its output stores are visible to the host, and the last one sets the mapped
   // host word done_flag to done_seq, which the host polls instead of synchronising the stream.
@@ -120,7 +125,7 @@ constexpr uint32_t kResStop = 0xFFFFFFFFu;  // a request number that stops the r
 // its frame in the kernel arguments, after the KernelArgs: the kernel's first loads read it from the
 // kernarg segment, whose address the wave holds from its first instruction, instead of waiting for the
 // arguments before it can issue the frame's read of pinned host memory over PCIe.
-constexpr int kInlineMaxN = 1024;  // (4,528 bytes of arguments at N = 1024: tools/ubench/kernarg_size.hip runs 4.8 KB)
+constexpr int kInlineMaxN = 1024;  // (4,592 bytes of arguments at N = 1024: tools/ubench/kernarg_size.hip runs 4.8 KB)
 template <int N>
 struct KernelArgsInline {
   KernelArgs a;

@@ -491,6 +491,7 @@ struct mgx_plan {
   // a launch whose frames exceed this many bytes reads them with non-temporal loads (KernelArgs::nt_frames):
   // the MALL's 256 MiB (MGX_NT_MIN_MB overrides, in MiB)
   uint64_t nt_min_bytes = 256ull << 20;
+  bool nt_forced = false;  // MGX_NT_MIN_MB was given: it also decides for overlapping frames (plain by default)
   // the small path's completion word (KernelArgs::done_flag): a mapped host word, the device
   // counter of finished waves and the launch sequence number
   uint32_t* h_done = nullptr;
@@ -520,7 +521,7 @@ namespace {
 struct ResidentLaunch {
   uint32_t seq;
 };
-int extract_device_impl(mgx_plan* p, const float* frames, uint64_t nframes, const mgx_outputs* o, void* stream,
+int extract_device_impl(mgx_plan* p, const float* frames, uint64_t nframes, uint64_t stride, const mgx_outputs* o, void* stream,
                         const uint32_t* done, const float* inline_frame = nullptr, const ResidentLaunch* res = nullptr);
 void resident_stop(mgx_plan* p);
 }  // namespace
@@ -665,7 +666,10 @@ int mgx_plan_create(const mgx_plan_desc* d, mgx_plan** out) {
   }
   if (const char* sb = getenv("MGX_SMALL_BATCH_FRAMES")) p->small_max = (uint64_t)std::max(0, atoi(sb));
   if (const char* pp = getenv("MGX_POOL_PCT")) p->pool_pct = std::min(50, std::max(0, atoi(pp)));
-  if (const char* nm = getenv("MGX_NT_MIN_MB")) p->nt_min_bytes = (uint64_t)std::max(0, atoi(nm)) << 20;
+  if (const char* nm = getenv("MGX_NT_MIN_MB")) {
+    p->nt_min_bytes = (uint64_t)std::max(0, atoi(nm)) << 20;
+    p->nt_forced = true;
+  }
   if (const char* ri = getenv("MGX_RESIDENT_IDLE_MS")) p->res_idle_ms = (uint32_t)std::min(10000, std::max(1, atoi(ri)));
   if (const char* rp = getenv("MGX_RESIDENT_POLL")) p->res_light = strcmp(rp, "light") == 0;
 
@@ -808,7 +812,25 @@ int mgx_plan_get_desc(const mgx_plan* p, mgx_plan_desc* out) {
 }
 
 int mgx_extract_device(mgx_plan* p, const float* frames, uint64_t nframes, const mgx_outputs* o, void* stream) {
-  return extract_device_impl(p, frames, nframes, o, stream, nullptr);
+  return extract_device_impl(p, frames, nframes, p ? (uint64_t)p->n : 0, o, stream, nullptr);
+}
+
+// src/meyda.js:69-91 delivers disjoint buffers; with a hop the same buffers start every `hop` samples
+int mgx_signal_frames(uint64_t num_samples, uint32_t buffer_size, uint32_t hop, uint64_t* num_frames) {
+  if (!num_frames) return fail(MGX_E_INVALID_ARGUMENT, "num_frames is NULL");
+  if (buffer_size == 0) return fail(MGX_E_INVALID_ARGUMENT, "buffer_size is 0");
+  if (hop == 0) return fail(MGX_E_INVALID_ARGUMENT, "hop is 0 (a hop of at least one sample)");
+  *num_frames = num_samples < buffer_size ? 0 : (num_samples - buffer_size) / hop + 1;
+  return MGX_OK;
+}
+
+int mgx_extract_signal_device(mgx_plan* p, const float* samples, uint64_t num_samples, uint32_t hop, const mgx_outputs* o,
+                              void* stream) {
+  if (!p || !o) return fail(MGX_E_INVALID_ARGUMENT, "NULL plan or outputs");
+  uint64_t nframes = 0;
+  const int rc = mgx_signal_frames(num_samples, (uint32_t)p->n, hop, &nframes);
+  if (rc) return rc;
+  return extract_device_impl(p, samples, nframes, hop, o, stream, nullptr);
 }
 
 }  // extern "C"
@@ -847,11 +869,12 @@ int add_stream_scratch(mgx_plan* p, void* stream) {
   return MGX_OK;
 }
 
-// mgx_extract_device, and with `done` (the small host path) the launch's completion word; inline_frame
+// mgx_extract_device and mgx_extract_signal_device (stride: the samples from one frame's start to the next, N
+// for dense frames), and with `done` (the small host path) the launch's completion word; inline_frame
 // (the small path's one frame in host memory) goes into the kernel arguments where the kernel takes it
 // (mgx::launch_extract); res: the plan's resident launch (resident_request). Any other launch ends the
 // plan's resident one first, so the plan's own work never waits behind it or shares the device with it.
-int extract_device_impl(mgx_plan* p, const float* frames, uint64_t nframes, const mgx_outputs* o, void* stream,
+int extract_device_impl(mgx_plan* p, const float* frames, uint64_t nframes, uint64_t stride, const mgx_outputs* o, void* stream,
                         const uint32_t* done, const float* inline_frame, const ResidentLaunch* res) {
   if (!p || !o) return fail(MGX_E_INVALID_ARGUMENT, "NULL plan or outputs");
   if (nframes == 0) return MGX_OK;
@@ -862,6 +885,7 @@ int extract_device_impl(mgx_plan* p, const float* frames, uint64_t nframes, cons
   mgx::KernelArgs a{};
   a.frames = frames;
   a.num_frames = nframes;
+  a.frame_stride = stride;
   a.t = p->t;
   a.out = *o;
   a.sample_rate = p->d.sample_rate;
@@ -908,7 +932,14 @@ int extract_device_impl(mgx_plan* p, const float* frames, uint64_t nframes, cons
   // its lines would evict the ones the launch reads back (the scalar windows); N = 1024 all features
   // -1.2 % per launch, the HBM-bound time-only set -12 % (profiles/r05_prologue_ab.txt, r06_nt_frames.txt).
   // A smaller one keeps plain loads: launches over the same frames then find them in the MALL (C2).
-  a.nt_frames = nframes * (uint64_t)p->n * sizeof(float) > p->nt_min_bytes;
+  // A signal launch (stride != N) decides by the samples it touches, ((F - 1) stride + N) floats: the same
+  // figure for dense frames. Overlapping frames (stride < N) are read again by the next frames of the batch
+  // and the workgroup, and plain loads keep their lines for them: N = 1024 at hop 512 / 256, a 512 / 256 MiB
+  // signal, the time-only set 0.136 / 0.119 ms plain against 0.163 / 0.149 ms non-temporal (dense frames
+  // 0.178), all features -1.8 / -3.0 % plain against +0.5 / -0.8 % (profiles/signal_hop.txt). So they are read
+  // non-temporally only when MGX_NT_MIN_MB is set (the tests and tools/signal_bench.py force either kind).
+  const bool overlap = stride < (uint64_t)p->n;
+  a.nt_frames = (!overlap || p->nt_forced) && ((nframes - 1) * stride + (uint64_t)p->n) * sizeof(float) > p->nt_min_bytes;
   hipError_t e = hipSetDevice(p->d.device);
   if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
   if (res) {
@@ -1108,7 +1139,7 @@ int resident_request(mgx_plan* p, const mgx_outputs* o, const mgx_outputs& d, ui
   auto start = [&]() -> int {
     __atomic_store_n(exitw, 0u, __ATOMIC_RELEASE);
     const ResidentLaunch rl{seq};
-    const int rc = extract_device_impl(p, p->t.window, 1, &d, p->s_res, p->d_done_map, nullptr, &rl);
+    const int rc = extract_device_impl(p, p->t.window, 1, (uint64_t)p->n, &d, p->s_res, p->d_done_map, nullptr, &rl);
     if (rc) return rc;
     p->res_live = true;
     g_resident_live[p->d.device >= 0 && p->d.device < kMaxDevices ? p->d.device : 0].fetch_add(1, std::memory_order_relaxed);
@@ -1148,12 +1179,14 @@ int resident_request(mgx_plan* p, const mgx_outputs* o, const mgx_outputs& d, ui
 // buffer, one synchronisation, the features out to the caller's arrays. `fill(dst)` writes the
 // batch's float32 frames to host memory at dst. The buffers are coherent (fine-grained) host
 // memory mapped into the device, so no cache of either side holds a stale copy between calls.
+// stride: the samples from one frame's start to the next in what `fill` writes, (nframes - 1) stride + N
+// samples in all (N: dense frames; a signal's hop <= N: its samples as they are, each written once).
 template <typename Fill>
-int extract_host_small(mgx_plan* p, uint64_t nframes, const mgx_outputs* o, Fill fill) {
+int extract_host_small(mgx_plan* p, uint64_t nframes, uint64_t stride, const mgx_outputs* o, Fill fill) {
   const int n = p->n, L = p->L;
   const size_t ss = p->d.scalar_f64 ? 8 : 4;
   const size_t nb = mgx::kBark, nc = p->d.num_mfcc_coeffs;
-  const size_t in_bytes = nframes * (size_t)n * sizeof(float);
+  const size_t in_bytes = ((nframes - 1) * (size_t)stride + (size_t)n) * sizeof(float);
   const size_t out_bytes = out_bytes_per_frame(p, o) * nframes + 20 * 256;
   hipError_t e = hipSetDevice(p->d.device);
   if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
@@ -1229,7 +1262,9 @@ int extract_host_small(mgx_plan* p, uint64_t nframes, const mgx_outputs* o, Fill
     if (e != hipSuccess) return hip_fail(e, "hipHostMalloc(completion word)");
     *hd = 0;
     e = hipMalloc(reinterpret_cast<void**>(&p->d_done_count), sizeof(uint32_t));
-    if (e == hipSuccess) e = hipMemset(p->d_done_count, 0, sizeof(uint32_t));
+    // (on the stream the launches run on: a null-stream memset of device memory may return before it has
+    // run, and the non-blocking s_comp does not wait for it -- the first launch's waves could count first)
+    if (e == hipSuccess) e = hipMemsetAsync(p->d_done_count, 0, sizeof(uint32_t), p->s_comp);
     if (e != hipSuccess) {
       (void)hipHostFree(hd);
       return hip_fail(e, "completion counter");
@@ -1264,7 +1299,7 @@ int extract_host_small(mgx_plan* p, uint64_t nframes, const mgx_outputs* o, Fill
     if (rc) return rc;
   } else {
     // (one frame: also handed over in the kernel arguments, read there by the kernels that take it)
-    rc = extract_device_impl(p, static_cast<const float*>(din), nframes, &d, p->s_comp, word_wait ? nullptr : ddone,
+    rc = extract_device_impl(p, static_cast<const float*>(din), nframes, stride, &d, p->s_comp, word_wait ? nullptr : ddone,
                              nframes == 1 ? p->h_in : nullptr);
     if (rc) {
       (void)hipStreamSynchronize(p->s_comp);
@@ -1330,8 +1365,19 @@ int extract_host_small(mgx_plan* p, uint64_t nframes, const mgx_outputs* o, Fill
   return MGX_OK;
 }
 
+// The frames of a chunk, for a signal cut at `hop` (signal_chunk_frames(p, n) = kHostChunk for dense
+// frames): a chunk of K frames occupies (K - 1) hop + N floats of its slot, and a slot holds kHostChunk N,
+// so up to hop = N a chunk keeps its kHostChunk frames, and a larger hop (samples skipped) gets as many
+// frames as still fit, one at least.
+uint64_t signal_chunk_frames(const mgx_plan* p, uint64_t hop) {
+  const uint64_t n = (uint64_t)p->n;
+  return hop <= n ? kHostChunk : std::max<uint64_t>(1, (kHostChunk * n - n) / hop + 1);
+}
+
+// stride: the samples between the starts of consecutive frames in a slot (N: dense frames; a signal's
+// hop: `fill` then writes a chunk's (cnt - 1) stride + N samples); chunk_max: frames per chunk.
 template <typename Fill>
-int extract_host_chunked(mgx_plan* p, uint64_t nframes, const mgx_outputs* o, Fill fill) {
+int extract_host_chunked(mgx_plan* p, uint64_t nframes, uint64_t stride, uint64_t chunk_max, const mgx_outputs* o, Fill fill) {
   const int n = p->n, L = p->L;
   const size_t ss = p->d.scalar_f64 ? 8 : 4;
   const size_t nb = mgx::kBark, nc = p->d.num_mfcc_coeffs;
@@ -1340,8 +1386,10 @@ int extract_host_chunked(mgx_plan* p, uint64_t nframes, const mgx_outputs* o, Fi
   for (int i = 0; i < MGX_NUM_SCALARS; ++i) per += o->scalars[i] ? ss : 0;
   per += (o->loudness_specific ? nb * 4 : 0) + (o->mfcc ? nc * 4 : 0) + (o->amplitude_spectrum ? L * 4 : 0) +
          (o->power_spectrum ? L * 4 : 0) + (o->complex_real ? 2 * (size_t)n * 4 : 0);
-  const uint64_t chunk = std::min<uint64_t>(nframes, kHostChunk);
-  int rc = ensure_host_staging(p, chunk, per * chunk + 4096);
+  const uint64_t chunk = std::min<uint64_t>(nframes, chunk_max);
+  // (the slot in whole frames of N floats: the chunk's span, at most kHostChunk frames' worth)
+  const uint64_t slot_frames = ((chunk - 1) * stride + (uint64_t)n + (uint64_t)n - 1) / (uint64_t)n;
+  int rc = ensure_host_staging(p, slot_frames, per * chunk + 4096);
   if (rc) return rc;
   const uint64_t nch = (nframes + chunk - 1) / chunk;
   hipError_t e = hipSuccess;
@@ -1370,7 +1418,7 @@ int extract_host_chunked(mgx_plan* p, uint64_t nframes, const mgx_outputs* o, Fi
     e = hipStreamWaitEvent(p->s_comp, p->ev_loaded[sl], 0);
     if (e == hipSuccess && i >= 2) e = hipStreamWaitEvent(p->s_comp, p->ev_back[sl], 0);
     if (e != hipSuccess) break;
-    rc = mgx_extract_device(p, p->s_frames[sl], cnt, &d, p->s_comp);
+    rc = extract_device_impl(p, p->s_frames[sl], cnt, stride, &d, p->s_comp, nullptr);
     if (rc) return fail_sync(rc);
     e = hipEventRecord(p->ev_done[sl], p->s_comp);
     // chunk i+1's frames into the other slot once chunk i-1's extraction has read them
@@ -1428,13 +1476,44 @@ int mgx_extract_host(mgx_plan* p, const float* frames, uint64_t nframes, const m
     return fail(MGX_E_INVALID_ARGUMENT, "complex_real and complex_imag must be given together");
   const int n = p->n;
   if (nframes <= p->small_max)
-    return extract_host_small(p, nframes, o, [&](float* dst) {
+    return extract_host_small(p, nframes, (uint64_t)n, o, [&](float* dst) {
       memcpy(dst, frames, nframes * (size_t)n * sizeof(float));
       return MGX_OK;
     });
-  return extract_host_chunked(p, nframes, o, [&](uint64_t f0, uint64_t cnt, int slot, hipStream_t st) {
+  return extract_host_chunked(p, nframes, (uint64_t)n, kHostChunk, o, [&](uint64_t f0, uint64_t cnt, int slot, hipStream_t st) {
     hipError_t e = hipMemcpyAsync(p->s_frames[slot], frames + f0 * n, cnt * n * sizeof(float), hipMemcpyHostToDevice, st);
     return e == hipSuccess ? MGX_OK : hip_fail(e, "hipMemcpyAsync(frames)");
+  });
+}
+
+int mgx_extract_signal_host(mgx_plan* p, const float* samples, uint64_t num_samples, uint32_t hop, const mgx_outputs* o) {
+  if (!p || !o) return fail(MGX_E_INVALID_ARGUMENT, "NULL plan or outputs");
+  uint64_t nframes = 0;
+  int rc = mgx_signal_frames(num_samples, (uint32_t)p->n, hop, &nframes);
+  if (rc) return rc;
+  if (nframes == 0) return MGX_OK;
+  if (!samples) return fail(MGX_E_INVALID_ARGUMENT, "samples is NULL");
+  if ((o->complex_real == nullptr) != (o->complex_imag == nullptr))
+    return fail(MGX_E_INVALID_ARGUMENT, "complex_real and complex_imag must be given together");
+  const int n = p->n;
+  const uint64_t h = hop;
+  if (nframes <= p->small_max) {
+    // up to hop = N the samples as they are (each written to the pinned buffer once, read at stride hop);
+    // a larger hop gathers its frames densely, so the buffer never exceeds the dense path's
+    if (h <= (uint64_t)n)
+      return extract_host_small(p, nframes, h, o, [&](float* dst) {
+        memcpy(dst, samples, ((nframes - 1) * h + (size_t)n) * sizeof(float));
+        return MGX_OK;
+      });
+    return extract_host_small(p, nframes, (uint64_t)n, o, [&](float* dst) {
+      for (uint64_t f = 0; f < nframes; ++f) memcpy(dst + f * n, samples + f * h, (size_t)n * sizeof(float));
+      return MGX_OK;
+    });
+  }
+  return extract_host_chunked(p, nframes, h, signal_chunk_frames(p, h), o, [&](uint64_t f0, uint64_t cnt, int slot, hipStream_t st) {
+    hipError_t e = hipMemcpyAsync(p->s_frames[slot], samples + f0 * h, ((cnt - 1) * h + (uint64_t)n) * sizeof(float),
+                                  hipMemcpyHostToDevice, st);
+    return e == hipSuccess ? MGX_OK : hip_fail(e, "hipMemcpyAsync(samples)");
   });
 }
 
@@ -1503,23 +1582,29 @@ int mgx_pcm_decode_device(const void* pcm, uint64_t sample_frames, uint32_t form
   return e == hipSuccess ? MGX_OK : hip_fail(e, "PCM decode launch");
 }
 
-int mgx_extract_host_pcm(mgx_plan* p, const void* pcm, uint64_t pcm_bytes, uint64_t sample_frames, uint32_t format,
-                         uint32_t channels, uint32_t channel, const mgx_outputs* o) {
-  if (!p || !o) return fail(MGX_E_INVALID_ARGUMENT, "NULL plan or outputs");
+}  // extern "C"
+
+namespace {
+
+// mgx_extract_host_pcm (hop = N: floor(sample_frames / N) disjoint buffers) and mgx_extract_signal_host_pcm
+int extract_host_pcm_impl(mgx_plan* p, const void* pcm, uint64_t pcm_bytes, uint64_t sample_frames, uint32_t format,
+                          uint32_t channels, uint32_t channel, uint64_t hop, const mgx_outputs* o) {
   const uint32_t bps = sample_bytes(format);
   if (!bps) return fail(MGX_E_INVALID_ARGUMENT, "unknown PCM format %u", format);
   if (channels == 0 || channel >= channels) return fail(MGX_E_INVALID_ARGUMENT, "channel %u of %u", channel, channels);
   if ((o->complex_real == nullptr) != (o->complex_imag == nullptr))
     return fail(MGX_E_INVALID_ARGUMENT, "complex_real and complex_imag must be given together");
   const int n = p->n;
-  const uint64_t nframes = sample_frames / (uint64_t)n;
+  const uint64_t nframes = sample_frames < (uint64_t)n ? 0 : (sample_frames - (uint64_t)n) / hop + 1;
   if (nframes == 0) return MGX_OK;
   if (!pcm) return fail(MGX_E_INVALID_ARGUMENT, "pcm is NULL");
   const uint64_t align = (uint64_t)bps * channels;
   if (sample_frames > pcm_bytes / align)
     return fail(MGX_E_INVALID_ARGUMENT, "%llu sample frames of %llu bytes exceed the %llu-byte PCM buffer",
                 (unsigned long long)sample_frames, (unsigned long long)align, (unsigned long long)pcm_bytes);
-  const uint64_t chunk_bytes = std::min<uint64_t>(nframes, kHostChunk) * n * align;
+  // (a chunk's span of samples, every channel: what one slot holds of the raw PCM)
+  const uint64_t chunk_max = signal_chunk_frames(p, hop);
+  const uint64_t chunk_bytes = ((std::min<uint64_t>(nframes, chunk_max) - 1) * hop + (uint64_t)n) * align;
   if (p->s_pcm_bytes < chunk_bytes) {
     if (p->s_copy) (void)hipStreamSynchronize(p->s_copy);
     for (int i = 0; i < 2; ++i) {
@@ -1533,13 +1618,30 @@ int mgx_extract_host_pcm(mgx_plan* p, const void* pcm, uint64_t pcm_bytes, uint6
     p->s_pcm_bytes = chunk_bytes;
   }
   const unsigned char* src = static_cast<const unsigned char*>(pcm);
-  return extract_host_chunked(p, nframes, o, [&](uint64_t f0, uint64_t cnt, int slot, hipStream_t st) {
-    const uint64_t bytes = cnt * n * align;
-    hipError_t e = hipMemcpyAsync(p->s_pcm[slot], src + f0 * n * align, bytes, hipMemcpyHostToDevice, st);
+  return extract_host_chunked(p, nframes, hop, chunk_max, o, [&](uint64_t f0, uint64_t cnt, int slot, hipStream_t st) {
+    const uint64_t span = (cnt - 1) * hop + (uint64_t)n;  // the chunk's samples, each copied and decoded once
+    hipError_t e = hipMemcpyAsync(p->s_pcm[slot], src + f0 * hop * align, span * align, hipMemcpyHostToDevice, st);
     if (e != hipSuccess) return hip_fail(e, "hipMemcpyAsync(pcm)");
-    e = mgx::launch_pcm_decode(p->s_pcm[slot], cnt * n, format, channels, channel, p->s_frames[slot], st);
+    e = mgx::launch_pcm_decode(p->s_pcm[slot], span, format, channels, channel, p->s_frames[slot], st);
     return e == hipSuccess ? MGX_OK : hip_fail(e, "PCM decode launch");
   });
+}
+
+}  // namespace
+
+extern "C" {
+
+int mgx_extract_host_pcm(mgx_plan* p, const void* pcm, uint64_t pcm_bytes, uint64_t sample_frames, uint32_t format,
+                         uint32_t channels, uint32_t channel, const mgx_outputs* o) {
+  if (!p || !o) return fail(MGX_E_INVALID_ARGUMENT, "NULL plan or outputs");
+  return extract_host_pcm_impl(p, pcm, pcm_bytes, sample_frames, format, channels, channel, (uint64_t)p->n, o);
+}
+
+int mgx_extract_signal_host_pcm(mgx_plan* p, const void* pcm, uint64_t pcm_bytes, uint64_t sample_frames, uint32_t format,
+                                uint32_t channels, uint32_t channel, uint32_t hop, const mgx_outputs* o) {
+  if (!p || !o) return fail(MGX_E_INVALID_ARGUMENT, "NULL plan or outputs");
+  if (hop == 0) return fail(MGX_E_INVALID_ARGUMENT, "hop is 0 (a hop of at least one sample)");
+  return extract_host_pcm_impl(p, pcm, pcm_bytes, sample_frames, format, channels, channel, hop, o);
 }
 
 int mgx_synth_frames_device(float* frames, uint64_t nframes, uint32_t n, uint64_t seed, uint64_t first_frame, void* stream) {

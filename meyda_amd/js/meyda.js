@@ -11,9 +11,16 @@
 //   process(signal)                 push one buffer (what onaudioprocess does, :69-91)
 //   getBatch(features, frames)      frames: Float32Array(F * bufferSize) -> SoA typed arrays
 //   getBatchAsync(features, frames) same, off the JS thread (napi_async_work)
-//   getBatchWav(features, wavBytes[, channel]) / getBatchWavAsync(...)
+//   getBatchWav(features, wavBytes[, channel[, hopSize]]) / getBatchWavAsync(...)
 //                                   every full buffer of a .wav file (RIFF walk in C, raw PCM
-//                                   decoded on the device: decodeAudioData's scaling)
+//                                   decoded on the device: decodeAudioData's scaling); with hopSize,
+//                                   the buffers that start every hopSize samples
+//   getBatchSignal(features, samples, hopSize) / getBatchSignalAsync(...)
+//                                   samples: one contiguous Float32Array; the overlapping buffers
+//                                   that start every hopSize samples (later Meyda's hopSize), read
+//                                   in place on the device, a trailing partial buffer dropped
+//   Meyda.signalFrames(numSamples, bufferSize, hopSize)
+//                                   how many buffers that is: (numSamples - bufferSize) / hopSize + 1
 //   Meyda.readWav(wavBytes)         the header: {pcmFormat, channels, sampleRate, sampleFrames, ...}
 //   flush()                         deliver buffered callbacks now (options.batchFrames > 1)
 //   options.devices = [0, 1, ...]   shard batches over several GPUs; the feature records are
@@ -350,14 +357,54 @@ class Meyda {
     return this._runAsync((plan) => addon.extractAsync(plan, x, names));
   }
 
-  // Every full buffer of a .wav file (Buffer / Uint8Array / ArrayBuffer), channel `channel`.
-  getBatchWav(features, wavBytes, channel) {
-    return addon.extractWav(this._plan(), wavBytes, checkBatchNames(features), channel | 0);
+  // Every full buffer of a .wav file (Buffer / Uint8Array / ArrayBuffer), channel `channel`; with
+  // hopSize, the buffers that start every hopSize samples of that channel.
+  getBatchWav(features, wavBytes, channel, hopSize) {
+    const names = checkBatchNames(features);
+    if (hopSize === undefined) return addon.extractWav(this._plan(), wavBytes, names, channel | 0);
+    const hop = this._checkHop(hopSize);
+    return addon.extractWav(this._plan(), wavBytes, names, channel | 0, hop);
   }
 
-  getBatchWavAsync(features, wavBytes, channel) {
+  getBatchWavAsync(features, wavBytes, channel, hopSize) {
     const names = checkBatchNames(features);
-    return this._runAsync((plan) => addon.extractWavAsync(plan, wavBytes, names, channel | 0));
+    if (hopSize === undefined) return this._runAsync((plan) => addon.extractWavAsync(plan, wavBytes, names, channel | 0));
+    const hop = this._checkHop(hopSize);
+    return this._runAsync((plan) => addon.extractWavAsync(plan, wavBytes, names, channel | 0, hop));
+  }
+
+  // Overlapping buffers of one contiguous signal: buffer f is samples [f hopSize, f hopSize + bufferSize),
+  // Meyda.signalFrames(samples.length, bufferSize, hopSize) of them; results as getBatch's.
+  getBatchSignal(features, samples, hopSize) {
+    const names = checkBatchNames(features);
+    const hop = this._checkHop(hopSize);
+    return addon.extractSignal(this._plan(), toF32(samples), hop, names);
+  }
+
+  getBatchSignalAsync(features, samples, hopSize) {
+    const names = checkBatchNames(features);
+    const hop = this._checkHop(hopSize);
+    const x = toF32(samples);
+    return this._runAsync((plan) => addon.extractSignalAsync(plan, x, hop, names));
+  }
+
+  // hopSize: a positive integer (that fits the C ABI's uint32), checked before the addon is called; the
+  // device groups of options.devices take dense buffers only (include/meyda_gpu.h).
+  _checkHop(hopSize) {
+    if (typeof hopSize !== 'number' || !Number.isInteger(hopSize) || hopSize < 1 || hopSize > 4294967295) {
+      throw new RangeError('hopSize must be a positive integer, got ' + String(hopSize));
+    }
+    if (Array.isArray(this.options.devices)) {
+      throw new Error('hopSize is not supported with options.devices: device groups take dense buffers only');
+    }
+    return hopSize;
+  }
+
+  static signalFrames(numSamples, bufferSize, hopSize) {
+    if (typeof hopSize !== 'number' || !Number.isInteger(hopSize) || hopSize < 1 || hopSize > 4294967295) {
+      throw new RangeError('hopSize must be a positive integer, got ' + String(hopSize));
+    }
+    return addon.signalFrames(numSamples, bufferSize, hopSize);
   }
 
   static readWav(wavBytes) {

@@ -90,8 +90,9 @@ def main():
     base = np.median(res[vs[0][0]])
     for name, _, _ in vs:
         m = np.median(res[name])
-        print("%-14s median %.4f ms  min %.4f ms  (%+.1f %% vs %s)  %.1f M frames/s" %
-              (name, m, np.min(res[name]), (m / base - 1) * 100, vs[0][0], F / m / 1e3))
+        # (spread: max - min of the variant's own per-round means, the noise an A/B difference is read against)
+        print("%-14s median %.4f ms  min %.4f ms  spread %.4f ms  (%+.1f %% vs %s)  %.1f M frames/s" %
+              (name, m, np.min(res[name]), np.max(res[name]) - np.min(res[name]), (m / base - 1) * 100, vs[0][0], F / m / 1e3))
 
 
 if __name__ == "__main__":
