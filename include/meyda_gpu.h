@@ -23,6 +23,9 @@
  *   mgx_extract_host_pcm
  *   mgx_extract_signal_* the same over one contiguous signal whose   src/meyda.js:69-91 (disjoint
  *                        buffers start every `hop` samples           buffers only: hop = N)
+ *   mgx_extract_*_ex     the signal calls with the outputs added     src/extractors/mfcc.js:53-65
+ *                        after mgx_outputs (mgx_aux_outputs):       (loggedMelBands, the Float32Array
+ *                        melBands, the log mel band energies        the DCT of :67-93 reads)
  *   mgx_group_*          several devices, RCCL gather of the        src/meyda.js:17-97 (one plan
  *                        per-frame records to the root device       per device), :69-91 (buffers
  *                                                                   are independent: shardable)
@@ -82,7 +85,10 @@ typedef enum mgx_feature {
   MGX_POWER_SPECTRUM = 16,      /* powerSpectrum.js */
   MGX_COMPLEX_SPECTRUM = 17,    /* complexSpectrum.js: {real, imag} */
   MGX_BUFFER = 18,              /* buffer (declared in feature-info.js:3-5): the frame itself */
-  MGX_NUM_FEATURES = 19
+  MGX_MEL_BANDS = 19,           /* mfcc.js:53-65 loggedMelBands: Float32Array(num_mel_bands), the log mel band
+                                   energies the MFCC is the DCT of (melBands in later Meyda releases); a
+                                   field of mgx_aux_outputs, not of mgx_outputs */
+  MGX_NUM_FEATURES = 20
 } mgx_feature;
 
 typedef enum mgx_window { MGX_WINDOW_HANNING = 0, MGX_WINDOW_HAMMING = 1 } mgx_window;
@@ -157,6 +163,17 @@ typedef struct mgx_outputs {
   float* complex_real;        /* num_frames x N */
   float* complex_imag;        /* num_frames x N */
 } mgx_outputs;
+
+/* Outputs added after mgx_outputs, whose layout is fixed (it carries no size): the mgx_extract_*_ex calls
+ * take this struct beside it. It is size-checked, so it can grow: a later field is appended, and a caller
+ * built against an older header keeps passing the size it knows. Pointers follow the rules of mgx_outputs
+ * (device pointers for the device call, host pointers for the host calls; NULL: not written). */
+typedef struct mgx_aux_outputs {
+  uint32_t struct_size;   /* = sizeof(mgx_aux_outputs); anything else: MGX_E_INVALID_ARGUMENT */
+  uint32_t reserved;      /* 0 */
+  float* mel_bands;       /* num_frames x num_mel_bands: loggedMelBands of mfcc.js:53-65, i.e. the
+                             Float32Array the reference's DCT reads; row f at mel_bands + f * num_mel_bands */
+} mgx_aux_outputs;
 
 /* Host-side tables of a plan (no device needed): used by tests and by bindings
  * that want to show the same tables Meyda exposes (hanning, hamming, barkScale). */
@@ -268,7 +285,7 @@ int mgx_extract_host_pcm(mgx_plan* plan, const void* pcm, uint64_t pcm_bytes, ui
  * kernel's loads past the last buffer are clamped to buffer F - 1 (its samples
  * [(F - 1) * hop, (F - 1) * hop + N)): nothing beyond that buffer is read, so none of the
  * up to hop - 1 samples of the dropped tail are. Multi-device groups (mgx_group_*) take
- * dense buffers only. */
+ * dense buffers only, and no auxiliary outputs (mgx_aux_outputs, below). */
 
 /* F of the formula above. Host only (no device). */
 int mgx_signal_frames(uint64_t num_samples, uint32_t buffer_size, uint32_t hop, uint64_t* num_frames);
@@ -296,6 +313,33 @@ int mgx_extract_signal_host(mgx_plan* plan, const float* samples, uint64_t num_s
 int mgx_extract_signal_host_pcm(mgx_plan* plan, const void* pcm, uint64_t pcm_bytes, uint64_t sample_frames,
                                 uint32_t format, uint32_t channels, uint32_t channel, uint32_t hop,
                                 const mgx_outputs* outputs);
+
+/* ---- The signal calls with auxiliary outputs -------------------------------------------
+ * mgx_extract_signal_device / _host / _host_pcm with a mgx_aux_outputs beside the mgx_outputs. aux = NULL
+ * is exactly the corresponding mgx_extract_signal_* call (the six calls above are these with aux = NULL:
+ * a dense batch of F buffers is num_samples = F * N, hop = N); with aux, every field of `outputs` may be
+ * NULL. The same per-stream scratch, first-call rule, graph-capture property, clamped last loads and
+ * pcm_bytes rule hold.
+ *
+ * aux->mel_bands (feature MGX_MEL_BANDS, "melBands"): for every plan that can compute mfcc -- either
+ * precision, literal mode, both windows, 1..64 bands, every flag -- the values the plan's MFCC is the DCT
+ * of: with MGX_FLAG_MFCC_REFERENCE the reference-order sums and the double Math.log (the reference's bits
+ * wherever the power spectrum is), otherwise the segmented-scan sums and the float32 log (within 1e-5).
+ * Asking for it without mfcc runs the mel sums and the log and skips the DCT; asking for it changes no
+ * other output in any bit. Rows are num_mel_bands floats apart (4-byte aligned only when that is odd).
+ * A silent buffer gives -Infinity in every band, as Math.log(0) does.
+ * MGX_FLAG_RESIDENT plans: a one-buffer host call that asks for mel_bands is served by a one-frame launch
+ * (the path of a plan without the flag), which first ends the resident workgroup as any other launch
+ * does; calls without it go back to the resident workgroup.
+ * Multi-device groups (mgx_group_*) take no auxiliary outputs: mgx_packed_layout and MGX_OUT_* are as
+ * they were. */
+int mgx_extract_device_ex(mgx_plan* plan, const float* samples, uint64_t num_samples, uint32_t hop,
+                          const mgx_outputs* outputs, const mgx_aux_outputs* aux, void* stream);
+int mgx_extract_host_ex(mgx_plan* plan, const float* samples, uint64_t num_samples, uint32_t hop,
+                        const mgx_outputs* outputs, const mgx_aux_outputs* aux);
+int mgx_extract_host_pcm_ex(mgx_plan* plan, const void* pcm, uint64_t pcm_bytes, uint64_t sample_frames,
+                            uint32_t format, uint32_t channels, uint32_t channel, uint32_t hop,
+                            const mgx_outputs* outputs, const mgx_aux_outputs* aux);
 
 /* ---- Multi-device groups -------------------------------
  * Replaces nothing in the reference (single-threaded browser code); it exists because

@@ -232,7 +232,7 @@ static napi_value destroy_plan(napi_env env, napi_callback_info info) {
 }
 
 /* ------------------------------------------------------------ extraction job */
-enum { SLOT_SCALAR0 = 0, SLOT_LOUD = MGX_NUM_SCALARS, SLOT_MFCC, SLOT_AMP, SLOT_POW, SLOT_CRE, SLOT_CIM, NSLOTS };
+enum { SLOT_SCALAR0 = 0, SLOT_LOUD = MGX_NUM_SCALARS, SLOT_MFCC, SLOT_AMP, SLOT_POW, SLOT_CRE, SLOT_CIM, SLOT_MEL, NSLOTS };
 
 typedef struct {
   plan_box* box;
@@ -248,6 +248,7 @@ typedef struct {
   uint32_t hop;
   uint64_t nsamples;
   mgx_outputs out;
+  mgx_aux_outputs aux;  /* melBands (SLOT_MEL): the job then makes the mgx_extract_*_ex call */
   /* The outputs are written straight into JS ArrayBuffers (napi_create_arraybuffer), held by
    * references until the result object takes them. (External ArrayBuffers over malloc'd memory
    * with a free finalizer made Node 12 abort at exit: v8impl ArrayBufferReference::Finalize's
@@ -304,6 +305,13 @@ static int parse_features(napi_env env, napi_value feats, job* j) {
     else if (f == MGX_AMPLITUDE_SPECTRUM) j->want[SLOT_AMP] = 1;
     else if (f == MGX_POWER_SPECTRUM) j->want[SLOT_POW] = 1;
     else if (f == MGX_COMPLEX_SPECTRUM) { j->want[SLOT_CRE] = 1; j->want[SLOT_CIM] = 1; }
+    else if (f == MGX_MEL_BANDS) {
+      if (j->box->group) {
+        napi_throw_error(env, NULL, "melBands is not supported on a plan created with `devices`: device groups take no auxiliary outputs");
+        return 0;
+      }
+      j->want[SLOT_MEL] = 1;
+    }
     /* MGX_BUFFER is the input itself: handled by the JS facade */
   }
   return 1;
@@ -393,6 +401,7 @@ static int job_alloc(napi_env env, job* j, napi_value feats) {
     if (i < MGX_NUM_SCALARS) b = F * ss;
     else if (i == SLOT_LOUD) b = F * 24 * 4;
     else if (i == SLOT_MFCC) b = F * j->box->desc.num_mfcc_coeffs * 4;
+    else if (i == SLOT_MEL) b = F * j->box->desc.num_mel_bands * 4;
     else if (i == SLOT_AMP || i == SLOT_POW) b = F * L * 4;
     else b = F * n * 4;
     j->bytes[i] = b;
@@ -411,6 +420,8 @@ static int job_alloc(napi_env env, job* j, napi_value feats) {
   j->out.power_spectrum = (float*)j->bufs[SLOT_POW];
   j->out.complex_real = (float*)j->bufs[SLOT_CRE];
   j->out.complex_imag = (float*)j->bufs[SLOT_CIM];
+  j->aux.struct_size = sizeof j->aux;
+  j->aux.mel_bands = (float*)j->bufs[SLOT_MEL];
   return 1;
 }
 
@@ -494,8 +505,15 @@ static void job_run(job* j) {
     snprintf(j->err, sizeof j->err, "extractWav on a multi-device plan: use a single-device plan");
     return;
   }
+  const uint32_t n = j->box->desc.buffer_size;
   if (j->box->group)
     j->rc = mgx_group_extract_host(j->box->group, j->frames, j->nframes, &j->out);
+  else if (j->want[SLOT_MEL] && j->pcm)  /* (a dense batch is the signal form at hop N) */
+    j->rc = mgx_extract_host_pcm_ex(j->box->plan, j->pcm, j->pcm_bytes, j->pcm_frames, j->pcm_format, j->pcm_channels,
+                                    j->pcm_channel, j->hop ? j->hop : n, &j->out, &j->aux);
+  else if (j->want[SLOT_MEL])
+    j->rc = mgx_extract_host_ex(j->box->plan, j->frames, j->hop ? j->nsamples : j->nframes * n, j->hop ? j->hop : n, &j->out,
+                                &j->aux);
   else if (j->hop && j->pcm)
     j->rc = mgx_extract_signal_host_pcm(j->box->plan, j->pcm, j->pcm_bytes, j->pcm_frames, j->pcm_format, j->pcm_channels,
                                         j->pcm_channel, j->hop, &j->out);
@@ -528,6 +546,7 @@ static napi_value job_result(napi_env env, job* j) {
     if (j->want[i]) napi_set_named_property(env, obj, names[i], typed(env, j, i, f64 ? napi_float64_array : napi_float32_array, f64 ? 8 : 4));
   if (j->want[SLOT_LOUD]) napi_set_named_property(env, obj, "loudness.specific", typed(env, j, SLOT_LOUD, napi_float32_array, 4));
   if (j->want[SLOT_MFCC]) napi_set_named_property(env, obj, "mfcc", typed(env, j, SLOT_MFCC, napi_float32_array, 4));
+  if (j->want[SLOT_MEL]) napi_set_named_property(env, obj, "melBands", typed(env, j, SLOT_MEL, napi_float32_array, 4));
   if (j->want[SLOT_AMP]) napi_set_named_property(env, obj, "amplitudeSpectrum", typed(env, j, SLOT_AMP, napi_float32_array, 4));
   if (j->want[SLOT_POW]) napi_set_named_property(env, obj, "powerSpectrum", typed(env, j, SLOT_POW, napi_float32_array, 4));
   if (j->want[SLOT_CRE]) napi_set_named_property(env, obj, "complexSpectrum.real", typed(env, j, SLOT_CRE, napi_float32_array, 4));
@@ -582,7 +601,7 @@ static napi_value extract_common(napi_env env, napi_callback_info info, int kind
 /* extractInto(plan, frames, offsets, out): the same synchronous extraction into ONE caller-provided
  * ArrayBuffer. offsets: a Float64Array of the 19 output fields' byte offsets in `out` (mgx_outputs
  * order: the 13 scalars, loudness_specific, mfcc, amplitude, power, complex real, complex imag; a
- * negative entry = not requested). The facade's real-time paths (get(), batched streaming) lay the
+ * negative entry = not requested), or of 20: those, then melBands (mgx_aux_outputs.mel_bands). The facade's real-time paths (get(), batched streaming) lay the
  * outputs of a feature list out once and call this per buffer or batch: one allocation and a handful of
  * N-API calls instead of an ArrayBuffer, a reference and a typed array per output. */
 static napi_value extract_into(napi_env env, napi_callback_info info) {
@@ -613,8 +632,8 @@ static napi_value extract_into(napi_env env, napi_callback_info info) {
   }
   napi_is_typedarray(env, argv[2], &is);
   if (is) napi_get_typedarray_info(env, argv[2], &tt, &olen, &offs, &ab, &off);
-  if (!is || tt != napi_float64_array || olen != 19) {
-    napi_throw_type_error(env, NULL, "offsets must be a Float64Array of 19 byte offsets");
+  if (!is || tt != napi_float64_array || (olen != 19 && olen != 20)) {
+    napi_throw_type_error(env, NULL, "offsets must be a Float64Array of 19 byte offsets (20 with melBands)");
     return NULL;
   }
   void* out = NULL;
@@ -632,15 +651,15 @@ static napi_value extract_into(napi_env env, napi_callback_info info) {
   }
   const uint64_t F = len / n;
   const size_t ss = box->desc.scalar_f64 ? 8 : 4;
-  size_t per[19];
-  for (int i = 0; i < 19; ++i)
+  size_t per[20];
+  for (int i = 0; i < 20; ++i)
     per[i] = i < MGX_NUM_SCALARS ? ss : i == 13 ? 24 * 4 : i == 14 ? (size_t)box->desc.num_mfcc_coeffs * 4
-           : i < 17 ? (size_t)(n / 2) * 4 : (size_t)n * 4;
-  void* ptr[19];
+           : i == 19 ? (size_t)box->desc.num_mel_bands * 4 : i < 17 ? (size_t)(n / 2) * 4 : (size_t)n * 4;
+  void* ptr[20];
   const double* o = (const double*)offs;
-  for (int i = 0; i < 19; ++i) {
+  for (int i = 0; i < 20; ++i) {
     ptr[i] = NULL;
-    if (!(o[i] >= 0)) continue;
+    if (i >= (int)olen || !(o[i] >= 0)) continue;
     const double end = o[i] + (double)(per[i] * F);
     if (o[i] != (double)(uint64_t)o[i] || end > (double)out_bytes || ((uint64_t)o[i] % (i < MGX_NUM_SCALARS ? ss : 4))) {
       napi_throw_range_error(env, NULL, "an output's offset is misaligned or runs past the end of out");
@@ -661,7 +680,16 @@ static napi_value extract_into(napi_env env, napi_callback_info info) {
   mo.power_spectrum = (float*)ptr[16];
   mo.complex_real = (float*)ptr[17];
   mo.complex_imag = (float*)ptr[18];
+  if (ptr[19] && box->group) {
+    napi_throw_error(env, NULL, "melBands is not supported on a plan created with `devices`: device groups take no auxiliary outputs");
+    return NULL;
+  }
+  mgx_aux_outputs ma;
+  memset(&ma, 0, sizeof ma);
+  ma.struct_size = sizeof ma;
+  ma.mel_bands = (float*)ptr[19];
   const int rc = box->group ? mgx_group_extract_host(box->group, (const float*)data, F, &mo)
+                 : ptr[19]  ? mgx_extract_host_ex(box->plan, (const float*)data, F * n, n, &mo, &ma)
                             : mgx_extract_host(box->plan, (const float*)data, F, &mo);
   if (rc) return throw_mgx(env, rc);
   return argv[3];

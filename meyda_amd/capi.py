@@ -19,7 +19,7 @@ SCALAR_NAMES = ["rms", "energy", "zcr", "spectralCentroid", "spectralFlatness", 
                 "spectralRolloff", "spectralSpread", "spectralSkewness", "spectralKurtosis",
                 "loudness.total", "perceptualSpread", "perceptualSharpness"]
 FEATURE_NAMES = SCALAR_NAMES + ["loudness", "mfcc", "amplitudeSpectrum", "powerSpectrum",
-                                "complexSpectrum", "buffer"]
+                                "complexSpectrum", "buffer", "melBands"]
 WINDOWS = {"hanning": 0, "hamming": 1}
 PRECISIONS = {"faithful": 0, "fast": 1}
 MODES = {"per_buffer_fft": 0, "literal": 1}
@@ -36,6 +36,7 @@ EXPORTS = ["mgx_plan_desc_init", "mgx_plan_create", "mgx_plan_destroy", "mgx_pla
            "mgx_wav_parse", "mgx_pcm_decode_device", "mgx_extract_host_pcm",
            "mgx_signal_frames", "mgx_extract_signal_device", "mgx_extract_signal_host",
            "mgx_extract_signal_host_pcm",
+           "mgx_extract_device_ex", "mgx_extract_host_ex", "mgx_extract_host_pcm_ex",
            "mgx_shard_range", "mgx_packed_layout", "mgx_comm_unique_id", "mgx_group_create",
            "mgx_group_create_rank", "mgx_group_create_loopback", "mgx_group_create_loopback_rccl", "mgx_group_destroy",
            "mgx_group_info", "mgx_group_comm_info", "mgx_group_extract_device", "mgx_group_extract_host"]
@@ -72,6 +73,28 @@ class Outputs(ctypes.Structure):
                 ("loudness_specific", ctypes.c_void_p), ("mfcc", ctypes.c_void_p),
                 ("amplitude_spectrum", ctypes.c_void_p), ("power_spectrum", ctypes.c_void_p),
                 ("complex_real", ctypes.c_void_p), ("complex_imag", ctypes.c_void_p)]
+
+
+class AuxOutputs(ctypes.Structure):
+    """mgx_aux_outputs: the outputs added after mgx_outputs (the mgx_extract_*_ex calls)."""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("reserved", ctypes.c_uint32), ("mel_bands", ctypes.c_void_p)]
+
+
+def _aux(outputs):
+    """The AuxOutputs that alloc_outputs / _host_outputs hung on `outputs` ("melBands" requested), or None."""
+    return getattr(outputs, "aux", None)
+
+
+def _aux_ref(outputs):
+    a = _aux(outputs)
+    return None if a is None else ctypes.byref(a)
+
+
+def _set_mel_bands(outputs, ptr):
+    a = AuxOutputs()
+    a.struct_size = ctypes.sizeof(AuxOutputs)
+    a.mel_bands = ptr
+    outputs.aux = a  # (a Python attribute of the Outputs instance: the C struct is unchanged)
 
 
 class HostTables(ctypes.Structure):
@@ -144,6 +167,14 @@ def lib():
         L.mgx_extract_signal_host_pcm.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64,
                                                   ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
                                                   ctypes.POINTER(Outputs)]
+        aux = ctypes.POINTER(AuxOutputs)
+        L.mgx_extract_device_ex.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32,
+                                            ctypes.POINTER(Outputs), aux, ctypes.c_void_p]
+        L.mgx_extract_host_ex.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32,
+                                          ctypes.POINTER(Outputs), aux]
+        L.mgx_extract_host_pcm_ex.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64,
+                                              ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
+                                              ctypes.POINTER(Outputs), aux]
         L.mgx_shard_range.argtypes = [ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, u64p, u64p]
         L.mgx_packed_layout.argtypes = [ctypes.POINTER(PlanDesc), ctypes.c_uint32, ctypes.c_uint64, u64p]
         L.mgx_packed_layout.restype = ctypes.c_uint64
@@ -246,7 +277,9 @@ class Plan:
 
     # ---------------------------------------------------------- device (torch)
     def alloc_outputs(self, num_frames, features, device="cuda"):
-        """Allocate torch device tensors for the requested features; returns (dict, Outputs)."""
+        """Allocate torch device tensors for the requested features; returns (dict, Outputs). "melBands" (an
+        output beyond mgx_outputs) rides on the Outputs as its `aux` attribute, an AuxOutputs: the extract
+        methods below then make the mgx_extract_*_ex call."""
         import torch
         st = torch.float64 if self.scalar_dtype == np.float64 else torch.float32
         L = self.n // 2
@@ -263,6 +296,9 @@ class Plan:
             elif f == "mfcc":
                 out[f] = torch.empty(num_frames, self.desc.num_mfcc_coeffs, dtype=torch.float32, device=device)
                 o.mfcc = out[f].data_ptr()
+            elif f == "melBands":
+                out[f] = torch.empty(num_frames, self.desc.num_mel_bands, dtype=torch.float32, device=device)
+                _set_mel_bands(o, out[f].data_ptr())
             elif f == "amplitudeSpectrum":
                 out[f] = torch.empty(num_frames, L, dtype=torch.float32, device=device)
                 o.amplitude_spectrum = out[f].data_ptr()
@@ -280,6 +316,8 @@ class Plan:
 
     def extract_device(self, frames_ptr, num_frames, outputs, stream=None):
         """Launch on device pointers (async on `stream`, an int hipStream_t handle or None)."""
+        if _aux(outputs) is not None:  # the dense batch as a signal at hop N (the same launch, bit for bit)
+            return self.extract_signal_device(frames_ptr, num_frames * self.n, self.n, outputs, stream)
         check(lib().mgx_extract_device(self._h, ctypes.c_void_p(frames_ptr), num_frames,
                                        ctypes.byref(outputs), ctypes.c_void_p(stream or 0)))
 
@@ -296,6 +334,10 @@ class Plan:
 
     def extract_signal_device(self, samples_ptr, num_samples, hop, outputs, stream=None):
         """Launch on a device signal cut every `hop` samples (async; outputs sized for signal_frames())."""
+        if _aux(outputs) is not None:
+            check(lib().mgx_extract_device_ex(self._h, ctypes.c_void_p(samples_ptr), num_samples, hop,
+                                              ctypes.byref(outputs), _aux_ref(outputs), ctypes.c_void_p(stream or 0)))
+            return
         check(lib().mgx_extract_signal_device(self._h, ctypes.c_void_p(samples_ptr), num_samples, hop,
                                               ctypes.byref(outputs), ctypes.c_void_p(stream or 0)))
 
@@ -317,6 +359,9 @@ class Plan:
         samples = np.ascontiguousarray(samples, dtype=np.float32)
         assert samples.ndim == 1
         out, o = self._host_outputs(signal_frames(samples.size, self.n, hop), features)
+        if _aux(o) is not None:
+            check(lib().mgx_extract_host_ex(self._h, samples.ctypes.data, samples.size, hop, ctypes.byref(o), _aux_ref(o)))
+            return out
         check(lib().mgx_extract_signal_host(self._h, samples.ctypes.data, samples.size, hop, ctypes.byref(o)))
         return out
 
@@ -326,6 +371,9 @@ class Plan:
         F, n = frames.shape
         assert n == self.n
         out, o = self._host_outputs(F, features)
+        if _aux(o) is not None:
+            check(lib().mgx_extract_host_ex(self._h, frames.ctypes.data, F * n, n, ctypes.byref(o), _aux_ref(o)))
+            return out
         check(lib().mgx_extract_host(self._h, frames.ctypes.data, F, ctypes.byref(o)))
         return out
 
@@ -336,6 +384,12 @@ class Plan:
         buf = np.frombuffer(pcm, dtype=np.uint8) if not isinstance(pcm, np.ndarray) else pcm.view(np.uint8)
         buf = np.ascontiguousarray(buf)
         fmt = PCM_FORMATS[fmt] if isinstance(fmt, str) else fmt
+        if "melBands" in features:
+            h = self.n if hop is None else hop
+            out, o = self._host_outputs(signal_frames(sample_frames, self.n, h), features)
+            check(lib().mgx_extract_host_pcm_ex(self._h, buf.ctypes.data, buf.size, sample_frames, fmt, channels,
+                                                channel, h, ctypes.byref(o), _aux_ref(o)))
+            return out
         if hop is None:
             out, o = self._host_outputs(sample_frames // self.n, features)
             check(lib().mgx_extract_host_pcm(self._h, buf.ctypes.data, buf.size, sample_frames, fmt, channels, channel,
@@ -371,6 +425,9 @@ class Plan:
             elif f == "mfcc":
                 out[f] = np.empty((F, self.desc.num_mfcc_coeffs), np.float32)
                 o.mfcc = out[f].ctypes.data
+            elif f == "melBands":
+                out[f] = np.empty((F, self.desc.num_mel_bands), np.float32)
+                _set_mel_bands(o, out[f].ctypes.data)
             elif f == "amplitudeSpectrum":
                 out[f] = np.empty((F, L), np.float32)
                 o.amplitude_spectrum = out[f].ctypes.data
@@ -488,6 +545,8 @@ class Group:
         frames = np.ascontiguousarray(frames, dtype=np.float32)
         F, n = frames.shape
         assert n == self.n
+        if "melBands" in features:
+            raise ValueError("multi-device groups take no auxiliary outputs (melBands): include/meyda_gpu.h")
         out, o = Plan._host_outputs(self, F, features)
         check(lib().mgx_group_extract_host(self._h, frames.ctypes.data, F, ctypes.byref(o)))
         return out

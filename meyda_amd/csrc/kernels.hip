@@ -1054,7 +1054,7 @@ __device__ __forceinline__ void nonfinite_frame_sums(KArgs* ap, const float (&av
     for (int k = lim[lane]; k < lim[lane + 1]; ++k) sum += (double)amp[k];
     rec.band[lane] = sum;
   }
-  if (ap->need_mfcc) {  // mfcc.js:53-62: every bin, double weight x float power, float32 sum
+  if (ap->need_mel) {  // mfcc.js:53-62: every bin, double weight x float power, float32 sum
     const int nf = ap->nfilt;
     const auto b = gbl(ap->t.mel_bins);
     for (int j = lane; j < nf; j += 64) {
@@ -1420,7 +1420,7 @@ __device__ __forceinline__ void frame_phase1(KArgs* ap, float (&x)[Geo<N>::CH], 
     // writing bin 64 c + l: 256 contiguous bytes per store, where the lane's own bins [R l, R l + R) were
     // R 4-byte stores 4 R bytes apart; profiles/r05_chain_rows.txt).
     // A non-finite frame's slot then takes its mel sums instead (below).
-    if (ap->need_mfcc) {
+    if (ap->need_mel) {
       auto row = gbl(rows) + ((ap->chain_pair ? 4 * (it & 1) : 0) + fb) * L;
 #pragma unroll
       for (int c = 0; c < R; ++c) {
@@ -1584,7 +1584,7 @@ __device__ __forceinline__ void frame_phase1(KArgs* ap, float (&x)[Geo<N>::CH], 
   // flight. (Issued any earlier, the extra live registers spill around the moment sums,
   // and a spill reload is a vector-memory wait behind the prefetch.)
   MelTab<N> mt;
-  if (!CHAIN && ap->need_mfcc) mt.load(ap, lane);
+  if (!CHAIN && ap->need_mel) mt.load(ap, lane);
   prefetch_next();
   if (!kMomLds && need_mom) {
     const double S1 = wave_sum(P1);
@@ -1630,14 +1630,14 @@ __device__ __forceinline__ void frame_phase1(KArgs* ap, float (&x)[Geo<N>::CH], 
   if (nonfinite) {
     // (CHAIN with paired batches: the pair's first batch keeps its mel sums in the upper half of lm)
     nonfinite_frame_sums<N>(ap, av, lane, buf, rec, CHAIN && ap->chain_pair && !(it & 1) ? 32 : 0);
-  } else if (!CHAIN && ap->need_mfcc) {
+  } else if (!CHAIN && ap->need_mel) {
     mel_energies<N>(ap, av, lane, buf, rec, mt);
   }
   if constexpr (CHAIN) {
     // A non-finite frame keeps the mel sums nonfinite_frame_sums formed (its flag: lm[31] of its half, or a
     // bit of its zcr count): they go to the start of its ring slot, over its power row, and mel_chains puts
     // them back after its chains (whose stores do not look at the flag).
-    if (ap->need_mfcc) {
+    if (ap->need_mel) {
       const bool pair = ap->chain_pair;
       auto row = gbl(rows) + ((pair ? 4 * (it & 1) : 0) + fb) * L;
       if (nonfinite) {  // (over the power row stored above)
@@ -1894,6 +1894,28 @@ __device__ __forceinline__ void mfcc_dct(KArgs* q, int l2, FrameRec* recs, const
   }
 }
 
+// The batch's log mel energies (lm[lmo + band] of its FPW records after mfcc_log: the Float32Array the
+// reference's DCT reads, mfcc.js:64) to rows fbase .. fbase + FPW - 1 of KernelArgs::out.mel_bands. The rows
+// are nfilt floats apart, so the batch's are one contiguous run of FPW x nfilt floats: lane l of pass k stores
+// float 64 k + l of the run (whole 256-byte stretches per store, whatever nfilt -- a row of an odd nfilt is
+// only 4-byte aligned, so dword stores) from a wave-uniform base (scalar 64-bit arithmetic) at a lane
+// offset below 2^10 (24-bit multiplies). The run ends with the launch's last frame; the padded bands nfilt .. nfp - 1 are not part of it.
+// (the MEL instances of extract_kernel only: a launch without the output runs a kernel without this code)
+__device__ __forceinline__ void mel_store(KArgs* q, int l2, FrameRec* recs, int lmo, uint64_t fbase) {
+  constexpr unsigned FPW = 4;
+  const uint64_t nf = q->num_frames;
+  if (fbase >= nf) return;
+  const unsigned nfilt = (unsigned)q->nfilt, nfr = nf - fbase < FPW ? (unsigned)(nf - fbase) : FPW;
+  const unsigned total = __umul24(nfr, nfilt);  // <= 4 x 64
+  const auto run = uniform_ptr(gbl(q->out.mel_bands) + fbase * (uint64_t)nfilt);
+  for (unsigned i = (unsigned)l2; i < total; i += 64) {
+    // float i of the run: frame i / nfilt (< 4: three compares instead of a division), band i % nfilt
+    const unsigned fb = (i >= nfilt) + (i >= 2 * nfilt) + (i >= 3 * nfilt);
+    const unsigned band = i - __umul24(fb, nfilt);
+    run[i] = rec_at(recs, (int)fb).lm[lmo + band];
+  }
+}
+
 // Copy of the TwLds image from the plan tables, once per workgroup (before its LDS barrier).
 template <int N, int P, int I>
 __device__ __forceinline__ void stage_twiddles(double2* twl, GTw tw, GTw twm) {
@@ -2037,7 +2059,12 @@ __device__ __forceinline__ bool res_wait(const uint64_t* mail, uint32_t seq, uin
 __device__ unsigned long long g_wave_times[65536 * 4];
 #endif
 
-template <int N, bool FAITH, bool LITERAL, bool SUB, bool LIGHT, bool NOTIME, bool CHAIN, bool INL = false, bool RES = false>
+// MEL: the launch writes KernelArgs::out.mel_bands (and may skip the DCT: need_dct). An instance of its own, so
+// that the launches without it run the code they ran before the output existed: with the store behind a
+// run-time test in the one kernel, the all-feature launch at N = 1024 measured +0.6 .. +1.1 % (four more SGPR
+// spills; profiles/mel_bands.txt).
+template <int N, bool FAITH, bool LITERAL, bool SUB, bool LIGHT, bool NOTIME, bool CHAIN, bool INL = false, bool RES = false,
+          bool MEL = false>
 __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(RES ? 1 : Geo<N>::WPE))) void extract_kernel(
     std::conditional_t<INL, KernelArgsInline<N>, KernelArgs> a) {
   using G = Geo<N>;
@@ -2331,7 +2358,7 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(RES ? 
     bool mfcc_now = false;
     if constexpr (CHAIN) {
       KArgs* q = args_ptr();
-      mfcc_now = q->need_spectrum && q->need_mfcc && (!q->chain_pair || (it & 1));
+      mfcc_now = q->need_spectrum && q->need_mel && (!q->chain_pair || (it & 1));
       if (mfcc_now) {
         // the rows' stores (every lane's) complete before any lane reads them: the ring is this
         // wave's alone and the CU's L1 is coherent for its own waves (workgroup scope)
@@ -2385,7 +2412,7 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(RES ? 
         }
       }
       MGX_MARK(loud2_done);
-      if (CHAIN ? mfcc_now : (q->need_spectrum && q->need_mfcc)) {
+      if (CHAIN ? mfcc_now : (q->need_spectrum && q->need_mel)) {
         mfcc_log<CHAIN, SUB>(q, l2, recs, 0);
         if (CHAIN && q->chain_pair) mfcc_log<CHAIN, SUB>(q, l2, recs, 32);  // the pair's first batch
       }
@@ -2395,9 +2422,15 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(RES ? 
       KArgs* q = args_ptr();
       const int l2 = opaque(lane);
       MGX_MARK(ln_done);
-      if (CHAIN ? mfcc_now : (q->need_spectrum && q->need_mfcc)) {
-        mfcc_dct<CHAIN, SUB>(q, l2, recs, dct_lds, 0, f0);
-        if (CHAIN && q->chain_pair) mfcc_dct<CHAIN, SUB>(q, l2, recs, dct_lds, 32, f0 - wstride * FPW);  // the pair's first batch
+      if (CHAIN ? mfcc_now : (q->need_spectrum && q->need_mel)) {
+        if (!MEL || q->need_dct) {
+          mfcc_dct<CHAIN, SUB>(q, l2, recs, dct_lds, 0, f0);
+          if (CHAIN && q->chain_pair) mfcc_dct<CHAIN, SUB>(q, l2, recs, dct_lds, 32, f0 - wstride * FPW);  // the pair's first batch
+        }
+        if constexpr (MEL) {  // the log energies themselves (the records are read-only from the log to the batch's end)
+          mel_store(q, l2, recs, 0, f0);
+          if (CHAIN && q->chain_pair) mel_store(q, l2, recs, 32, f0 - wstride * FPW);
+        }
       }
       MGX_MARK(dct_done);
       const bool defer = kScalDefer && q->scal_defer && !stolen;
@@ -2483,7 +2516,7 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(RES ? 
   if constexpr (CHAIN) {
     // paired batches: a wave whose last batch opened a pair finishes that batch's mfcc alone
     KArgs* q = args_ptr();
-    if (q->need_spectrum && q->need_mfcc && q->chain_pair && (it & 1)) {
+    if (q->need_spectrum && q->need_mel && q->chain_pair && (it & 1)) {
       prio_hi<4>();
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
       __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
@@ -2492,7 +2525,9 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(RES ? 
       wave_sync();
       mfcc_log<CHAIN, SUB>(q, l2, recs, 32);
       wave_sync();
-      mfcc_dct<CHAIN, SUB>(q, l2, recs, dct_lds, 32, (b0 + (uint64_t)(it - 1) * wstride) * FPW);
+      const uint64_t fl = (b0 + (uint64_t)(it - 1) * wstride) * FPW;
+      if (!MEL || q->need_dct) mfcc_dct<CHAIN, SUB>(q, l2, recs, dct_lds, 32, fl);
+      if constexpr (MEL) mel_store(q, l2, recs, 32, fl);
       prio_lo<4>();
     }
   }
@@ -2579,6 +2614,14 @@ __global__ void unpack_kernel(UnpackArgs a) {
 template <int N, bool FAITH, bool LITERAL, bool SUB = false, bool LIGHT = false, bool NOTIME = false, bool CHAIN = false>
 hipError_t launch_n(const KernelArgs& a, int grid, hipStream_t stream, const float* inl = nullptr, bool res = false) {
   const size_t lds = Lds<N>::bytes(a.ncoef, a.nfilt);
+  if (a.out.mel_bands) {
+    // the MEL instance (a one-frame launch's frame then comes from memory, not from the kernel arguments;
+    // the resident launch never writes mel_bands: plan.cpp extract_host_small)
+    if (res) return hipErrorInvalidValue;
+    hipLaunchKernelGGL((extract_kernel<N, FAITH, LITERAL, SUB, LIGHT, NOTIME, CHAIN, false, false, true>), dim3(grid), dim3(kThreads),
+                       lds, stream, a);
+    return hipGetLastError();
+  }
   if constexpr (FAITH && !LITERAL && !CHAIN) {
     if (res) {  // MGX_FLAG_RESIDENT: the one-workgroup server of one-frame requests
       hipLaunchKernelGGL((extract_kernel<N, FAITH, LITERAL, SUB, LIGHT, NOTIME, CHAIN, false, true>), dim3(1), dim3(kThreads), lds,
@@ -2641,7 +2684,7 @@ hipError_t launch_prec(int precision, int mode, const KernelArgs& a, int grid, h
   const bool every = a.need_mom == 2 && a.need_prefix && a.need_energy && a.need_zcr;
   if constexpr (kChainN<N>) {
     // MGX_FLAG_MFCC_REFERENCE: the mel sums as chains in the reference's order (mel_chains)
-    if (a.chain_groups > 0 && a.need_spectrum && a.need_mfcc) {
+    if (a.chain_groups > 0 && a.need_spectrum && a.need_mel) {
       if (every) return launch_n<N, true, false, false, false, false, true>(a, grid, stream);
       return launch_n<N, true, false, true, false, false, true>(a, grid, stream);
     }

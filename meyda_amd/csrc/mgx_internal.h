@@ -57,6 +57,23 @@ struct DevTables {
   uint32_t lds_image_chunks; // 16-byte chunks of the image
 };
 
+// The output arrays a launch writes: the fields of mgx_outputs, then the ones that came after its layout was
+// fixed (mgx_aux_outputs of the mgx_extract_*_ex calls). The plan code and the kernels pass this around;
+// the public entry points build it from the caller's two structs (plan.cpp make_outputs).
+struct Outputs {
+  void* scalars[MGX_NUM_SCALARS];
+  float* loudness_specific;
+  float* mfcc;
+  float* amplitude_spectrum;
+  float* power_spectrum;
+  float* complex_real;
+  float* complex_imag;
+  float* mel_bands;  // num_frames x nfilt: the log mel energies the DCT reads (mfcc.js:53-65)
+};
+static_assert(offsetof(Outputs, mel_bands) == sizeof(mgx_outputs) && offsetof(Outputs, mfcc) == offsetof(mgx_outputs, mfcc) &&
+                  offsetof(Outputs, complex_imag) == offsetof(mgx_outputs, complex_imag),
+              "Outputs begins with mgx_outputs");
+
 struct KernelArgs {
   const float* frames;
   uint64_t num_frames;
@@ -66,7 +83,7 @@ struct KernelArgs {
   // frame pointer it multiplies into (kernels.hip frame_ptr).
   uint64_t frame_stride;
   DevTables t;
-  mgx_outputs out;
+  Outputs out;
   double sample_rate;
   double freq_sum;       // spectralSlope.js: sum of i*sr/N, i < N/2 (input independent)
   double pow_freq_sum;   // spectralSlope.js: sum of (i*sr/N)^2
@@ -78,7 +95,8 @@ struct KernelArgs {
   int scalar_f64;
   int need_spectrum;     // any spectral output requested
   int need_loudness;     // loudness / perceptual outputs requested
-  int need_mfcc;
+  int need_mel;          // mfcc or mel_bands: the mel band sums and their log (mfcc.js:53-65)
+  int need_dct;          // mfcc: the DCT of the log energies (mfcc.js:67-93)
   int need_mom;          // 2: flatness / spread / skewness / kurtosis (S1..S4, sum log2 a); 1: centroid / slope (S1); 0
   int need_prefix;       // rolloff or loudness: the prefix row (rolloff count, bark band sums)
   int need_energy;       // rms or energy: the wave sum of the squares (SUB kernel)
@@ -125,7 +143,7 @@ constexpr uint32_t kResStop = 0xFFFFFFFFu;  // a request number that stops the r
 // its frame in the kernel arguments, after the KernelArgs: the kernel's first loads read it from the
 // kernarg segment, whose address the wave holds from its first instruction, instead of waiting for the
 // arguments before it can issue the frame's read of pinned host memory over PCIe.
-constexpr int kInlineMaxN = 1024;  // (4,592 bytes of arguments at N = 1024: tools/ubench/kernarg_size.hip runs 4.8 KB)
+constexpr int kInlineMaxN = 1024;  // (4,608 bytes of arguments at N = 1024: tools/ubench/kernarg_size.hip runs 4.8 KB)
 template <int N>
 struct KernelArgsInline {
   KernelArgs a;

@@ -69,14 +69,14 @@ const char* const kNames[MGX_NUM_FEATURES] = {
     "rms", "energy", "zcr", "spectralCentroid", "spectralFlatness", "spectralSlope",
     "spectralRolloff", "spectralSpread", "spectralSkewness", "spectralKurtosis",
     "loudness.total", "perceptualSpread", "perceptualSharpness", "loudness", "mfcc",
-    "amplitudeSpectrum", "powerSpectrum", "complexSpectrum", "buffer"};
+    "amplitudeSpectrum", "powerSpectrum", "complexSpectrum", "buffer", "melBands"};
 
 // src/feature-info.js:1-65
 const int kInfo[MGX_NUM_FEATURES] = {
     MGX_TYPE_NUMBER, MGX_TYPE_NUMBER, MGX_TYPE_NUMBER, MGX_TYPE_NUMBER, MGX_TYPE_NUMBER,
     MGX_TYPE_NUMBER, MGX_TYPE_NUMBER, MGX_TYPE_NUMBER, MGX_TYPE_NUMBER, MGX_TYPE_NUMBER,
     MGX_TYPE_NUMBER, MGX_TYPE_NUMBER, MGX_TYPE_NUMBER, MGX_TYPE_MULTIPLE_ARRAYS, MGX_TYPE_ARRAY,
-    MGX_TYPE_ARRAY, MGX_TYPE_ARRAY, MGX_TYPE_MULTIPLE_ARRAYS, MGX_TYPE_ARRAY};
+    MGX_TYPE_ARRAY, MGX_TYPE_ARRAY, MGX_TYPE_MULTIPLE_ARRAYS, MGX_TYPE_ARRAY, MGX_TYPE_ARRAY};
 
 // --------------------------------------------------------------- host tables
 // src/meyda.js:128-138
@@ -521,9 +521,22 @@ namespace {
 struct ResidentLaunch {
   uint32_t seq;
 };
-int extract_device_impl(mgx_plan* p, const float* frames, uint64_t nframes, uint64_t stride, const mgx_outputs* o, void* stream,
+int extract_device_impl(mgx_plan* p, const float* frames, uint64_t nframes, uint64_t stride, const mgx::Outputs* o, void* stream,
                         const uint32_t* done, const float* inline_frame = nullptr, const ResidentLaunch* res = nullptr);
 void resident_stop(mgx_plan* p);
+
+// The caller's two output structs as the one the plan code passes around. aux: NULL (no output beyond
+// mgx_outputs), or a mgx_aux_outputs of exactly this build's size -- the check that lets the struct grow.
+int make_outputs(const mgx_outputs* o, const mgx_aux_outputs* aux, mgx::Outputs* out) {
+  *out = mgx::Outputs{};
+  memcpy(out, o, sizeof *o);  // (Outputs begins with mgx_outputs: mgx_internal.h)
+  if (!aux) return MGX_OK;
+  if (aux->struct_size != sizeof(mgx_aux_outputs))
+    return fail(MGX_E_INVALID_ARGUMENT, "mgx_aux_outputs.struct_size is %u, expected %zu", aux->struct_size, sizeof(mgx_aux_outputs));
+  if (aux->reserved != 0) return fail(MGX_E_INVALID_ARGUMENT, "mgx_aux_outputs.reserved is %u, expected 0", aux->reserved);
+  out->mel_bands = aux->mel_bands;
+  return MGX_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -812,7 +825,8 @@ int mgx_plan_get_desc(const mgx_plan* p, mgx_plan_desc* out) {
 }
 
 int mgx_extract_device(mgx_plan* p, const float* frames, uint64_t nframes, const mgx_outputs* o, void* stream) {
-  return extract_device_impl(p, frames, nframes, p ? (uint64_t)p->n : 0, o, stream, nullptr);
+  if (!p || !o) return fail(MGX_E_INVALID_ARGUMENT, "NULL plan or outputs");
+  return mgx_extract_device_ex(p, frames, nframes * (uint64_t)p->n, (uint32_t)p->n, o, nullptr, stream);
 }
 
 // src/meyda.js:69-91 delivers disjoint buffers; with a hop the same buffers start every `hop` samples
@@ -826,11 +840,19 @@ int mgx_signal_frames(uint64_t num_samples, uint32_t buffer_size, uint32_t hop, 
 
 int mgx_extract_signal_device(mgx_plan* p, const float* samples, uint64_t num_samples, uint32_t hop, const mgx_outputs* o,
                               void* stream) {
+  return mgx_extract_device_ex(p, samples, num_samples, hop, o, nullptr, stream);
+}
+
+int mgx_extract_device_ex(mgx_plan* p, const float* samples, uint64_t num_samples, uint32_t hop, const mgx_outputs* o,
+                          const mgx_aux_outputs* aux, void* stream) {
   if (!p || !o) return fail(MGX_E_INVALID_ARGUMENT, "NULL plan or outputs");
-  uint64_t nframes = 0;
-  const int rc = mgx_signal_frames(num_samples, (uint32_t)p->n, hop, &nframes);
+  mgx::Outputs x;
+  int rc = make_outputs(o, aux, &x);
   if (rc) return rc;
-  return extract_device_impl(p, samples, nframes, hop, o, stream, nullptr);
+  uint64_t nframes = 0;
+  rc = mgx_signal_frames(num_samples, (uint32_t)p->n, hop, &nframes);
+  if (rc) return rc;
+  return extract_device_impl(p, samples, nframes, hop, &x, stream, nullptr);
 }
 
 }  // extern "C"
@@ -874,7 +896,7 @@ int add_stream_scratch(mgx_plan* p, void* stream) {
 // (the small path's one frame in host memory) goes into the kernel arguments where the kernel takes it
 // (mgx::launch_extract); res: the plan's resident launch (resident_request). Any other launch ends the
 // plan's resident one first, so the plan's own work never waits behind it or shares the device with it.
-int extract_device_impl(mgx_plan* p, const float* frames, uint64_t nframes, uint64_t stride, const mgx_outputs* o, void* stream,
+int extract_device_impl(mgx_plan* p, const float* frames, uint64_t nframes, uint64_t stride, const mgx::Outputs* o, void* stream,
                         const uint32_t* done, const float* inline_frame, const ResidentLaunch* res) {
   if (!p || !o) return fail(MGX_E_INVALID_ARGUMENT, "NULL plan or outputs");
   if (nframes == 0) return MGX_OK;
@@ -900,12 +922,13 @@ int extract_device_impl(mgx_plan* p, const float* frames, uint64_t nframes, uint
   a.dct_sequential = (p->d.flags & MGX_FLAG_DCT_SEQUENTIAL) ? 1 : 0;
   a.chain_groups = p->chain_groups;
   a.chain_pair = p->chain_pair;
-  bool spec = o->loudness_specific || o->mfcc || o->amplitude_spectrum || o->power_spectrum || o->complex_real;
+  bool spec = o->loudness_specific || o->mfcc || o->mel_bands || o->amplitude_spectrum || o->power_spectrum || o->complex_real;
   for (int i = MGX_SPECTRAL_CENTROID; i < MGX_NUM_SCALARS; ++i) spec = spec || o->scalars[i];
   a.need_spectrum = spec;
   a.need_loudness = o->loudness_specific || o->scalars[MGX_LOUDNESS_TOTAL] || o->scalars[MGX_PERCEPTUAL_SPREAD] ||
                     o->scalars[MGX_PERCEPTUAL_SHARPNESS];
-  a.need_mfcc = o->mfcc != nullptr;
+  a.need_mel = o->mfcc != nullptr || o->mel_bands != nullptr;
+  a.need_dct = o->mfcc != nullptr;
   // moment sums: 2 = S1..S4 and sum log2 a, 1 = S1 only, 0 = none
   a.need_mom = (o->scalars[MGX_SPECTRAL_FLATNESS] || o->scalars[MGX_SPECTRAL_SPREAD] ||
                 o->scalars[MGX_SPECTRAL_SKEWNESS] || o->scalars[MGX_SPECTRAL_KURTOSIS]) ? 2
@@ -966,11 +989,11 @@ int extract_device_impl(mgx_plan* p, const float* frames, uint64_t nframes, uint
     ring = &p->chain_rings.back();
   }
   if (a.scal_defer) a.scal_rows = ring->scal;
-  if (a.chain_groups > 0 && a.need_spectrum && a.need_mfcc) a.chain_rows = ring->rows;
+  if (a.chain_groups > 0 && a.need_spectrum && a.need_mel) a.chain_rows = ring->rows;
   // The tail pool at N = 2048 (the kernels without a frame prefetch; not the reference-order ones): the
   // last pool_pct percent of the groups taken by ticket (kernels.hip; 15 %: -2.7 % per launch against the static
   // shares alone, outputs identical, profiles/r05_tail_pool.txt).
-  if (p->n == 2048 && !(a.chain_groups > 0 && a.need_spectrum && a.need_mfcc) && p->pool_pct > 0) {
+  if (p->n == 2048 && !(a.chain_groups > 0 && a.need_spectrum && a.need_mel) && p->pool_pct > 0) {
     // (nb here counts groups of 16 frames, the kernel's groups; the pool's tickets are batches of 4 frames)
     const uint64_t ng_all = nb, pg = ng_all * (uint64_t)p->pool_pct / 100;
     if (pg > 0 && pg < ng_all && ring->pool_ctr) {
@@ -1047,12 +1070,12 @@ int ensure_host_staging(mgx_plan* p, uint64_t chunk, size_t out_bytes) {
 }
 
 // Device bytes per frame of the requested outputs (host staging layouts).
-size_t out_bytes_per_frame(const mgx_plan* p, const mgx_outputs* o) {
+size_t out_bytes_per_frame(const mgx_plan* p, const mgx::Outputs* o) {
   const size_t ss = p->d.scalar_f64 ? 8 : 4;
   size_t per = 0;
   for (int i = 0; i < MGX_NUM_SCALARS; ++i) per += o->scalars[i] ? ss : 0;
   per += (o->loudness_specific ? (size_t)mgx::kBark * 4 : 0) + (o->mfcc ? (size_t)p->d.num_mfcc_coeffs * 4 : 0) +
-         (o->amplitude_spectrum ? (size_t)p->L * 4 : 0) + (o->power_spectrum ? (size_t)p->L * 4 : 0) +
+         (o->mel_bands ? (size_t)p->d.num_mel_bands * 4 : 0) + (o->amplitude_spectrum ? (size_t)p->L * 4 : 0) + (o->power_spectrum ? (size_t)p->L * 4 : 0) +
          (o->complex_real ? 2 * (size_t)p->n * 4 : 0);
   return per;
 }
@@ -1073,7 +1096,8 @@ void resident_stop(mgx_plan* p) {
 }
 
 // bit k: output k of mgx_outputs requested (the scalars, then loudness, mfcc, amplitude, power, complex)
-uint32_t output_key(const mgx_outputs* o) {
+// (mel_bands is not among them: a request for it is served by a launch, extract_host_small)
+uint32_t output_key(const mgx::Outputs* o) {
   uint32_t k = 0;
   for (int i = 0; i < MGX_NUM_SCALARS; ++i) k |= o->scalars[i] ? 1u << i : 0u;
   const void* v[] = {o->loudness_specific, o->mfcc, o->amplitude_spectrum, o->power_spectrum, o->complex_real, o->complex_imag};
@@ -1093,7 +1117,7 @@ uint32_t output_key(const mgx_outputs* o) {
 //    words themselves cannot be waited on as the one-launch path does). A launch that ends while the host
 //    waits (it read the mailbox before the frame landed, then timed out) is started again, twice at most;
 //    past 1 s the call fails with the launch ended.
-int resident_request(mgx_plan* p, const mgx_outputs* o, const mgx_outputs& d, uint32_t seq) {
+int resident_request(mgx_plan* p, const mgx::Outputs* o, const mgx::Outputs& d, uint32_t seq) {
   const int n = p->n;
   hipError_t e = hipSuccess;
   const uint32_t key = output_key(o);
@@ -1182,12 +1206,12 @@ int resident_request(mgx_plan* p, const mgx_outputs* o, const mgx_outputs& d, ui
 // stride: the samples from one frame's start to the next in what `fill` writes, (nframes - 1) stride + N
 // samples in all (N: dense frames; a signal's hop <= N: its samples as they are, each written once).
 template <typename Fill>
-int extract_host_small(mgx_plan* p, uint64_t nframes, uint64_t stride, const mgx_outputs* o, Fill fill) {
+int extract_host_small(mgx_plan* p, uint64_t nframes, uint64_t stride, const mgx::Outputs* o, Fill fill) {
   const int n = p->n, L = p->L;
   const size_t ss = p->d.scalar_f64 ? 8 : 4;
   const size_t nb = mgx::kBark, nc = p->d.num_mfcc_coeffs;
   const size_t in_bytes = ((nframes - 1) * (size_t)stride + (size_t)n) * sizeof(float);
-  const size_t out_bytes = out_bytes_per_frame(p, o) * nframes + 20 * 256;
+  const size_t out_bytes = out_bytes_per_frame(p, o) * nframes + 21 * 256;
   hipError_t e = hipSetDevice(p->d.device);
   if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
   if (!p->s_comp) {
@@ -1226,12 +1250,13 @@ int extract_host_small(mgx_plan* p, uint64_t nframes, uint64_t stride, const mgx
   if (rc) return rc;
   void* const din = p->d_in_map;
   void* const dout = p->d_out_map;
-  mgx_outputs d{};
-  const mgx_outputs h = [&] {  // the same layout, host addresses
-    mgx_outputs r{};
+  const size_t nm = p->d.num_mel_bands;
+  mgx::Outputs d{};
+  const mgx::Outputs h = [&] {  // the same layout, host addresses
+    mgx::Outputs r{};
     size_t off = 0;
     auto take = [&](size_t bytes) { const size_t at = off; off += (bytes + 255) / 256 * 256; return at; };
-    size_t at[19];
+    size_t at[20];
     for (int k = 0; k < MGX_NUM_SCALARS; ++k) at[k] = o->scalars[k] ? take(nframes * ss) : 0;
     at[13] = o->loudness_specific ? take(nframes * nb * 4) : 0;
     at[14] = o->mfcc ? take(nframes * nc * 4) : 0;
@@ -1239,6 +1264,7 @@ int extract_host_small(mgx_plan* p, uint64_t nframes, uint64_t stride, const mgx
     at[16] = o->power_spectrum ? take(nframes * L * 4) : 0;
     at[17] = o->complex_real ? take(nframes * (size_t)n * 4) : 0;
     at[18] = o->complex_imag ? take(nframes * (size_t)n * 4) : 0;
+    at[19] = o->mel_bands ? take(nframes * nm * 4) : 0;
     unsigned char* dv = static_cast<unsigned char*>(dout);
     for (int k = 0; k < MGX_NUM_SCALARS; ++k) {
       d.scalars[k] = o->scalars[k] ? dv + at[k] : nullptr;
@@ -1254,6 +1280,7 @@ int extract_host_small(mgx_plan* p, uint64_t nframes, uint64_t stride, const mgx
     both(o->power_spectrum, at[16], d.power_spectrum, r.power_spectrum);
     both(o->complex_real, at[17], d.complex_real, r.complex_real);
     both(o->complex_imag, at[18], d.complex_imag, r.complex_imag);
+    both(o->mel_bands, at[19], d.mel_bands, r.mel_bands);
     return r;
   }();
   if (!p->h_done) {
@@ -1279,21 +1306,24 @@ int extract_host_small(mgx_plan* p, uint64_t nframes, uint64_t stride, const mgx
   uint32_t* const ddone = p->d_done_map;
   // never 0 (the word's initial value) nor the resident launch's stop word
   p->done_seq = (p->done_seq + 1 == 0 || p->done_seq + 1 == mgx::kResStop) ? 1 : p->done_seq + 1;
-  // One frame without spectrum outputs (at most 13 + 24 + 32 words): the host waits on the output words
+  // One frame without spectrum outputs (at most 13 + 24 + 32 + 64 words): the host waits on the output words
   // themselves -- each preset to an all-ones NaN and polled until the kernel's store has landed -- and the
   // launch releases no completion word, which spares the system-scope release (a wait for the outputs'
   // write acknowledgements) and the word's own trip back. Stores of 4 and 8 aligned bytes arrive whole. An
   // output that is itself that NaN (a NaN input can carry any payload) only ends the spin at its limit.
   const bool word_wait = nframes == 1 && !o->amplitude_spectrum && !o->power_spectrum && !o->complex_real && !o->complex_imag;
   constexpr uint64_t kSent = ~(uint64_t)0;
-  if (word_wait && !(p->resident && nframes == 1)) {
+  // MGX_FLAG_RESIDENT: the resident workgroup serves one-frame calls for the mgx_outputs fields; one that asks
+  // for mel_bands takes the launch below (which ends the resident one first, as any other launch does)
+  const bool res = p->resident && nframes == 1 && !o->mel_bands;
+  if (word_wait && !res) {
     for (int k = 0; k < MGX_NUM_SCALARS; ++k)
       if (o->scalars[k]) memset(h.scalars[k], 0xFF, ss);
     if (o->loudness_specific) memset(h.loudness_specific, 0xFF, nb * 4);
     if (o->mfcc) memset(h.mfcc, 0xFF, nc * 4);
+    if (o->mel_bands) memset(h.mel_bands, 0xFF, nm * 4);
     std::atomic_thread_fence(std::memory_order_release);
   }
-  const bool res = p->resident && nframes == 1;
   if (res) {
     rc = resident_request(p, o, d, p->done_seq);
     if (rc) return rc;
@@ -1326,6 +1356,7 @@ int extract_host_small(mgx_plan* p, uint64_t nframes, uint64_t stride, const mgx
       if (o->scalars[k]) wait_word(h.scalars[k], ss);
     for (size_t i = 0; o->loudness_specific && i < nb; ++i) wait_word(h.loudness_specific + i, 4);
     for (size_t i = 0; o->mfcc && i < nc; ++i) wait_word(h.mfcc + i, 4);
+    for (size_t i = 0; o->mel_bands && i < nm; ++i) wait_word(h.mel_bands + i, 4);
     if (late) {  // a busy device, a failed launch, or an output equal to the preset: the stream decides
       e = hipStreamSynchronize(p->s_comp);
       if (e != hipSuccess) return hip_fail(e, "small host batch");
@@ -1358,6 +1389,7 @@ int extract_host_small(mgx_plan* p, uint64_t nframes, uint64_t stride, const mgx
     if (o->scalars[k]) memcpy(o->scalars[k], h.scalars[k], nframes * ss);
   if (o->loudness_specific) memcpy(o->loudness_specific, h.loudness_specific, nframes * nb * 4);
   if (o->mfcc) memcpy(o->mfcc, h.mfcc, nframes * nc * 4);
+  if (o->mel_bands) memcpy(o->mel_bands, h.mel_bands, nframes * nm * 4);
   if (o->amplitude_spectrum) memcpy(o->amplitude_spectrum, h.amplitude_spectrum, nframes * L * 4);
   if (o->power_spectrum) memcpy(o->power_spectrum, h.power_spectrum, nframes * L * 4);
   if (o->complex_real) memcpy(o->complex_real, h.complex_real, nframes * (size_t)n * 4);
@@ -1377,19 +1409,16 @@ uint64_t signal_chunk_frames(const mgx_plan* p, uint64_t hop) {
 // stride: the samples between the starts of consecutive frames in a slot (N: dense frames; a signal's
 // hop: `fill` then writes a chunk's (cnt - 1) stride + N samples); chunk_max: frames per chunk.
 template <typename Fill>
-int extract_host_chunked(mgx_plan* p, uint64_t nframes, uint64_t stride, uint64_t chunk_max, const mgx_outputs* o, Fill fill) {
+int extract_host_chunked(mgx_plan* p, uint64_t nframes, uint64_t stride, uint64_t chunk_max, const mgx::Outputs* o, Fill fill) {
   const int n = p->n, L = p->L;
   const size_t ss = p->d.scalar_f64 ? 8 : 4;
-  const size_t nb = mgx::kBark, nc = p->d.num_mfcc_coeffs;
+  const size_t nb = mgx::kBark, nc = p->d.num_mfcc_coeffs, nm = p->d.num_mel_bands;
   // device bytes per frame for the requested outputs
-  size_t per = 0;
-  for (int i = 0; i < MGX_NUM_SCALARS; ++i) per += o->scalars[i] ? ss : 0;
-  per += (o->loudness_specific ? nb * 4 : 0) + (o->mfcc ? nc * 4 : 0) + (o->amplitude_spectrum ? L * 4 : 0) +
-         (o->power_spectrum ? L * 4 : 0) + (o->complex_real ? 2 * (size_t)n * 4 : 0);
+  const size_t per = out_bytes_per_frame(p, o);
   const uint64_t chunk = std::min<uint64_t>(nframes, chunk_max);
   // (the slot in whole frames of N floats: the chunk's span, at most kHostChunk frames' worth)
   const uint64_t slot_frames = ((chunk - 1) * stride + (uint64_t)n + (uint64_t)n - 1) / (uint64_t)n;
-  int rc = ensure_host_staging(p, slot_frames, per * chunk + 4096);
+  int rc = ensure_host_staging(p, slot_frames, per * chunk + 21 * 256);
   if (rc) return rc;
   const uint64_t nch = (nframes + chunk - 1) / chunk;
   hipError_t e = hipSuccess;
@@ -1404,7 +1433,7 @@ int extract_host_chunked(mgx_plan* p, uint64_t nframes, uint64_t stride, uint64_
   for (uint64_t i = 0; i < nch && e == hipSuccess; ++i) {
     const int sl = (int)(i & 1);
     const uint64_t f0 = i * chunk, cnt = std::min<uint64_t>(chunk, nframes - f0);
-    mgx_outputs d{};
+    mgx::Outputs d{};
     size_t off = 0;
     auto take = [&](size_t bytes) { unsigned char* q = p->s_out[sl] + off; off += (bytes + 255) / 256 * 256; return q; };
     for (int k = 0; k < MGX_NUM_SCALARS; ++k) d.scalars[k] = o->scalars[k] ? take(cnt * ss) : nullptr;
@@ -1414,6 +1443,7 @@ int extract_host_chunked(mgx_plan* p, uint64_t nframes, uint64_t stride, uint64_
     d.power_spectrum = o->power_spectrum ? reinterpret_cast<float*>(take(cnt * L * 4)) : nullptr;
     d.complex_real = o->complex_real ? reinterpret_cast<float*>(take(cnt * n * 4)) : nullptr;
     d.complex_imag = o->complex_imag ? reinterpret_cast<float*>(take(cnt * n * 4)) : nullptr;
+    d.mel_bands = o->mel_bands ? reinterpret_cast<float*>(take(cnt * nm * 4)) : nullptr;
     // extraction of chunk i: after its frames arrived and chunk i-2's outputs left the slot
     e = hipStreamWaitEvent(p->s_comp, p->ev_loaded[sl], 0);
     if (e == hipSuccess && i >= 2) e = hipStreamWaitEvent(p->s_comp, p->ev_back[sl], 0);
@@ -1443,6 +1473,7 @@ int extract_host_chunked(mgx_plan* p, uint64_t nframes, uint64_t stride, uint64_
     if (e == hipSuccess && o->power_spectrum) e = back(o->power_spectrum + f0 * L, d.power_spectrum, cnt * L * 4);
     if (e == hipSuccess && o->complex_real) e = back(o->complex_real + f0 * n, d.complex_real, cnt * n * 4);
     if (e == hipSuccess && o->complex_imag) e = back(o->complex_imag + f0 * n, d.complex_imag, cnt * n * 4);
+    if (e == hipSuccess && o->mel_bands) e = back(o->mel_bands + f0 * nm, d.mel_bands, cnt * nm * 4);
     if (e == hipSuccess) e = hipEventRecord(p->ev_back[sl], p->s_copy);
   }
   if (e == hipSuccess) e = hipStreamSynchronize(p->s_copy);
@@ -1470,26 +1501,22 @@ extern "C" {
 
 int mgx_extract_host(mgx_plan* p, const float* frames, uint64_t nframes, const mgx_outputs* o) {
   if (!p || !o) return fail(MGX_E_INVALID_ARGUMENT, "NULL plan or outputs");
-  if (nframes == 0) return MGX_OK;
-  if (!frames) return fail(MGX_E_INVALID_ARGUMENT, "frames is NULL");
-  if ((o->complex_real == nullptr) != (o->complex_imag == nullptr))
-    return fail(MGX_E_INVALID_ARGUMENT, "complex_real and complex_imag must be given together");
-  const int n = p->n;
-  if (nframes <= p->small_max)
-    return extract_host_small(p, nframes, (uint64_t)n, o, [&](float* dst) {
-      memcpy(dst, frames, nframes * (size_t)n * sizeof(float));
-      return MGX_OK;
-    });
-  return extract_host_chunked(p, nframes, (uint64_t)n, kHostChunk, o, [&](uint64_t f0, uint64_t cnt, int slot, hipStream_t st) {
-    hipError_t e = hipMemcpyAsync(p->s_frames[slot], frames + f0 * n, cnt * n * sizeof(float), hipMemcpyHostToDevice, st);
-    return e == hipSuccess ? MGX_OK : hip_fail(e, "hipMemcpyAsync(frames)");
-  });
+  return mgx_extract_host_ex(p, frames, nframes * (uint64_t)p->n, (uint32_t)p->n, o, nullptr);
 }
 
 int mgx_extract_signal_host(mgx_plan* p, const float* samples, uint64_t num_samples, uint32_t hop, const mgx_outputs* o) {
-  if (!p || !o) return fail(MGX_E_INVALID_ARGUMENT, "NULL plan or outputs");
+  return mgx_extract_host_ex(p, samples, num_samples, hop, o, nullptr);
+}
+
+int mgx_extract_host_ex(mgx_plan* p, const float* samples, uint64_t num_samples, uint32_t hop, const mgx_outputs* outputs,
+                        const mgx_aux_outputs* aux) {
+  if (!p || !outputs) return fail(MGX_E_INVALID_ARGUMENT, "NULL plan or outputs");
+  mgx::Outputs x;
+  int rc = make_outputs(outputs, aux, &x);
+  if (rc) return rc;
+  const mgx::Outputs* const o = &x;
   uint64_t nframes = 0;
-  int rc = mgx_signal_frames(num_samples, (uint32_t)p->n, hop, &nframes);
+  rc = mgx_signal_frames(num_samples, (uint32_t)p->n, hop, &nframes);
   if (rc) return rc;
   if (nframes == 0) return MGX_OK;
   if (!samples) return fail(MGX_E_INVALID_ARGUMENT, "samples is NULL");
@@ -1588,7 +1615,7 @@ namespace {
 
 // mgx_extract_host_pcm (hop = N: floor(sample_frames / N) disjoint buffers) and mgx_extract_signal_host_pcm
 int extract_host_pcm_impl(mgx_plan* p, const void* pcm, uint64_t pcm_bytes, uint64_t sample_frames, uint32_t format,
-                          uint32_t channels, uint32_t channel, uint64_t hop, const mgx_outputs* o) {
+                          uint32_t channels, uint32_t channel, uint64_t hop, const mgx::Outputs* o) {
   const uint32_t bps = sample_bytes(format);
   if (!bps) return fail(MGX_E_INVALID_ARGUMENT, "unknown PCM format %u", format);
   if (channels == 0 || channel >= channels) return fail(MGX_E_INVALID_ARGUMENT, "channel %u of %u", channel, channels);
@@ -1634,14 +1661,23 @@ extern "C" {
 int mgx_extract_host_pcm(mgx_plan* p, const void* pcm, uint64_t pcm_bytes, uint64_t sample_frames, uint32_t format,
                          uint32_t channels, uint32_t channel, const mgx_outputs* o) {
   if (!p || !o) return fail(MGX_E_INVALID_ARGUMENT, "NULL plan or outputs");
-  return extract_host_pcm_impl(p, pcm, pcm_bytes, sample_frames, format, channels, channel, (uint64_t)p->n, o);
+  return mgx_extract_host_pcm_ex(p, pcm, pcm_bytes, sample_frames, format, channels, channel, (uint32_t)p->n, o, nullptr);
 }
 
 int mgx_extract_signal_host_pcm(mgx_plan* p, const void* pcm, uint64_t pcm_bytes, uint64_t sample_frames, uint32_t format,
                                 uint32_t channels, uint32_t channel, uint32_t hop, const mgx_outputs* o) {
+  return mgx_extract_host_pcm_ex(p, pcm, pcm_bytes, sample_frames, format, channels, channel, hop, o, nullptr);
+}
+
+int mgx_extract_host_pcm_ex(mgx_plan* p, const void* pcm, uint64_t pcm_bytes, uint64_t sample_frames, uint32_t format,
+                            uint32_t channels, uint32_t channel, uint32_t hop, const mgx_outputs* o,
+                            const mgx_aux_outputs* aux) {
   if (!p || !o) return fail(MGX_E_INVALID_ARGUMENT, "NULL plan or outputs");
   if (hop == 0) return fail(MGX_E_INVALID_ARGUMENT, "hop is 0 (a hop of at least one sample)");
-  return extract_host_pcm_impl(p, pcm, pcm_bytes, sample_frames, format, channels, channel, hop, o);
+  mgx::Outputs x;
+  const int rc = make_outputs(o, aux, &x);
+  if (rc) return rc;
+  return extract_host_pcm_impl(p, pcm, pcm_bytes, sample_frames, format, channels, channel, hop, &x);
 }
 
 int mgx_synth_frames_device(float* frames, uint64_t nframes, uint32_t n, uint64_t seed, uint64_t first_frame, void* stream) {

@@ -20,4 +20,6 @@ module.exports = {
   perceptualSpread: { type: 'number' },
   perceptualSharpness: { type: 'number' },
   mfcc: { type: 'array' },
+  // (not in the snapshot: later Meyda's melBands, the log mel band energies of mfcc.js:53-65)
+  melBands: { type: 'array' },
 };

@@ -22,6 +22,10 @@
 //   Meyda.signalFrames(numSamples, bufferSize, hopSize)
 //                                   how many buffers that is: (numSamples - bufferSize) / hopSize + 1
 //   Meyda.readWav(wavBytes)         the header: {pcmFormat, channels, sampleRate, sampleFrames, ...}
+//   'melBands'                      a feature name beyond the snapshot's 18 (later Meyda's melBands): the
+//                                   log mel band energies the MFCC is the DCT of (mfcc.js:53-65), a
+//                                   Float32Array(options.numMelBands) per buffer; in get(), start() and
+//                                   every getBatch* form, not with options.devices
 //   flush()                         deliver buffered callbacks now (options.batchFrames > 1)
 //   options.devices = [0, 1, ...]   shard batches over several GPUs; the feature records are
 //                                   gathered to the first one by RCCL (one plan per device)
@@ -52,7 +56,7 @@ const FEATURE_INFO = require('./feature-info');
 const GPU_FEATURES = new Set(['rms', 'energy', 'zcr', 'spectralCentroid', 'spectralFlatness',
   'spectralSlope', 'spectralRolloff', 'spectralSpread', 'spectralSkewness', 'spectralKurtosis',
   'perceptualSpread', 'perceptualSharpness', 'loudness', 'mfcc', 'amplitudeSpectrum',
-  'powerSpectrum', 'complexSpectrum']);
+  'powerSpectrum', 'complexSpectrum', 'melBands']);
 
 // src/utils.js:13-19
 function isPowerOfTwo(num) {
@@ -219,13 +223,14 @@ class Meyda {
     if (plugins) gpu.push('amplitudeSpectrum', 'complexSpectrum', 'loudness');
     const N = this.bufferSize;
     const frames = this._ring.slice(0, count * N);
+    this._checkNames(gpu);
     const r = gpu.length ? addon.extract(this._plan(), frames, gpu) : {};
     const keep = this.signal;
     for (let i = 0; i < count; i++) {
       const sig = frames.subarray(i * N, (i + 1) * N);
       this.signal = sig;
       this._frame = {};
-      for (const n of new Set(gpu)) this._frame[n] = frameValue(n, r, i, N, this.options.numMfccCoeffs);
+      for (const n of new Set(gpu)) this._frame[n] = frameValue(n, r, i, N, this.options.numMfccCoeffs, this.options.numMelBands);
       const out = typeof list === 'string' ? this._value(list) : this.get(names);
       this._callback(out);
     }
@@ -240,11 +245,12 @@ class Meyda {
   // callback. `signal` is a view of the queued frames, made only if read (the ring is reused by the
   // next batch); 'buffer' is a copy of the frame.
   _flushViews(count, list, names) {
-    const N = this.bufferSize, nc = this.options.numMfccCoeffs || 13;
+    const N = this.bufferSize, nc = this.options.numMfccCoeffs || 13, nm = this.options.numMelBands || 26;
     const frames = this._ring.subarray(0, count * N);
     this._flushing = this._ring;  // (a process() from a callback starts a new ring: these frames stay put)
     const gpu = Array.from(new Set(names.filter((n) => n !== 'buffer')));
-    const r = gpu.length ? extractViews(this._layouts, this._plan(), frames, gpu, N, nc) : {};
+    this._checkNames(gpu);
+    const r = gpu.length ? extractViews(this._layouts, this._plan(), frames, gpu, N, nc, nm) : {};
     const keep = this.signal;
     const cb = this._callback;
     const build = frameBuilder(typeof list === 'string' ? null : names, typeof list === 'string' ? list : null);
@@ -252,7 +258,7 @@ class Meyda {
       this._sigBatch = frames;
       this._sigIndex = i;
       this._frame = null;
-      cb(build(r, frames, i, N, nc));
+      cb(build(r, frames, i, N, nc, nm));
     }
     this._flushing = null;
     this.signal = keep;
@@ -312,9 +318,10 @@ class Meyda {
     for (let x = 0; x < names.length; x++) if (!(names[x] in fr)) need.push(names[x]);
     if (!need.length) return;
     // (into the layout's scratch buffer: frameValue copies every value out before anything else runs)
+    this._checkNames(need);
     const r = extractViews(this._layouts, this._plan(), this._signal(), need, this.bufferSize, this.options.numMfccCoeffs,
-      true);
-    for (const n of need) this._frame[n] = frameValue(n, r, 0, this.bufferSize, this.options.numMfccCoeffs);
+      this.options.numMelBands, true);
+    for (const n of need) this._frame[n] = frameValue(n, r, 0, this.bufferSize, this.options.numMfccCoeffs, this.options.numMelBands);
   }
 
   _value(name) {
@@ -347,12 +354,12 @@ class Meyda {
 
   // Batch API: frames is a Float32Array holding F consecutive buffers.
   getBatch(features, frames) {
-    const names = checkBatchNames(features);
+    const names = this._checkNames(checkBatchNames(features));
     return addon.extract(this._plan(), toF32(frames), names);
   }
 
   getBatchAsync(features, frames) {
-    const names = checkBatchNames(features);
+    const names = this._checkNames(checkBatchNames(features));
     const x = toF32(frames);
     return this._runAsync((plan) => addon.extractAsync(plan, x, names));
   }
@@ -360,14 +367,14 @@ class Meyda {
   // Every full buffer of a .wav file (Buffer / Uint8Array / ArrayBuffer), channel `channel`; with
   // hopSize, the buffers that start every hopSize samples of that channel.
   getBatchWav(features, wavBytes, channel, hopSize) {
-    const names = checkBatchNames(features);
+    const names = this._checkNames(checkBatchNames(features));
     if (hopSize === undefined) return addon.extractWav(this._plan(), wavBytes, names, channel | 0);
     const hop = this._checkHop(hopSize);
     return addon.extractWav(this._plan(), wavBytes, names, channel | 0, hop);
   }
 
   getBatchWavAsync(features, wavBytes, channel, hopSize) {
-    const names = checkBatchNames(features);
+    const names = this._checkNames(checkBatchNames(features));
     if (hopSize === undefined) return this._runAsync((plan) => addon.extractWavAsync(plan, wavBytes, names, channel | 0));
     const hop = this._checkHop(hopSize);
     return this._runAsync((plan) => addon.extractWavAsync(plan, wavBytes, names, channel | 0, hop));
@@ -376,13 +383,13 @@ class Meyda {
   // Overlapping buffers of one contiguous signal: buffer f is samples [f hopSize, f hopSize + bufferSize),
   // Meyda.signalFrames(samples.length, bufferSize, hopSize) of them; results as getBatch's.
   getBatchSignal(features, samples, hopSize) {
-    const names = checkBatchNames(features);
+    const names = this._checkNames(checkBatchNames(features));
     const hop = this._checkHop(hopSize);
     return addon.extractSignal(this._plan(), toF32(samples), hop, names);
   }
 
   getBatchSignalAsync(features, samples, hopSize) {
-    const names = checkBatchNames(features);
+    const names = this._checkNames(checkBatchNames(features));
     const hop = this._checkHop(hopSize);
     const x = toF32(samples);
     return this._runAsync((plan) => addon.extractSignalAsync(plan, x, hop, names));
@@ -400,6 +407,15 @@ class Meyda {
     return hopSize;
   }
 
+  // 'melBands' is an auxiliary output of the C ABI (mgx_aux_outputs), which the device groups of
+  // options.devices do not take (include/meyda_gpu.h): refused here, before the addon is called.
+  _checkNames(names) {
+    if (Array.isArray(this.options.devices) && names.indexOf('melBands') >= 0) {
+      throw new Error('melBands is not supported with options.devices: device groups take no auxiliary outputs');
+    }
+    return names;
+  }
+
   static signalFrames(numSamples, bufferSize, hopSize) {
     if (typeof hopSize !== 'number' || !Number.isInteger(hopSize) || hopSize < 1 || hopSize > 4294967295) {
       throw new RangeError('hopSize must be a positive integer, got ' + String(hopSize));
@@ -412,8 +428,8 @@ class Meyda {
   }
 
   // Per-frame view of a batch result, in the shapes get() returns.
-  static frame(result, name, index, bufferSize, numMfccCoeffs) {
-    return frameValue(name, result, index, bufferSize, numMfccCoeffs);
+  static frame(result, name, index, bufferSize, numMfccCoeffs, numMelBands) {
+    return frameValue(name, result, index, bufferSize, numMfccCoeffs, numMelBands);
   }
 
   // Frees the device plans now. A plan an async job still owns is left to that job: the
@@ -428,11 +444,12 @@ class Meyda {
   }
 }
 
-// The output fields of the C ABI in mgx_outputs order (the addon's extractInto offsets) and the result
-// keys each requested feature fills.
+// The output fields of the C ABI in mgx_outputs order, then mgx_aux_outputs' (the addon's extractInto
+// offsets) and the result keys each requested feature fills.
 const FIELDS = ['rms', 'energy', 'zcr', 'spectralCentroid', 'spectralFlatness', 'spectralSlope', 'spectralRolloff',
   'spectralSpread', 'spectralSkewness', 'spectralKurtosis', 'loudness.total', 'perceptualSpread', 'perceptualSharpness',
-  'loudness.specific', 'mfcc', 'amplitudeSpectrum', 'powerSpectrum', 'complexSpectrum.real', 'complexSpectrum.imag'];
+  'loudness.specific', 'mfcc', 'amplitudeSpectrum', 'powerSpectrum', 'complexSpectrum.real', 'complexSpectrum.imag',
+  'melBands'];
 const KEYS_OF = { loudness: ['loudness.specific', 'loudness.total'],
   complexSpectrum: ['complexSpectrum.real', 'complexSpectrum.imag'] };
 
@@ -447,15 +464,16 @@ FIELD_BITS.complexSpectrum = FIELD_BITS['complexSpectrum.real'] + FIELD_BITS['co
 // extract()'s keys and shapes (scalars as Float64Array: the facade's plans use scalarF64). One
 // allocation and a few N-API calls per launch instead of an ArrayBuffer, a reference and a typed array
 // per output (the real-time paths).
-function extractViews(cache, plan, frames, names, N, nc, scratch) {
+function extractViews(cache, plan, frames, names, N, nc, nm, scratch) {
   const F = frames.length / N;
   let bits = 0;
   for (let j = 0; j < names.length; j++) bits += FIELD_BITS[names[j]] || 0;  // (names are distinct)
   const key = F < 4194304 ? bits * 4194304 + F : bits + ':' + F;
   let lay = cache.get(key);
   if (!lay) {
-    const per = (i) => (i < 13 ? 1 : i === 13 ? 24 : i === 14 ? nc : i < 17 ? N / 2 : N);
-    const offsets = new Float64Array(19).fill(-1);
+    const per = (i) => (i < 13 ? 1 : i === 13 ? 24 : i === 14 ? nc : i === 19 ? nm || 26 : i < 17 ? N / 2 : N);
+    // (19 offsets, the mgx_outputs fields, unless melBands is asked for: then its offset is the 20th)
+    const offsets = new Float64Array(bits >= 2 ** 19 ? 20 : 19).fill(-1);
     const views = [];
     let at = 0;
     FIELDS.forEach((k, i) => {
@@ -497,6 +515,7 @@ function frameBuilder(names, single) {
       case 'buffer': return 'x.slice(i * N, i * N + N)';
       case 'loudness': return "{ specific: r['loudness.specific'].subarray(i * 24, i * 24 + 24), total: r['loudness.total'][i] }";
       case 'mfcc': return 'r.mfcc.subarray(i * nc, i * nc + nc)';
+      case 'melBands': return 'r.melBands.subarray(i * nm, i * nm + nm)';
       case 'amplitudeSpectrum': case 'powerSpectrum': return 'r.' + n + '.subarray(i * (N >> 1), i * (N >> 1) + (N >> 1))';
       case 'complexSpectrum': return "{ real: r['complexSpectrum.real'].subarray(i * N, i * N + N), " +
         "imag: r['complexSpectrum.imag'].subarray(i * N, i * N + N), length: N }";
@@ -505,7 +524,7 @@ function frameBuilder(names, single) {
   };
   const body = single !== null ? expr(single)
     : '{ ' + names.map((n) => JSON.stringify(n) + ': ' + expr(n)).join(', ') + ' }';
-  f = new Function('r', 'x', 'i', 'N', 'nc', 'return (' + body + ');');  // eslint-disable-line no-new-func
+  f = new Function('r', 'x', 'i', 'N', 'nc', 'nm', 'return (' + body + ');');  // eslint-disable-line no-new-func
   BUILDERS.set(key, f);
   return f;
 }
@@ -524,14 +543,17 @@ function checkBatchNames(features) {
 
 // Slice frame `i` of a SoA batch result into the reference's return shapes
 // (src/feature-info.js): numbers, Float32Array, {specific, total}, {real, imag}.
-function frameValue(name, r, i, n, ncoef) {
+function frameValue(name, r, i, n, ncoef, nmel) {
   ncoef = ncoef || 13;
+  nmel = nmel || 26;
   const L = n / 2;
   switch (name) {
     case 'loudness':
       return { specific: r['loudness.specific'].slice(i * 24, i * 24 + 24), total: r['loudness.total'][i] };
     case 'mfcc':
       return r.mfcc.slice(i * ncoef, i * ncoef + ncoef);
+    case 'melBands':
+      return r.melBands.slice(i * nmel, i * nmel + nmel);
     case 'amplitudeSpectrum':
       return r.amplitudeSpectrum.slice(i * L, i * L + L);
     case 'powerSpectrum':

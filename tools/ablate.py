@@ -90,7 +90,7 @@ PATCHES = {
     # (CHAIN) ... and the power rows as constants too (the chains' arithmetic alone)
     "chain_rconst": [("    const f32x4 n0 = kAhead ? prn[0] : p0, n1 = kAhead ? prn[1] : p1;",
                       "    const f32x4 n0 = p0 * 0.5f + 1.0f, n1 = p1 * 0.5f + 1.0f;")],
-    "no_mel": [("  } else if (!CHAIN && ap->need_mfcc) {\n    mel_energies", "  } else if (opaque(0) && !CHAIN && ap->need_mfcc) {\n    mel_energies")],
+    "no_mel": [("  } else if (!CHAIN && ap->need_mel) {\n    mel_energies", "  } else if (opaque(0) && !CHAIN && ap->need_mel) {\n    mel_energies")],
 }
 
 

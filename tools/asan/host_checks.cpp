@@ -177,7 +177,7 @@ static void arithmetic() {
   CHECK(mgx_packed_layout(nullptr, 1, 1, off) == 0);
   CHECK(mgx_feature_index(nullptr) == -1);
   CHECK(mgx_feature_index("") == -1);
-  CHECK(mgx_feature_name(-1) == nullptr && mgx_feature_name(19) == nullptr);
+  CHECK(mgx_feature_name(-1) == nullptr && mgx_feature_name(MGX_NUM_FEATURES) == nullptr);
   CHECK(mgx_is_power_of_two(0.0) == 0 && mgx_is_power_of_two(1.0) == 1 && mgx_is_power_of_two(-8.0) == 0);
 }
 
