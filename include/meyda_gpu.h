@@ -26,6 +26,9 @@
  *   mgx_extract_*_ex     the signal calls with the outputs added     src/extractors/mfcc.js:53-65
  *                        after mgx_outputs (mgx_aux_outputs):       (loggedMelBands, the Float32Array
  *                        melBands, the log mel band energies        the DCT of :67-93 reads)
+ *   mgx_extract_gather_* the same over buffers that start where a    src/meyda.js:69-91 (one source,
+ *   mgx_signals_frame_starts  table says: every buffer of every     one buffer per call)
+ *                        clip of a corpus in one launch
  *   mgx_group_*          several devices, RCCL gather of the        src/meyda.js:17-97 (one plan
  *                        per-frame records to the root device       per device), :69-91 (buffers
  *                                                                   are independent: shardable)
@@ -340,6 +343,57 @@ int mgx_extract_host_ex(mgx_plan* plan, const float* samples, uint64_t num_sampl
 int mgx_extract_host_pcm_ex(mgx_plan* plan, const void* pcm, uint64_t pcm_bytes, uint64_t sample_frames,
                             uint32_t format, uint32_t channels, uint32_t channel, uint32_t hop,
                             const mgx_outputs* outputs, const mgx_aux_outputs* aux);
+
+/* ---- Buffers at given sample offsets: many signals in one launch ------------------------
+ * Replaces, in a host application, the loop over a corpus that slices every clip into buffers and hands
+ * each to the reference (src/meyda.js:69-91, one buffer per call; the signal calls above, one clip per
+ * call): buffer f of the launch is samples [starts[f], starts[f] + N) of one array, wherever the caller
+ * says. One launch then covers every buffer of every clip (mgx_signals_frame_starts), random crops,
+ * onset-aligned buffers, or channels stored one after another.
+ *
+ * Starts in any order are legal: they may repeat, overlap and be odd; `samples` and every buffer need only
+ * float (4-byte) alignment. num_frames = 0 returns MGX_OK and writes nothing; num_frames > 0 with starts =
+ * NULL or num_samples < N is MGX_E_INVALID_ARGUMENT. Outputs are laid out exactly as for mgx_extract_device
+ * with that num_frames, and every output of every plan kind (both precisions, literal mode, both windows,
+ * every flag; mel_bands included) equals, bit for bit, what mgx_extract_device gives on the same buffers
+ * stored densely. Multi-device groups (mgx_group_*) take dense buffers only; PCM goes through
+ * mgx_pcm_decode_device first. */
+
+/* The starts of every buffer of a corpus stored as one array. Replaces the per-clip slicing loop's
+ * bookkeeping (src/meyda.js:69-91 delivers the buffers of one source only). Host only (no device).
+ * offsets[0..num_signals], non-decreasing: signal s is samples [offsets[s], offsets[s + 1]). Signal s gives
+ * mgx_signal_frames(its length, N, hop) buffers, buffer k at offsets[s] + k * hop: no buffer crosses a
+ * signal's end. frame_offsets (num_signals + 1 entries, or NULL): the prefix sums of those counts, so signal
+ * s's rows of every output are [frame_offsets[s], frame_offsets[s + 1]). starts (or NULL: count only): the
+ * start of every buffer, in signal order; capacity: the entries it holds. *num_frames: the total.
+ * MGX_E_INVALID_ARGUMENT (nothing written): hop = 0, decreasing offsets, a non-NULL starts with capacity
+ * below the total, NULL offsets or num_frames. */
+int mgx_signals_frame_starts(const uint64_t* offsets, uint64_t num_signals, uint32_t buffer_size, uint32_t hop,
+                             uint64_t* frame_offsets, uint64_t* starts, uint64_t capacity, uint64_t* num_frames);
+
+/* mgx_extract_device (src/meyda.js:69-91,244-261) over buffers at given starts. samples, starts (num_frames
+ * entries) and every output are device pointers; asynchronous on `stream`, with the same per-stream scratch,
+ * first-call rule and graph-capture property as mgx_extract_device (the table is read by the launch: keep it
+ * unchanged until the launch, or every replay of a graph that holds it, has ended). aux as in the _ex calls
+ * (NULL allowed). The host cannot see the table, so the kernel reads buffer f at min(starts[f], num_samples - N):
+ * nothing outside samples[0, num_samples) is read whatever the table holds, and a start beyond the last whole
+ * buffer gives that buffer's outputs. Nothing of `starts` beyond its num_frames entries is read (the kernel's
+ * loads past the last buffer are clamped to buffer num_frames - 1, as everywhere in this ABI). */
+int mgx_extract_gather_device(mgx_plan* plan, const float* samples, uint64_t num_samples, const uint64_t* starts,
+                              uint64_t num_frames, const mgx_outputs* outputs, const mgx_aux_outputs* aux, void* stream);
+
+/* mgx_extract_host over buffers at given starts: host pointers throughout; returns when the outputs are
+ * written. A start above num_samples - N is MGX_E_INVALID_ARGUMENT before any copy (the message names its
+ * index). Up to 512 buffers are gathered densely into the pinned input buffer and run the one-launch path
+ * of mgx_extract_host (one buffer: the kernel-argument frame, or the resident workgroup of a
+ * MGX_FLAG_RESIDENT plan). Larger batches go through the two staging slots of the dense path in chunks: a
+ * chunk is the longest run of consecutive buffers of at most 65,536 whose span, max(start) + N - min(start),
+ * fits a slot (65,536 * N floats; one buffer always fits). The span crosses PCIe once per chunk, with the
+ * chunk's starts (8 bytes per buffer) beside it. Sorted starts -- what mgx_signals_frame_starts gives -- fill
+ * their chunks; starts in arbitrary order are served correctly, but every jump of more than a slot ends a
+ * chunk, down to one buffer per chunk. */
+int mgx_extract_gather_host(mgx_plan* plan, const float* samples, uint64_t num_samples, const uint64_t* starts,
+                            uint64_t num_frames, const mgx_outputs* outputs, const mgx_aux_outputs* aux);
 
 /* ---- Multi-device groups -------------------------------
  * Replaces nothing in the reference (single-threaded browser code); it exists because

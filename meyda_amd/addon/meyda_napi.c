@@ -247,6 +247,9 @@ typedef struct {
    * the PCM's channel), cut into nframes = mgx_signal_frames() buffers that start every hop samples */
   uint32_t hop;
   uint64_t nsamples;
+  /* extractGather: `frames` is nsamples samples, buffer f starts at starts[f] (malloc'd, nframes entries) */
+  uint64_t* starts;
+  int gather;
   mgx_outputs out;
   mgx_aux_outputs aux;  /* melBands (SLOT_MEL): the job then makes the mgx_extract_*_ex call */
   /* The outputs are written straight into JS ArrayBuffers (napi_create_arraybuffer), held by
@@ -266,6 +269,8 @@ typedef struct {
 } job;
 
 static void job_free_buffers(napi_env env, job* j) {
+  free(j->starts);
+  j->starts = NULL;
   for (int i = 0; i < NSLOTS; ++i)
     if (j->refs[i]) {
       napi_delete_reference(env, j->refs[i]);
@@ -389,6 +394,69 @@ static int job_prepare_signal(napi_env env, job* j, napi_value samples_v, napi_v
   return job_alloc(env, j, feats);
 }
 
+/* A Float64Array of non-negative safe integers (sample indices, lengths) as uint64; `what` names it in the
+ * RangeError. Returns a malloc'd array (NULL with an exception pending), *count entries (one at least is
+ * allocated, so an empty table is not mistaken for a failure). */
+static uint64_t* u64_of_f64(napi_env env, napi_value v, const char* what, size_t* count) {
+  bool is_ta = false;
+  napi_typedarray_type tt = napi_int8_array;
+  size_t len = 0, off = 0;
+  void* data = NULL;
+  napi_value ab;
+  char msg[128];
+  napi_is_typedarray(env, v, &is_ta);
+  if (is_ta) napi_get_typedarray_info(env, v, &tt, &len, &data, &ab, &off);
+  if (!is_ta || tt != napi_float64_array) {
+    snprintf(msg, sizeof msg, "%s must be a Float64Array", what);
+    napi_throw_type_error(env, NULL, msg);
+    return NULL;
+  }
+  uint64_t* out = (uint64_t*)malloc((len ? len : 1) * sizeof *out);
+  if (!out) {
+    napi_throw_error(env, NULL, "out of host memory");
+    return NULL;
+  }
+  const double* d = (const double*)data;
+  for (size_t i = 0; i < len; ++i) {
+    if (!(d[i] >= 0) || d[i] > 9007199254740991.0 || d[i] != (double)(uint64_t)d[i]) {
+      snprintf(msg, sizeof msg, "%s[%zu] must be a non-negative safe integer", what, i);
+      free(out);
+      napi_throw_range_error(env, NULL, msg);
+      return NULL;
+    }
+    out[i] = (uint64_t)d[i];
+  }
+  *count = len;
+  return out;
+}
+
+/* extractGather(plan, samples, starts, features): buffer f is samples [starts[f], starts[f] + bufferSize) of one
+ * Float32Array; starts: a Float64Array of sample indices. */
+static int job_prepare_gather(napi_env env, job* j, napi_value samples_v, napi_value starts_v, napi_value feats) {
+  bool is_ta = false;
+  napi_typedarray_type tt = napi_int8_array;
+  size_t len = 0, off = 0, count = 0;
+  void* data = NULL;
+  napi_value ab;
+  napi_is_typedarray(env, samples_v, &is_ta);
+  if (is_ta) napi_get_typedarray_info(env, samples_v, &tt, &len, &data, &ab, &off);
+  if (!is_ta || tt != napi_float32_array) {
+    napi_throw_type_error(env, NULL, "samples must be a Float32Array");
+    return 0;
+  }
+  if (j->box->group) {
+    napi_throw_error(env, NULL, "starts are not supported on a plan created with `devices`: device groups take dense buffers only");
+    return 0;
+  }
+  j->starts = u64_of_f64(env, starts_v, "starts", &count);
+  if (!j->starts) return 0;
+  j->gather = 1;
+  j->frames = (const float*)data;
+  j->nsamples = len;
+  j->nframes = count;
+  return job_alloc(env, j, feats);
+}
+
 /* Wanted outputs for j->nframes frames. */
 static int job_alloc(napi_env env, job* j, napi_value feats) {
   const uint32_t n = j->box->desc.buffer_size;
@@ -506,7 +574,10 @@ static void job_run(job* j) {
     return;
   }
   const uint32_t n = j->box->desc.buffer_size;
-  if (j->box->group)
+  if (j->gather)
+    j->rc = mgx_extract_gather_host(j->box->plan, j->frames, j->nsamples, j->starts, j->nframes, &j->out,
+                                    j->want[SLOT_MEL] ? &j->aux : NULL);
+  else if (j->box->group)
     j->rc = mgx_group_extract_host(j->box->group, j->frames, j->nframes, &j->out);
   else if (j->want[SLOT_MEL] && j->pcm)  /* (a dense batch is the signal form at hop N) */
     j->rc = mgx_extract_host_pcm_ex(j->box->plan, j->pcm, j->pcm_bytes, j->pcm_frames, j->pcm_format, j->pcm_channels,
@@ -555,11 +626,12 @@ static napi_value job_result(napi_env env, job* j) {
 }
 
 /* kind: the input of an extraction job */
-enum { IN_FRAMES = 0, IN_WAV = 1, IN_SIGNAL = 2 };
+enum { IN_FRAMES = 0, IN_WAV = 1, IN_SIGNAL = 2, IN_GATHER = 3 };
 
 static int job_prepare_kind(napi_env env, job* j, int kind, size_t argc, napi_value* argv) {
   if (kind == IN_WAV) return job_prepare_wav(env, j, argv[1], argv[2], argc > 3 ? argv[3] : NULL, argc > 4 ? argv[4] : NULL);
   if (kind == IN_SIGNAL) return job_prepare_signal(env, j, argv[1], argv[2], argv[3]);
+  if (kind == IN_GATHER) return job_prepare_gather(env, j, argv[1], argv[2], argv[3]);
   return job_prepare(env, j, argv[1], argv[2]);
 }
 
@@ -567,8 +639,9 @@ static napi_value extract_common(napi_env env, napi_callback_info info, int kind
   size_t argc = 5;
   napi_value argv[5];
   CHECK(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
-  if (argc < (kind == IN_SIGNAL ? 4u : 3u)) {
+  if (argc < (kind == IN_SIGNAL || kind == IN_GATHER ? 4u : 3u)) {
     napi_throw_type_error(env, NULL, kind == IN_WAV ? "extractWav(plan, wavBytes, features[, channel[, hop]])"
+                                   : kind == IN_GATHER ? "extractGather(plan, samples, starts, features)"
                                    : kind == IN_SIGNAL ? "extractSignal(plan, samples, hop, features)"
                                                        : "extract(plan, frames, features)");
     return NULL;
@@ -698,6 +771,7 @@ static napi_value extract_into(napi_env env, napi_callback_info info) {
 static napi_value extract_sync(napi_env env, napi_callback_info info) { return extract_common(env, info, IN_FRAMES); }
 static napi_value extract_wav_sync(napi_env env, napi_callback_info info) { return extract_common(env, info, IN_WAV); }
 static napi_value extract_signal_sync(napi_env env, napi_callback_info info) { return extract_common(env, info, IN_SIGNAL); }
+static napi_value extract_gather_sync(napi_env env, napi_callback_info info) { return extract_common(env, info, IN_GATHER); }
 
 static void async_execute(napi_env env, void* data) {
   (void)env;
@@ -728,8 +802,9 @@ static napi_value extract_async_common(napi_env env, napi_callback_info info, in
   size_t argc = 5;
   napi_value argv[5];
   CHECK(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
-  if (argc < (kind == IN_SIGNAL ? 4u : 3u)) {
+  if (argc < (kind == IN_SIGNAL || kind == IN_GATHER ? 4u : 3u)) {
     napi_throw_type_error(env, NULL, kind == IN_WAV ? "extractWavAsync(plan, wavBytes, features[, channel[, hop]])"
+                                   : kind == IN_GATHER ? "extractGatherAsync(plan, samples, starts, features)"
                                    : kind == IN_SIGNAL ? "extractSignalAsync(plan, samples, hop, features)"
                                                        : "extractAsync(plan, frames, features)");
     return NULL;
@@ -761,6 +836,84 @@ static napi_value extract_async_common(napi_env env, napi_callback_info info, in
 static napi_value extract_async(napi_env env, napi_callback_info info) { return extract_async_common(env, info, IN_FRAMES); }
 static napi_value extract_wav_async(napi_env env, napi_callback_info info) { return extract_async_common(env, info, IN_WAV); }
 static napi_value extract_signal_async(napi_env env, napi_callback_info info) { return extract_async_common(env, info, IN_SIGNAL); }
+static napi_value extract_gather_async(napi_env env, napi_callback_info info) { return extract_async_common(env, info, IN_GATHER); }
+
+/* signalsFrameStarts(lengths, bufferSize, hop): mgx_signals_frame_starts (host only) for signals stored one after
+ * another; lengths: a Float64Array. Returns {starts, frameOffsets}, Float64Arrays. */
+static napi_value signals_frame_starts(napi_env env, napi_callback_info info) {
+  size_t argc = 3;
+  napi_value argv[3];
+  CHECK(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  if (argc < 3) {
+    napi_throw_type_error(env, NULL, "signalsFrameStarts(lengths, bufferSize, hop)");
+    return NULL;
+  }
+  double v[2] = {0, 0};
+  for (int i = 0; i < 2; ++i) {
+    napi_valuetype t = napi_undefined;
+    napi_typeof(env, argv[1 + i], &t);
+    if (t == napi_number) napi_get_value_double(env, argv[1 + i], &v[i]);
+    if (t != napi_number || !(v[i] >= 0) || v[i] > 4294967295.0 || v[i] != (double)(uint64_t)v[i]) {
+      napi_throw_range_error(env, NULL, "signalsFrameStarts(lengths, bufferSize, hop): non-negative integers");
+      return NULL;
+    }
+  }
+  size_t ns = 0;
+  uint64_t* len = u64_of_f64(env, argv[0], "lengths", &ns);
+  if (!len) return NULL;
+  uint64_t* off = (uint64_t*)malloc((ns + 1) * sizeof *off);
+  uint64_t* fo = (uint64_t*)malloc((ns + 1) * sizeof *fo);
+  uint64_t* st = NULL;
+  uint64_t total = 0;
+  napi_value r = NULL;
+  int rc = off && fo ? MGX_OK : MGX_E_OUT_OF_MEMORY;
+  if (!rc) {
+    off[0] = 0;
+    for (size_t i = 0; i < ns; ++i) {
+      /* (each length is below 2^53; their sum has to stay a sample index JavaScript can hold) */
+      if (len[i] > 9007199254740991ull - off[i]) {
+        char msg[96];
+        snprintf(msg, sizeof msg, "lengths[0..%zu] add up to more than a safe integer", i);
+        free(len);
+        free(off);
+        free(fo);
+        napi_throw_range_error(env, NULL, msg);
+        return NULL;
+      }
+      off[i + 1] = off[i] + len[i];
+    }
+    rc = mgx_signals_frame_starts(off, ns, (uint32_t)v[0], (uint32_t)v[1], NULL, NULL, 0, &total);
+  }
+  if (!rc) {
+    st = (uint64_t*)malloc((total ? total : 1) * sizeof *st);
+    rc = st ? mgx_signals_frame_starts(off, ns, (uint32_t)v[0], (uint32_t)v[1], fo, st, total, &total) : MGX_E_OUT_OF_MEMORY;
+  }
+  if (rc == MGX_E_OUT_OF_MEMORY) {
+    napi_throw_error(env, NULL, "out of host memory");
+  } else if (rc) {
+    throw_mgx(env, rc);
+  } else {
+    napi_value ab, ta, obj;
+    void* d = NULL;
+    if (napi_create_object(env, &obj) == napi_ok && napi_create_arraybuffer(env, total * 8, &d, &ab) == napi_ok &&
+        napi_create_typedarray(env, napi_float64_array, total, ab, 0, &ta) == napi_ok) {
+      for (uint64_t i = 0; i < total; ++i) ((double*)d)[i] = (double)st[i];
+      napi_set_named_property(env, obj, "starts", ta);
+      if (napi_create_arraybuffer(env, (ns + 1) * 8, &d, &ab) == napi_ok &&
+          napi_create_typedarray(env, napi_float64_array, ns + 1, ab, 0, &ta) == napi_ok) {
+        for (size_t i = 0; i <= ns; ++i) ((double*)d)[i] = (double)fo[i];
+        napi_set_named_property(env, obj, "frameOffsets", ta);
+        r = obj;
+      }
+    }
+    if (!r) napi_throw_error(env, NULL, "out of host memory");
+  }
+  free(len);
+  free(off);
+  free(fo);
+  free(st);
+  return r;
+}
 
 /* signalFrames(numSamples, bufferSize, hop): mgx_signal_frames (host only). */
 static napi_value signal_frames(napi_env env, napi_callback_info info) {
@@ -910,6 +1063,9 @@ static napi_value init(napi_env env, napi_value exports) {
       {"extractSignal", NULL, extract_signal_sync, NULL, NULL, NULL, napi_enumerable, NULL},
       {"extractSignalAsync", NULL, extract_signal_async, NULL, NULL, NULL, napi_enumerable, NULL},
       {"signalFrames", NULL, signal_frames, NULL, NULL, NULL, napi_enumerable, NULL},
+      {"extractGather", NULL, extract_gather_sync, NULL, NULL, NULL, napi_enumerable, NULL},
+      {"extractGatherAsync", NULL, extract_gather_async, NULL, NULL, NULL, napi_enumerable, NULL},
+      {"signalsFrameStarts", NULL, signals_frame_starts, NULL, NULL, NULL, napi_enumerable, NULL},
       {"wavParse", NULL, wav_parse, NULL, NULL, NULL, napi_enumerable, NULL},
       {"hostTables", NULL, host_tables, NULL, NULL, NULL, napi_enumerable, NULL},
       {"isPowerOfTwo", NULL, is_pow2, NULL, NULL, NULL, napi_enumerable, NULL},

@@ -37,6 +37,7 @@ EXPORTS = ["mgx_plan_desc_init", "mgx_plan_create", "mgx_plan_destroy", "mgx_pla
            "mgx_signal_frames", "mgx_extract_signal_device", "mgx_extract_signal_host",
            "mgx_extract_signal_host_pcm",
            "mgx_extract_device_ex", "mgx_extract_host_ex", "mgx_extract_host_pcm_ex",
+           "mgx_signals_frame_starts", "mgx_extract_gather_device", "mgx_extract_gather_host",
            "mgx_shard_range", "mgx_packed_layout", "mgx_comm_unique_id", "mgx_group_create",
            "mgx_group_create_rank", "mgx_group_create_loopback", "mgx_group_create_loopback_rccl", "mgx_group_destroy",
            "mgx_group_info", "mgx_group_comm_info", "mgx_group_extract_device", "mgx_group_extract_host"]
@@ -175,6 +176,12 @@ def lib():
         L.mgx_extract_host_pcm_ex.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64,
                                               ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
                                               ctypes.POINTER(Outputs), aux]
+        L.mgx_signals_frame_starts.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32,
+                                               ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, u64p]
+        L.mgx_extract_gather_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p,
+                                                ctypes.c_uint64, ctypes.POINTER(Outputs), aux, ctypes.c_void_p]
+        L.mgx_extract_gather_host.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p,
+                                              ctypes.c_uint64, ctypes.POINTER(Outputs), aux]
         L.mgx_shard_range.argtypes = [ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, u64p, u64p]
         L.mgx_packed_layout.argtypes = [ctypes.POINTER(PlanDesc), ctypes.c_uint32, ctypes.c_uint64, u64p]
         L.mgx_packed_layout.restype = ctypes.c_uint64
@@ -245,6 +252,23 @@ def signal_frames(num_samples, n, hop):
     f = ctypes.c_uint64()
     check(lib().mgx_signal_frames(num_samples, n, hop, ctypes.byref(f)))
     return f.value
+
+
+def signals_frame_starts(lengths_or_offsets, n, hop, offsets=False):
+    """The buffers of several signals stored one after another (mgx_signals_frame_starts; host only): `n`
+    samples each, `hop` apart within a signal, none across a signal's end. lengths_or_offsets: the signals'
+    lengths, or with offsets=True their num_signals + 1 offsets into the concatenated array. Returns
+    (starts, frame_offsets), uint64 arrays: the start of every buffer in signal order, and the
+    num_signals + 1 prefix sums of the signals' buffer counts."""
+    v = np.asarray(lengths_or_offsets, dtype=np.uint64).ravel()
+    off = np.ascontiguousarray(v) if offsets else np.concatenate([np.zeros(1, np.uint64), np.cumsum(v, dtype=np.uint64)])
+    ns = off.size - 1
+    total = ctypes.c_uint64()
+    check(lib().mgx_signals_frame_starts(off.ctypes.data, ns, n, hop, None, None, 0, ctypes.byref(total)))
+    starts, frame_offsets = np.empty(total.value, np.uint64), np.empty(ns + 1, np.uint64)
+    check(lib().mgx_signals_frame_starts(off.ctypes.data, ns, n, hop, frame_offsets.ctypes.data, starts.ctypes.data,
+                                         starts.size, ctypes.byref(total)))
+    return starts, frame_offsets
 
 
 def device_count():
@@ -353,7 +377,49 @@ class Plan:
         self.extract_signal_device(samples.data_ptr(), S, hop, o, stream)
         return out
 
+    def extract_gather_device(self, samples_ptr, num_samples, starts_ptr, num_frames, outputs, stream=None):
+        """Launch on device pointers: buffer f is samples [starts[f], starts[f] + N) (uint64 starts; async)."""
+        check(lib().mgx_extract_gather_device(self._h, ctypes.c_void_p(samples_ptr), num_samples, ctypes.c_void_p(starts_ptr),
+                                              num_frames, ctypes.byref(outputs), _aux_ref(outputs),
+                                              ctypes.c_void_p(stream or 0)))
+
+    def extract_gather_torch(self, samples, starts, features, stream=None):
+        """samples: a 1-D float32 CUDA tensor (any 4-byte alignment); starts: a 1-D int64 CUDA tensor of
+        non-negative sample indices (read as the ABI's uint64), or anything numpy turns into one. Returns a
+        dict of device tensors over the len(starts) buffers; the buffers are not materialised."""
+        import torch
+        assert samples.is_cuda and samples.dtype == torch.float32 and samples.is_contiguous() and samples.dim() == 1
+        if not torch.is_tensor(starts):
+            starts = torch.from_numpy(np.ascontiguousarray(starts, dtype=np.uint64).view(np.int64)).to(samples.device)
+        assert starts.is_cuda and starts.dtype == torch.int64 and starts.is_contiguous() and starts.dim() == 1
+        out, o = self.alloc_outputs(starts.shape[0], features, device=samples.device)
+        if stream is None:
+            stream = torch.cuda.current_stream(samples.device).cuda_stream
+        self.extract_gather_device(samples.data_ptr(), samples.shape[0], starts.data_ptr(), starts.shape[0], o, stream)
+        # (the launch reads the table: a caller who passes a stream other than torch's current one keeps
+        # `starts` alive until the launch has ended, as it does `samples`)
+        return out
+
     # ------------------------------------------------------------------ host
+    def extract_gather(self, samples, starts, features):
+        """Host numpy signal and starts in / numpy out: buffer f is samples [starts[f], starts[f] + N)."""
+        samples = np.ascontiguousarray(samples, dtype=np.float32)
+        starts = np.ascontiguousarray(starts, dtype=np.uint64)
+        assert samples.ndim == 1 and starts.ndim == 1
+        out, o = self._host_outputs(starts.size, features)
+        check(lib().mgx_extract_gather_host(self._h, samples.ctypes.data, samples.size, starts.ctypes.data, starts.size,
+                                            ctypes.byref(o), _aux_ref(o)))
+        return out
+
+    def extract_signals(self, signals, hop, features):
+        """A list of 1-D host signals in one call: every signal's buffers, `hop` apart, none across two signals.
+        Returns (outputs, frame_offsets): signal s's rows of every output are
+        [frame_offsets[s], frame_offsets[s + 1])."""
+        signals = [np.ascontiguousarray(x, dtype=np.float32).ravel() for x in signals]
+        starts, frame_offsets = signals_frame_starts([x.size for x in signals], self.n, hop)
+        samples = np.concatenate(signals) if signals else np.empty(0, np.float32)
+        return self.extract_gather(samples, starts, features), frame_offsets
+
     def extract_signal(self, samples, hop, features):
         """Host numpy signal in / numpy out, buffers every `hop` samples (stages the signal, not the buffers)."""
         samples = np.ascontiguousarray(samples, dtype=np.float32)

@@ -2059,14 +2059,63 @@ __device__ __forceinline__ bool res_wait(const uint64_t* mail, uint32_t seq, uin
 __device__ unsigned long long g_wave_times[65536 * 4];
 #endif
 
+// GATHER kernels (below): the start of frame f -- a scalar load of the launch's table (KernelArgsGather; f is
+// wave-uniform, and the table read-only for the launch, hence the constant address space), clamped, unsigned, to
+// the last start whose frame lies inside the samples. f < num_frames always (the callers clamp it), so no
+// entry past the table's num_frames is read.
+__device__ __forceinline__ uint64_t gather_start(uint64_t f) {
+  const auto q = (const __attribute__((address_space(4))) KernelArgsGather*)args_ptr();
+  const uint64_t s = ((const __attribute__((address_space(4))) uint64_t*)q->g.starts)[f];
+  return s < q->g.last_start ? s : q->g.last_start;
+}
+// Without a frame prefetch (Geo::PF == 0, N = 2048) the frame's own first loads would wait for that scalar
+// round trip, so the start of the frame the wave takes next (the next of its batch, then the first of its next
+// static batch) is loaded while this frame is computed and waits in two scalar registers beside its index;
+// any other frame (the wave's first, a batch from the tail pool) loads its start as it comes. With a prefetch
+// the start feeds loads whose data the NEXT frame needs (PF == 1 at the frame's start, PF == 2 in its middle):
+// the wave does wait for the scalar load there (s_load, lgkmcnt, the clamp, the address), but no data it is
+// about to use waits with it. Keeping the start a frame ahead at those N too (-DMGX_GATHER_AHEAD_ALL=1) measured
+// slower at N = 1024, where the kernels already spill SGPRs: with starts = f * 256 the time-only set's excess
+// over the signal launch about tripled, and every feature's went from inside the spread to +0.8 %
+// (profiles/gather_starts.txt, section B, "start a frame ahead").
+#ifndef MGX_GATHER_AHEAD_ALL
+#define MGX_GATHER_AHEAD_ALL 0
+#endif
+template <bool AHEAD>
+struct GatherAhead {};
+template <>
+struct GatherAhead<true> {
+  uint64_t f = ~(uint64_t)0, s = 0;
+};
+// the pointer to frame f = b * FPW + j (clamped by the caller) of a gather launch
+template <int FPW, bool AHEAD>
+__device__ __forceinline__ GF gather_frame(uint64_t f, uint64_t b, int j, uint64_t nf, uint64_t wstride, GatherAhead<AHEAD>& ahead) {
+  uint64_t s;
+  if constexpr (AHEAD) {
+    s = f == ahead.f ? ahead.s : gather_start(f);
+    uint64_t g = j + 1 < FPW ? f + 1 : (b + wstride) * FPW;
+    g = g < nf ? g : nf - 1;
+    ahead.f = g;
+    ahead.s = gather_start(g);
+  } else {
+    s = gather_start(f);
+  }
+  return (GF)uniform_ptr(gbl(args_ptr()->frames) + s);
+}
+
 // MEL: the launch writes KernelArgs::out.mel_bands (and may skip the DCT: need_dct). An instance of its own, so
 // that the launches without it run the code they ran before the output existed: with the store behind a
 // run-time test in the one kernel, the all-feature launch at N = 1024 measured +0.6 .. +1.1 % (four more SGPR
 // spills; profiles/mel_bands.txt).
+// GATHER: a gather launch (mgx_extract_gather_*): frame f starts at the sample its table names (KernelArgsGather,
+// the table after the KernelArgs) instead of at f * frame_stride (frame_ptr below; nothing else differs:
+// batches, shares, windows and the pool count frames, not samples). Instances of their own for the same
+// reason: the start's scalar load, its clamp and the registers the next start waits in stay out of every
+// other launch's code, and the table's 16 bytes out of every other launch's arguments.
 template <int N, bool FAITH, bool LITERAL, bool SUB, bool LIGHT, bool NOTIME, bool CHAIN, bool INL = false, bool RES = false,
-          bool MEL = false>
+          bool MEL = false, bool GATHER = false>
 __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(RES ? 1 : Geo<N>::WPE))) void extract_kernel(
-    std::conditional_t<INL, KernelArgsInline<N>, KernelArgs> a) {
+    std::conditional_t<INL, KernelArgsInline<N>, std::conditional_t<GATHER, KernelArgsGather, KernelArgs>> a) {
   using G = Geo<N>;
   using PG = PassGeo<N>;
   using LY = Lds<N>;
@@ -2205,9 +2254,14 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(RES ? 
   // are never stored), so they issue back to back with no branches or waits between them.
   // With G::PREFETCH the next frame of the wave is loaded while this one is processed.
   const bool ntf = args_ptr()->nt_frames != 0;  // (one scalar register for the launch)
+  static_assert(!GATHER || (!INL && !RES), "a gather launch reads its frames from memory");
+  // GATHER: the start of the frame the wave takes next, where a kernel keeps one (gather_frame; empty otherwise)
+  constexpr bool kStartAhead = GATHER && (G::PF == 0 || MGX_GATHER_AHEAD_ALL);
+  [[maybe_unused]] GatherAhead<kStartAhead> ahead;
   auto frame_ptr = [&](uint64_t b, int j) {
     uint64_t f = b * FPW + j;
     f = f < nf ? f : nf - 1;
+    if constexpr (GATHER) return gather_frame<FPW, kStartAhead>(f, b, j, nf, wstride, ahead);
     // (wave-uniform, uniform_ptr: the lane's offset is added at each load)
     // (the frame's start: a 64-bit scalar product with the launch's stride, KernelArgs::frame_stride -- the
     // clamped index keeps the last load inside frame nf - 1, the signal's last whole frame)
@@ -2237,7 +2291,13 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(RES ? 
 #pragma unroll
     for (int c = 0; c < CH; ++c) wreg[c] = w[c * 64 + lane];
   }
-  if constexpr (G::PREFETCH && !INL) {  // (load(xn, b0, 0) with the burst's frame pointer)
+  if constexpr (G::PREFETCH && GATHER) {
+    // (the same with the table's start. Written out, not load(xn, b0, 0): with the lambda called here the
+    // compiler scheduled the N = 1024 instances WITHOUT a table differently, one or two VGPRs more; this form
+    // leaves every one of them the parent's code, instruction for instruction -- profiles/gather_starts.txt)
+    const uint64_t f = b0 * FPW < nf ? b0 * FPW : nf - 1;
+    ld_frame<CHAIN>(xn, (GF)uniform_ptr(gbl(frames_p) + gather_start(f)), (unsigned)lane, ntf);
+  } else if constexpr (G::PREFETCH && !INL) {  // (load(xn, b0, 0) with the burst's frame pointer)
     const uint64_t f = b0 * FPW < nf ? b0 * FPW : nf - 1;
     ld_frame<CHAIN>(xn, (GF)uniform_ptr(gbl(frames_p) + f * fstride), (unsigned)lane, ntf);
   }
@@ -2612,8 +2672,24 @@ __global__ void unpack_kernel(UnpackArgs a) {
 }
 
 template <int N, bool FAITH, bool LITERAL, bool SUB = false, bool LIGHT = false, bool NOTIME = false, bool CHAIN = false>
-hipError_t launch_n(const KernelArgs& a, int grid, hipStream_t stream, const float* inl = nullptr, bool res = false) {
+hipError_t launch_n(const KernelArgs& a, int grid, hipStream_t stream, const float* inl = nullptr, bool res = false,
+                    const GatherTable* gather = nullptr) {
   const size_t lds = Lds<N>::bytes(a.ncoef, a.nfilt);
+  if (gather) {
+    // the GATHER instances (plan.cpp gathers a small host batch densely, so neither the inline frame nor
+    // the resident launch meets a table of starts)
+    if (res || inl) return hipErrorInvalidValue;
+    KernelArgsGather x;
+    x.a = a;
+    x.g = *gather;
+    if (a.out.mel_bands)
+      hipLaunchKernelGGL((extract_kernel<N, FAITH, LITERAL, SUB, LIGHT, NOTIME, CHAIN, false, false, true, true>), dim3(grid),
+                         dim3(kThreads), lds, stream, x);
+    else
+      hipLaunchKernelGGL((extract_kernel<N, FAITH, LITERAL, SUB, LIGHT, NOTIME, CHAIN, false, false, false, true>), dim3(grid),
+                         dim3(kThreads), lds, stream, x);
+    return hipGetLastError();
+  }
   if (a.out.mel_bands) {
     // the MEL instance (a one-frame launch's frame then comes from memory, not from the kernel arguments;
     // the resident launch never writes mel_bands: plan.cpp extract_host_small)
@@ -2678,29 +2754,30 @@ int occupancy_prec(int precision, int mode, int ncoef, int nfilt, bool chain) {
 }
 
 template <int N>
-hipError_t launch_prec(int precision, int mode, const KernelArgs& a, int grid, hipStream_t stream, const float* inl, bool res) {
-  if (mode == MGX_MODE_LITERAL) return launch_n<N, true, true>(a, grid, stream);
-  if (precision == MGX_PRECISION_FAST) return launch_n<N, false, false>(a, grid, stream);
+hipError_t launch_prec(int precision, int mode, const KernelArgs& a, int grid, hipStream_t stream, const float* inl, bool res,
+                       const GatherTable* gt) {
+  if (mode == MGX_MODE_LITERAL) return launch_n<N, true, true>(a, grid, stream, nullptr, false, gt);
+  if (precision == MGX_PRECISION_FAST) return launch_n<N, false, false>(a, grid, stream, nullptr, false, gt);
   const bool every = a.need_mom == 2 && a.need_prefix && a.need_energy && a.need_zcr;
   if constexpr (kChainN<N>) {
     // MGX_FLAG_MFCC_REFERENCE: the mel sums as chains in the reference's order (mel_chains)
     if (a.chain_groups > 0 && a.need_spectrum && a.need_mel) {
-      if (every) return launch_n<N, true, false, false, false, false, true>(a, grid, stream);
-      return launch_n<N, true, false, true, false, false, true>(a, grid, stream);
+      if (every) return launch_n<N, true, false, false, false, false, true>(a, grid, stream, nullptr, false, gt);
+      return launch_n<N, true, false, true, false, false, true>(a, grid, stream, nullptr, false, gt);
     }
   }
   // a spectral feature subset that skips the moment / prefix / time-domain work takes the SUB kernel
   // (LIGHT: a subset reading neither the moments nor the prefix row, e.g. mfcc or the spectra
   // alone, compiled without that code: no runtime branches to keep its registers live)
   if (a.need_spectrum && a.need_mom == 0 && !a.need_prefix)
-    return launch_n<N, true, false, true, true>(a, grid, stream, inl, res);
+    return launch_n<N, true, false, true, true>(a, grid, stream, inl, res, gt);
   // (NOTIME: every spectral sum but no rms / energy / zcr, e.g. C3: the all-feature schedule
   // with the time-domain reductions compiled out)
   if (a.need_spectrum && a.need_mom == 2 && a.need_prefix && !a.need_energy && !a.need_zcr)
-    return launch_n<N, true, false, false, false, true>(a, grid, stream, inl, res);
+    return launch_n<N, true, false, false, false, true>(a, grid, stream, inl, res, gt);
   if (a.need_spectrum && !every)
-    return launch_n<N, true, false, true>(a, grid, stream, inl, res);
-  return launch_n<N, true, false>(a, grid, stream, inl, res);
+    return launch_n<N, true, false, true>(a, grid, stream, inl, res, gt);
+  return launch_n<N, true, false>(a, grid, stream, inl, res, gt);
 }
 
 template <int N>
@@ -2770,16 +2847,16 @@ int extract_blocks_per_cu(int n, int precision, int mode, int ncoef, int nfilt, 
 }
 
 hipError_t launch_extract(int n, int precision, int mode, const KernelArgs& a, int grid,
-                          hipStream_t stream, const float* inline_frame, bool resident) {
-  if (a.num_frames != 1) inline_frame = nullptr;
+                          hipStream_t stream, const float* inline_frame, bool resident, const GatherTable* gather) {
+  if (a.num_frames != 1 || gather) inline_frame = nullptr;
   if (resident && (a.num_frames != 1 || grid != 1 || a.res_mail == nullptr || a.res_exit == nullptr ||
                    a.done_flag == nullptr))
     return hipErrorInvalidValue;
   switch (n) {
-    case 256: return launch_prec<256>(precision, mode, a, grid, stream, inline_frame, resident);
-    case 512: return launch_prec<512>(precision, mode, a, grid, stream, inline_frame, resident);
-    case 1024: return launch_prec<1024>(precision, mode, a, grid, stream, inline_frame, resident);
-    case 2048: return launch_prec<2048>(precision, mode, a, grid, stream, nullptr, resident);
+    case 256: return launch_prec<256>(precision, mode, a, grid, stream, inline_frame, resident, gather);
+    case 512: return launch_prec<512>(precision, mode, a, grid, stream, inline_frame, resident, gather);
+    case 1024: return launch_prec<1024>(precision, mode, a, grid, stream, inline_frame, resident, gather);
+    case 2048: return launch_prec<2048>(precision, mode, a, grid, stream, nullptr, resident, gather);
     default: return hipErrorInvalidValue;
   }
 }

@@ -154,6 +154,23 @@ constexpr size_t kInlineFrameOff = (sizeof(KernelArgs) + 15) / 16 * 16;
 static_assert(offsetof(KernelArgsInline<256>, frame) == kInlineFrameOff && offsetof(KernelArgsInline<2048>, frame) == kInlineFrameOff,
               "inline frame offset");
 
+// A gather launch (mgx_extract_gather_*; the GATHER kernels) carries its table after the KernelArgs, where a
+// one-frame launch carries its frame: frame f starts at sample min(starts[f], last_start) of a.frames instead
+// of at f * a.frame_stride. starts: num_frames entries in device memory, read with scalar loads and never
+// written; last_start: num_samples - N, the last start whose frame lies inside the samples, so a start the
+// host never saw cannot take a load outside them. The 16 bytes are arguments of those kernels alone:
+// KernelArgs keeps its size and layout (504 bytes, the eight 64-byte lines the kernel's prologue touches, the
+// inline frame at 512), so every other kernel reads the arguments it read before.
+struct GatherTable {
+  const uint64_t* starts;
+  uint64_t last_start;
+};
+struct KernelArgsGather {
+  KernelArgs a;
+  alignas(16) GatherTable g;
+};
+static_assert(offsetof(KernelArgsGather, g) == kInlineFrameOff, "the table at the inline frame's offset");
+
 // Last-error reporting (plan.cpp): set mgx_last_error() and return `code`.
 int fail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
 int hip_fail(hipError_t e, const char* what);
@@ -165,8 +182,10 @@ int hip_fail(hipError_t e, const char* what);
 // resident (MGX_FLAG_RESIDENT, one frame, grid 1, a.res_* set): the launch stays on the
 // device serving requests from a.res_mail until the stop word or the idle timeout (kernels.hip res_wait);
 // the literal, fast and reference-order plans have no resident form (an error).
+// gather: the launch's table of starts (the GATHER kernels; neither an inline frame nor the resident launch).
 hipError_t launch_extract(int n, int precision, int mode, const KernelArgs& a, int grid,
-                          hipStream_t stream, const float* inline_frame = nullptr, bool resident = false);
+                          hipStream_t stream, const float* inline_frame = nullptr, bool resident = false,
+                          const GatherTable* gather = nullptr);
 hipError_t launch_synth(float* out, uint64_t count, uint64_t seed, uint64_t first_index,
                         hipStream_t stream);
 hipError_t launch_pcm_decode(const void* pcm, uint64_t count, uint32_t format, uint32_t channels,

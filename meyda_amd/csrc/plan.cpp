@@ -482,6 +482,7 @@ struct mgx_plan {
   size_t s_out_bytes = 0;
   uint64_t s_chunk = 0;
   unsigned char* s_pcm[2] = {nullptr, nullptr};  // raw PCM slots for mgx_extract_host_pcm
+  uint64_t* s_starts[2] = {nullptr, nullptr};    // a chunk's starts for mgx_extract_gather_host (kHostChunk entries each)
   uint64_t s_pcm_bytes = 0;
   hipStream_t s_copy = nullptr, s_comp = nullptr;
   hipEvent_t ev_loaded[2] = {nullptr, nullptr}, ev_done[2] = {nullptr, nullptr}, ev_back[2] = {nullptr, nullptr};
@@ -521,8 +522,15 @@ namespace {
 struct ResidentLaunch {
   uint32_t seq;
 };
+// gather: the launch's frames start where a table says (mgx_extract_gather_*): starts, nframes entries in device
+// memory, into the num_samples samples at `frames`
+struct GatherLaunch {
+  const uint64_t* starts;
+  uint64_t num_samples;
+};
 int extract_device_impl(mgx_plan* p, const float* frames, uint64_t nframes, uint64_t stride, const mgx::Outputs* o, void* stream,
-                        const uint32_t* done, const float* inline_frame = nullptr, const ResidentLaunch* res = nullptr);
+                        const uint32_t* done, const float* inline_frame = nullptr, const ResidentLaunch* res = nullptr,
+                        const GatherLaunch* gather = nullptr);
 void resident_stop(mgx_plan* p);
 
 // The caller's two output structs as the one the plan code passes around. aux: NULL (no output beyond
@@ -803,6 +811,7 @@ int mgx_plan_destroy(mgx_plan* p) {
     if (p->s_frames[i]) (void)hipFree(p->s_frames[i]);
     if (p->s_out[i]) (void)hipFree(p->s_out[i]);
     if (p->s_pcm[i]) (void)hipFree(p->s_pcm[i]);
+    if (p->s_starts[i]) (void)hipFree(p->s_starts[i]);
     for (hipEvent_t ev : {p->ev_loaded[i], p->ev_done[i], p->ev_back[i]})
       if (ev) (void)hipEventDestroy(ev);
   }
@@ -855,6 +864,51 @@ int mgx_extract_device_ex(mgx_plan* p, const float* samples, uint64_t num_sample
   return extract_device_impl(p, samples, nframes, hop, &x, stream, nullptr);
 }
 
+// A corpus as one array: the buffers of every signal, none across a signal's end
+int mgx_signals_frame_starts(const uint64_t* offsets, uint64_t num_signals, uint32_t buffer_size, uint32_t hop,
+                             uint64_t* frame_offsets, uint64_t* starts, uint64_t capacity, uint64_t* num_frames) {
+  if (!num_frames) return fail(MGX_E_INVALID_ARGUMENT, "num_frames is NULL");
+  if (buffer_size == 0) return fail(MGX_E_INVALID_ARGUMENT, "buffer_size is 0");
+  if (hop == 0) return fail(MGX_E_INVALID_ARGUMENT, "hop is 0 (a hop of at least one sample)");
+  if (!offsets) return fail(MGX_E_INVALID_ARGUMENT, "offsets is NULL");
+  uint64_t total = 0;
+  for (uint64_t s = 0; s < num_signals; ++s) {
+    if (offsets[s + 1] < offsets[s])
+      return fail(MGX_E_INVALID_ARGUMENT, "offsets[%llu] = %llu is below offsets[%llu] = %llu", (unsigned long long)(s + 1),
+                  (unsigned long long)offsets[s + 1], (unsigned long long)s, (unsigned long long)offsets[s]);
+    const uint64_t len = offsets[s + 1] - offsets[s];
+    total += len < buffer_size ? 0 : (len - buffer_size) / hop + 1;
+  }
+  if (starts && capacity < total)
+    return fail(MGX_E_INVALID_ARGUMENT, "starts holds %llu entries, %llu buffers", (unsigned long long)capacity, (unsigned long long)total);
+  // (nothing is written before every check has passed)
+  uint64_t at = 0;
+  for (uint64_t s = 0; s < num_signals; ++s) {
+    if (frame_offsets) frame_offsets[s] = at;
+    const uint64_t len = offsets[s + 1] - offsets[s];
+    const uint64_t k = len < buffer_size ? 0 : (len - buffer_size) / hop + 1;
+    for (uint64_t i = 0; starts && i < k; ++i) starts[at + i] = offsets[s] + i * hop;
+    at += k;
+  }
+  if (frame_offsets) frame_offsets[num_signals] = at;
+  *num_frames = total;
+  return MGX_OK;
+}
+
+int mgx_extract_gather_device(mgx_plan* p, const float* samples, uint64_t num_samples, const uint64_t* starts, uint64_t nframes,
+                              const mgx_outputs* o, const mgx_aux_outputs* aux, void* stream) {
+  if (!p || !o) return fail(MGX_E_INVALID_ARGUMENT, "NULL plan or outputs");
+  mgx::Outputs x;
+  const int rc = make_outputs(o, aux, &x);
+  if (rc) return rc;
+  if (nframes == 0) return MGX_OK;
+  if (!starts) return fail(MGX_E_INVALID_ARGUMENT, "starts is NULL");
+  if (num_samples < (uint64_t)p->n)
+    return fail(MGX_E_INVALID_ARGUMENT, "%llu samples hold no buffer of %d", (unsigned long long)num_samples, p->n);
+  const GatherLaunch g{starts, num_samples};
+  return extract_device_impl(p, samples, nframes, (uint64_t)p->n, &x, stream, nullptr, nullptr, nullptr, &g);
+}
+
 }  // extern "C"
 
 namespace {
@@ -897,7 +951,7 @@ int add_stream_scratch(mgx_plan* p, void* stream) {
 // (mgx::launch_extract); res: the plan's resident launch (resident_request). Any other launch ends the
 // plan's resident one first, so the plan's own work never waits behind it or shares the device with it.
 int extract_device_impl(mgx_plan* p, const float* frames, uint64_t nframes, uint64_t stride, const mgx::Outputs* o, void* stream,
-                        const uint32_t* done, const float* inline_frame, const ResidentLaunch* res) {
+                        const uint32_t* done, const float* inline_frame, const ResidentLaunch* res, const GatherLaunch* gather) {
   if (!p || !o) return fail(MGX_E_INVALID_ARGUMENT, "NULL plan or outputs");
   if (nframes == 0) return MGX_OK;
   if (!frames) return fail(MGX_E_INVALID_ARGUMENT, "frames is NULL");
@@ -963,6 +1017,14 @@ int extract_device_impl(mgx_plan* p, const float* frames, uint64_t nframes, uint
   // non-temporally only when MGX_NT_MIN_MB is set (the tests and tools/signal_bench.py force either kind).
   const bool overlap = stride < (uint64_t)p->n;
   a.nt_frames = (!overlap || p->nt_forced) && ((nframes - 1) * stride + (uint64_t)p->n) * sizeof(float) > p->nt_min_bytes;
+  if (gather) {
+    // A gather launch (stride is not read): the table is the kernel's to see, not the host's, so whether its
+    // frames overlap is judged by count -- more samples read than there are (nframes N > num_samples) means
+    // lines read more than once, which plain loads keep, as for a signal's overlapping frames; otherwise the
+    // dense rule on the samples' bytes. MGX_NT_MIN_MB decides for both, as above.
+    const bool reread = nframes * (uint64_t)p->n > gather->num_samples;
+    a.nt_frames = (!reread || p->nt_forced) && gather->num_samples * sizeof(float) > p->nt_min_bytes;
+  }
   hipError_t e = hipSetDevice(p->d.device);
   if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
   if (res) {
@@ -1017,7 +1079,10 @@ int extract_device_impl(mgx_plan* p, const float* frames, uint64_t nframes, uint
     a.done_seq = p->done_seq;
     a.done_waves = (uint32_t)grid * 4;
   }
-  e = mgx::launch_extract(p->n, (int)p->d.precision, (int)p->d.mode, a, grid, (hipStream_t)stream, inline_frame);
+  // (a gather launch: its table beside the arguments, the last start whose frame lies inside the samples)
+  const mgx::GatherTable gt{gather ? gather->starts : nullptr, gather ? gather->num_samples - (uint64_t)p->n : 0};
+  e = mgx::launch_extract(p->n, (int)p->d.precision, (int)p->d.mode, a, grid, (hipStream_t)stream, inline_frame, false,
+                          gather ? &gt : nullptr);
   if (e != hipSuccess) return hip_fail(e, "extract kernel launch");
   if (ring_done) {
     e = hipEventRecord(ring_done, (hipStream_t)stream);
@@ -1406,10 +1471,19 @@ uint64_t signal_chunk_frames(const mgx_plan* p, uint64_t hop) {
   return hop <= n ? kHostChunk : std::max<uint64_t>(1, (kHostChunk * n - n) / hop + 1);
 }
 
+// The chunks of a gather call (mgx_extract_gather_host): chunk i is frames [bounds[i], bounds[i + 1]), whose
+// samples are the span [lo[i], lo[i] + span[i]) of the caller's array; `fill` copies that span into the slot and
+// the chunk's starts, less lo[i], into p->s_starts[slot].
+struct GatherChunks {
+  std::vector<uint64_t> bounds, lo, span;
+};
+
 // stride: the samples between the starts of consecutive frames in a slot (N: dense frames; a signal's
 // hop: `fill` then writes a chunk's (cnt - 1) stride + N samples); chunk_max: frames per chunk.
+// gc: the chunks are gc's instead (chunk_max: the longest of them), each launched over its slot's table of starts.
 template <typename Fill>
-int extract_host_chunked(mgx_plan* p, uint64_t nframes, uint64_t stride, uint64_t chunk_max, const mgx::Outputs* o, Fill fill) {
+int extract_host_chunked(mgx_plan* p, uint64_t nframes, uint64_t stride, uint64_t chunk_max, const mgx::Outputs* o, Fill fill,
+                         const GatherChunks* gc = nullptr) {
   const int n = p->n, L = p->L;
   const size_t ss = p->d.scalar_f64 ? 8 : 4;
   const size_t nb = mgx::kBark, nc = p->d.num_mfcc_coeffs, nm = p->d.num_mel_bands;
@@ -1417,22 +1491,26 @@ int extract_host_chunked(mgx_plan* p, uint64_t nframes, uint64_t stride, uint64_
   const size_t per = out_bytes_per_frame(p, o);
   const uint64_t chunk = std::min<uint64_t>(nframes, chunk_max);
   // (the slot in whole frames of N floats: the chunk's span, at most kHostChunk frames' worth)
-  const uint64_t slot_frames = ((chunk - 1) * stride + (uint64_t)n + (uint64_t)n - 1) / (uint64_t)n;
+  uint64_t slot_frames = ((chunk - 1) * stride + (uint64_t)n + (uint64_t)n - 1) / (uint64_t)n;
+  if (gc) slot_frames = (*std::max_element(gc->span.begin(), gc->span.end()) + (uint64_t)n - 1) / (uint64_t)n;
   int rc = ensure_host_staging(p, slot_frames, per * chunk + 21 * 256);
   if (rc) return rc;
-  const uint64_t nch = (nframes + chunk - 1) / chunk;
+  const uint64_t nch = gc ? gc->lo.size() : (nframes + chunk - 1) / chunk;
+  // chunk i's first frame and count
+  auto first = [&](uint64_t i) { return gc ? gc->bounds[i] : i * chunk; };
+  auto count = [&](uint64_t i) { return gc ? gc->bounds[i + 1] - gc->bounds[i] : std::min<uint64_t>(chunk, nframes - i * chunk); };
   hipError_t e = hipSuccess;
   auto fail_sync = [&](int code) {  // leave no work in flight on the plan's buffers
     (void)hipStreamSynchronize(p->s_comp);
     (void)hipStreamSynchronize(p->s_copy);
     return code;
   };
-  rc = fill(0, std::min<uint64_t>(chunk, nframes), 0, p->s_copy);
+  rc = fill(0, count(0), 0, p->s_copy);
   if (rc) return fail_sync(rc);
   e = hipEventRecord(p->ev_loaded[0], p->s_copy);
   for (uint64_t i = 0; i < nch && e == hipSuccess; ++i) {
     const int sl = (int)(i & 1);
-    const uint64_t f0 = i * chunk, cnt = std::min<uint64_t>(chunk, nframes - f0);
+    const uint64_t f0 = first(i), cnt = count(i);
     mgx::Outputs d{};
     size_t off = 0;
     auto take = [&](size_t bytes) { unsigned char* q = p->s_out[sl] + off; off += (bytes + 255) / 256 * 256; return q; };
@@ -1448,15 +1526,15 @@ int extract_host_chunked(mgx_plan* p, uint64_t nframes, uint64_t stride, uint64_
     e = hipStreamWaitEvent(p->s_comp, p->ev_loaded[sl], 0);
     if (e == hipSuccess && i >= 2) e = hipStreamWaitEvent(p->s_comp, p->ev_back[sl], 0);
     if (e != hipSuccess) break;
-    rc = extract_device_impl(p, p->s_frames[sl], cnt, stride, &d, p->s_comp, nullptr);
+    const GatherLaunch g{p->s_starts[sl], gc ? gc->span[i] : 0};
+    rc = extract_device_impl(p, p->s_frames[sl], cnt, stride, &d, p->s_comp, nullptr, nullptr, nullptr, gc ? &g : nullptr);
     if (rc) return fail_sync(rc);
     e = hipEventRecord(p->ev_done[sl], p->s_comp);
     // chunk i+1's frames into the other slot once chunk i-1's extraction has read them
     if (e == hipSuccess && i + 1 < nch) {
-      const uint64_t g0 = (i + 1) * chunk, gc = std::min<uint64_t>(chunk, nframes - g0);
       if (i >= 1) e = hipStreamWaitEvent(p->s_copy, p->ev_done[sl ^ 1], 0);
       if (e != hipSuccess) break;
-      rc = fill(g0, gc, sl ^ 1, p->s_copy);
+      rc = fill(first(i + 1), count(i + 1), sl ^ 1, p->s_copy);
       if (rc) return fail_sync(rc);
       e = hipEventRecord(p->ev_loaded[sl ^ 1], p->s_copy);
     }
@@ -1542,6 +1620,76 @@ int mgx_extract_host_ex(mgx_plan* p, const float* samples, uint64_t num_samples,
                                   hipMemcpyHostToDevice, st);
     return e == hipSuccess ? MGX_OK : hip_fail(e, "hipMemcpyAsync(samples)");
   });
+}
+
+int mgx_extract_gather_host(mgx_plan* p, const float* samples, uint64_t num_samples, const uint64_t* starts, uint64_t nframes,
+                            const mgx_outputs* outputs, const mgx_aux_outputs* aux) {
+  if (!p || !outputs) return fail(MGX_E_INVALID_ARGUMENT, "NULL plan or outputs");
+  mgx::Outputs x;
+  int rc = make_outputs(outputs, aux, &x);
+  if (rc) return rc;
+  const mgx::Outputs* const o = &x;
+  if (nframes == 0) return MGX_OK;
+  if (!starts) return fail(MGX_E_INVALID_ARGUMENT, "starts is NULL");
+  if (!samples) return fail(MGX_E_INVALID_ARGUMENT, "samples is NULL");
+  const uint64_t n = (uint64_t)p->n;
+  if (num_samples < n) return fail(MGX_E_INVALID_ARGUMENT, "%llu samples hold no buffer of %d", (unsigned long long)num_samples, p->n);
+  if ((o->complex_real == nullptr) != (o->complex_imag == nullptr))
+    return fail(MGX_E_INVALID_ARGUMENT, "complex_real and complex_imag must be given together");
+  // (the host sees the table: a start whose buffer leaves the samples is refused here, before any copy)
+  for (uint64_t f = 0; f < nframes; ++f)
+    if (starts[f] > num_samples - n)
+      return fail(MGX_E_INVALID_ARGUMENT, "starts[%llu] = %llu: a buffer of %d leaves the %llu samples", (unsigned long long)f,
+                  (unsigned long long)starts[f], p->n, (unsigned long long)num_samples);
+  // a batch of the one-launch path gathers its buffers densely into the pinned input buffer, as a signal
+  // at hop > N does: one buffer then takes the inline-frame launch or the resident workgroup
+  if (nframes <= p->small_max)
+    return extract_host_small(p, nframes, n, o, [&](float* dst) {
+      for (uint64_t f = 0; f < nframes; ++f) memcpy(dst + f * n, samples + starts[f], (size_t)n * sizeof(float));
+      return MGX_OK;
+    });
+  // Chunks: the longest runs of consecutive buffers of at most kHostChunk whose span, max start + N - min start,
+  // fits a slot of the dense path (kHostChunk N floats; one buffer always does). Sorted starts no further apart
+  // than N fill their chunks; any other order is served, in as many chunks as its jumps make.
+  GatherChunks gc;
+  std::vector<uint64_t> rel(nframes);  // every start less its chunk's lowest: what the chunk's launch reads
+  const uint64_t slot = kHostChunk * n;
+  uint64_t longest = 0;
+  for (uint64_t f0 = 0; f0 < nframes;) {
+    uint64_t lo = starts[f0], hi = starts[f0], f1 = f0 + 1;
+    for (; f1 < nframes && f1 - f0 < kHostChunk; ++f1) {
+      const uint64_t l = std::min(lo, starts[f1]), h = std::max(hi, starts[f1]);
+      if (h - l + n > slot) break;
+      lo = l;
+      hi = h;
+    }
+    for (uint64_t f = f0; f < f1; ++f) rel[f] = starts[f] - lo;
+    gc.bounds.push_back(f0);
+    gc.lo.push_back(lo);
+    gc.span.push_back(hi - lo + n);
+    longest = std::max(longest, f1 - f0);
+    f0 = f1;
+  }
+  gc.bounds.push_back(nframes);
+  if (!p->s_starts[0]) {
+    hipError_t e = hipSetDevice(p->d.device);
+    for (int i = 0; i < 2 && e == hipSuccess; ++i) {
+      e = hipMalloc(reinterpret_cast<void**>(&p->s_starts[i]), kHostChunk * sizeof(uint64_t));
+      if (e != hipSuccess) p->s_starts[i] = nullptr;
+    }
+    if (e != hipSuccess) {
+      if (p->s_starts[0]) (void)hipFree(p->s_starts[0]);
+      p->s_starts[0] = nullptr;
+      return hip_fail(e, "hipMalloc(staging starts)");
+    }
+  }
+  uint64_t ci = 0;  // (fill is called for the chunks in order, once each)
+  return extract_host_chunked(p, nframes, n, longest, o, [&](uint64_t f0, uint64_t cnt, int sl, hipStream_t st) {
+    const uint64_t i = ci++;
+    hipError_t e = hipMemcpyAsync(p->s_frames[sl], samples + gc.lo[i], gc.span[i] * sizeof(float), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(p->s_starts[sl], rel.data() + f0, cnt * sizeof(uint64_t), hipMemcpyHostToDevice, st);
+    return e == hipSuccess ? MGX_OK : hip_fail(e, "hipMemcpyAsync(samples, starts)");
+  }, &gc);
 }
 
 int mgx_wav_parse(const void* bytes, uint64_t len, mgx_wav_info* info) {

@@ -21,6 +21,15 @@
 //                                   in place on the device, a trailing partial buffer dropped
 //   Meyda.signalFrames(numSamples, bufferSize, hopSize)
 //                                   how many buffers that is: (numSamples - bufferSize) / hopSize + 1
+//   getBatchGather(features, samples, starts) / getBatchGatherAsync(...)
+//                                   buffer f is samples [starts[f], starts[f] + bufferSize): any order,
+//                                   repeats and overlaps allowed, one launch for all of them
+//   getBatchSignals(features, signals, hopSize) / getBatchSignalsAsync(...)
+//                                   signals: an array of Float32Arrays (a corpus); every signal's buffers
+//                                   in one launch, none across two signals; getBatch's result plus
+//                                   frameOffsets (signal s: rows frameOffsets[s] .. frameOffsets[s + 1])
+//   Meyda.signalsFrameStarts(lengths, bufferSize, hopSize)
+//                                   {starts, frameOffsets} of signals stored one after another
 //   Meyda.readWav(wavBytes)         the header: {pcmFormat, channels, sampleRate, sampleFrames, ...}
 //   'melBands'                      a feature name beyond the snapshot's 18 (later Meyda's melBands): the
 //                                   log mel band energies the MFCC is the DCT of (mfcc.js:53-65), a
@@ -395,6 +404,66 @@ class Meyda {
     return this._runAsync((plan) => addon.extractSignalAsync(plan, x, hop, names));
   }
 
+  // Buffers at given sample offsets: buffer f is samples [starts[f], starts[f] + bufferSize) of one
+  // Float32Array. starts: an array or typed array of non-negative safe integers, in any order (they may
+  // repeat and overlap); one whose buffer leaves the samples is refused. Results as getBatch's.
+  getBatchGather(features, samples, starts) {
+    const names = this._checkNames(checkBatchNames(features));
+    const st = this._checkStarts(starts);
+    return addon.extractGather(this._plan(), toF32(samples), st, names);
+  }
+
+  getBatchGatherAsync(features, samples, starts) {
+    const names = this._checkNames(checkBatchNames(features));
+    const st = this._checkStarts(starts);
+    const x = toF32(samples);
+    return this._runAsync((plan) => addon.extractGatherAsync(plan, x, st, names));
+  }
+
+  // Many signals in one call: signals is an array of Float32Arrays, each cut every hopSize samples as
+  // getBatchSignal cuts one, no buffer across two signals. getBatch's result object over all the buffers
+  // in signal order, with frameOffsets added: signal s's buffers are rows
+  // [frameOffsets[s], frameOffsets[s + 1]) of every output.
+  getBatchSignals(features, signals, hopSize) {
+    const names = this._checkNames(checkBatchNames(features));
+    const c = this._concatSignals(signals, hopSize);
+    const r = addon.extractGather(this._plan(), c.samples, c.starts, names);
+    r.frameOffsets = c.frameOffsets;
+    return r;
+  }
+
+  getBatchSignalsAsync(features, signals, hopSize) {
+    const names = this._checkNames(checkBatchNames(features));
+    const c = this._concatSignals(signals, hopSize);
+    return this._runAsync((plan) => addon.extractGatherAsync(plan, c.samples, c.starts, names)).then((r) => {
+      r.frameOffsets = c.frameOffsets;
+      return r;
+    });
+  }
+
+  _concatSignals(signals, hopSize) {
+    const hop = this._checkHop(hopSize);
+    if (!Array.isArray(signals)) throw new TypeError('signals must be an array of Float32Arrays');
+    const xs = signals.map(toF32);
+    const t = Meyda.signalsFrameStarts(xs.map((x) => x.length), this.bufferSize, hop);
+    const samples = new Float32Array(xs.reduce((a, x) => a + x.length, 0));
+    let at = 0;
+    for (const x of xs) {
+      samples.set(x, at);
+      at += x.length;
+    }
+    return { samples, starts: t.starts, frameOffsets: t.frameOffsets };
+  }
+
+  // starts as the addon takes them (a Float64Array), checked before it is called; the device groups of
+  // options.devices take dense buffers only (include/meyda_gpu.h).
+  _checkStarts(starts) {
+    if (Array.isArray(this.options.devices)) {
+      throw new Error('starts are not supported with options.devices: device groups take dense buffers only');
+    }
+    return safeIntegers(starts, 'starts');
+  }
+
   // hopSize: a positive integer (that fits the C ABI's uint32), checked before the addon is called; the
   // device groups of options.devices take dense buffers only (include/meyda_gpu.h).
   _checkHop(hopSize) {
@@ -421,6 +490,19 @@ class Meyda {
       throw new RangeError('hopSize must be a positive integer, got ' + String(hopSize));
     }
     return addon.signalFrames(numSamples, bufferSize, hopSize);
+  }
+
+  // The buffers of signals of the given lengths stored one after another: {starts, frameOffsets}, Float64Arrays
+  // -- the start of every buffer in signal order (getBatchGather's starts), and the lengths.length + 1 prefix
+  // sums of the signals' buffer counts. Host only.
+  static signalsFrameStarts(lengths, bufferSize, hopSize) {
+    if (typeof hopSize !== 'number' || !Number.isInteger(hopSize) || hopSize < 1 || hopSize > 4294967295) {
+      throw new RangeError('hopSize must be a positive integer, got ' + String(hopSize));
+    }
+    if (typeof bufferSize !== 'number' || !Number.isInteger(bufferSize) || bufferSize < 1 || bufferSize > 4294967295) {
+      throw new RangeError('bufferSize must be a positive integer, got ' + String(bufferSize));
+    }
+    return addon.signalsFrameStarts(safeIntegers(lengths, 'lengths'), bufferSize, hopSize);
   }
 
   static readWav(wavBytes) {
@@ -531,6 +613,23 @@ function frameBuilder(names, single) {
 
 function toF32(frames) {
   return frames instanceof Float32Array ? frames : Float32Array.from(frames);
+}
+
+// Sample indices or lengths as the addon takes them, a Float64Array: every entry a non-negative safe integer
+// (anything else -- a fraction, a negative, NaN, a non-number -- is a RangeError naming the entry).
+function safeIntegers(values, what) {
+  if (!Array.isArray(values) && !ArrayBuffer.isView(values)) {
+    throw new TypeError(what + ' must be an array or a typed array of integers');
+  }
+  const out = new Float64Array(values.length);
+  for (let i = 0; i < values.length; ++i) {
+    const v = typeof values[i] === 'bigint' ? Number(values[i]) : values[i];
+    if (typeof v !== 'number' || !Number.isSafeInteger(v) || v < 0) {
+      throw new RangeError(what + '[' + i + '] must be a non-negative safe integer, got ' + String(values[i]));
+    }
+    out[i] = v;
+  }
+  return out;
 }
 
 function checkBatchNames(features) {

@@ -181,6 +181,44 @@ static void arithmetic() {
   CHECK(mgx_is_power_of_two(0.0) == 0 && mgx_is_power_of_two(1.0) == 1 && mgx_is_power_of_two(-8.0) == 0);
 }
 
+// mgx_signals_frame_starts: exactly-sized offsets, frame_offsets and starts arrays (a write past the total,
+// or a read past offsets[num_signals], is the sanitizer's to see), every start inside its own signal.
+static void frame_starts() {
+  long n = 0;
+  for (uint32_t N : {1u, 256u, 1024u})
+    for (uint32_t hop : {1u, N / 4 + 1, N, N + 3})
+      for (size_t ns : {(size_t)0, (size_t)1, (size_t)7}) {
+        const uint64_t lens[7] = {0, N - 1, N, (uint64_t)N + hop - 1, (uint64_t)N + hop, (uint64_t)N + 5 * hop, 3ull * N + 1};
+        std::vector<uint64_t> off(ns + 1, 5);
+        for (size_t s = 0; s < ns; ++s) off[s + 1] = off[s] + lens[s];
+        uint64_t total = ~0ull, again = 0, want = 0;
+        for (size_t s = 0; s < ns; ++s) {
+          uint64_t f = 0;
+          CHECK(mgx_signal_frames(lens[s], N, hop, &f) == MGX_OK);
+          want += f;
+        }
+        CHECK(mgx_signals_frame_starts(off.data(), ns, N, hop, nullptr, nullptr, 0, &total) == MGX_OK && total == want);
+        std::vector<uint64_t> fo(ns + 1), st((size_t)total);
+        CHECK(mgx_signals_frame_starts(off.data(), ns, N, hop, fo.data(), st.data(), total, &again) == MGX_OK && again == total);
+        CHECK(fo[0] == 0 && fo[ns] == total);
+        for (size_t s = 0; s < ns; ++s)
+          for (uint64_t f = fo[s]; f < fo[s + 1]; ++f)
+            CHECK(st[(size_t)f] == off[s] + (f - fo[s]) * hop && st[(size_t)f] + N <= off[s + 1]);
+        if (total > 0) CHECK(mgx_signals_frame_starts(off.data(), ns, N, hop, fo.data(), st.data(), total - 1, &again) == MGX_E_INVALID_ARGUMENT);
+        ++n;
+      }
+  const uint64_t down[3] = {0, 10, 9};
+  uint64_t total = 0;
+  CHECK(mgx_signals_frame_starts(down, 2, 4, 1, nullptr, nullptr, 0, &total) == MGX_E_INVALID_ARGUMENT);
+  CHECK(mgx_signals_frame_starts(down, 1, 4, 0, nullptr, nullptr, 0, &total) == MGX_E_INVALID_ARGUMENT);
+  CHECK(mgx_signals_frame_starts(down, 1, 4, 1, nullptr, nullptr, 0, nullptr) == MGX_E_INVALID_ARGUMENT);
+  CHECK(mgx_signals_frame_starts(nullptr, 1, 4, 1, nullptr, nullptr, 0, &total) == MGX_E_INVALID_ARGUMENT);
+  const uint64_t one = 0;
+  CHECK(mgx_extract_gather_host(nullptr, nullptr, 0, &one, 1, nullptr, nullptr) == MGX_E_INVALID_ARGUMENT);
+  CHECK(mgx_extract_gather_device(nullptr, nullptr, 0, &one, 1, nullptr, nullptr, nullptr) == MGX_E_INVALID_ARGUMENT);
+  printf("frame starts: %ld tables\n", n);
+}
+
 static void validation() {
   mgx_plan* p = nullptr;
   CHECK(mgx_plan_create(nullptr, &p) == MGX_E_INVALID_ARGUMENT);
@@ -205,6 +243,7 @@ int main() {
   wav_fuzz();
   host_tables();
   arithmetic();
+  frame_starts();
   validation();
   printf("host_checks: %s (%d failures)\n", failures ? "FAILED" : "ok", failures);
   return failures ? 1 : 0;
