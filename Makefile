@@ -7,7 +7,7 @@ HIPFLAGS = --offload-arch=$(ARCH) -O3 -fPIC -std=c++17 -ffp-contract=off -Wall -
            -mllvm -disable-machine-licm
 LIB = meyda_amd/libmeyda_gpu.so
 SRC = meyda_amd/csrc/kernels.hip meyda_amd/csrc/plan.cpp meyda_amd/csrc/group.cpp
-HDR = include/meyda_gpu.h meyda_amd/csrc/mgx_internal.h
+HDR = include/meyda_gpu.h meyda_amd/csrc/mgx_internal.h meyda_amd/csrc/out_fields.h
 
 all: $(LIB) oracle
 
@@ -24,7 +24,7 @@ $(ASAN_DIR)/libmeyda_gpu.so: $(SRC) $(HDR)
 	mkdir -p $(ASAN_DIR)
 	$(HIPCC) $(HIPFLAGS) $(foreach f,$(SAN),-Xarch_host $(f)) -shared -o $@ -x hip $(SRC) -ldl
 
-$(ASAN_DIR)/host_checks: tools/asan/host_checks.cpp $(ASAN_DIR)/libmeyda_gpu.so include/meyda_gpu.h
+$(ASAN_DIR)/host_checks: tools/asan/host_checks.cpp $(ASAN_DIR)/libmeyda_gpu.so $(HDR)
 	$(CLANG)++ -O1 -g -std=c++17 $(SAN) -o $@ $< -L$(ASAN_DIR) -l:libmeyda_gpu.so -Wl,-rpath,'$$ORIGIN'
 
 $(ASAN_DIR)/addon/meyda_napi.node: meyda_amd/addon/meyda_napi.c $(ASAN_DIR)/libmeyda_gpu.so include/meyda_gpu.h

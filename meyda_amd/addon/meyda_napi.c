@@ -234,6 +234,22 @@ static napi_value destroy_plan(napi_env env, napi_callback_info info) {
 /* ------------------------------------------------------------ extraction job */
 enum { SLOT_SCALAR0 = 0, SLOT_LOUD = MGX_NUM_SCALARS, SLOT_MFCC, SLOT_AMP, SLOT_POW, SLOT_CRE, SLOT_CIM, SLOT_MEL, NSLOTS };
 
+/* The output fields, slot = field number: this file's copy of the library's table (meyda_amd/csrc/out_fields.h
+ * out_field_bytes / out_field), kept because the addon is C against the public header alone. An output added
+ * there is added here. Bytes per frame of field i: */
+static size_t field_bytes(const mgx_plan_desc* d, int i) {
+  const size_t n = d->buffer_size;
+  const size_t floats[NSLOTS - SLOT_LOUD] = {d->num_bark_bands, d->num_mfcc_coeffs, n / 2, n / 2, n, n, d->num_mel_bands};
+  return i < MGX_NUM_SCALARS ? (d->scalar_f64 ? 8u : 4u) : 4 * floats[i - SLOT_LOUD];
+}
+/* ... and its pointer in the caller's two structs */
+static void set_field(mgx_outputs* o, mgx_aux_outputs* aux, int i, void* p) {
+  float** const arrays[NSLOTS - SLOT_LOUD] = {&o->loudness_specific, &o->mfcc,         &o->amplitude_spectrum, &o->power_spectrum,
+                                              &o->complex_real,      &o->complex_imag, &aux->mel_bands};
+  if (i < MGX_NUM_SCALARS) o->scalars[i] = p;
+  else *arrays[i - SLOT_LOUD] = (float*)p;
+}
+
 typedef struct {
   plan_box* box;
   const float* frames;
@@ -459,19 +475,11 @@ static int job_prepare_gather(napi_env env, job* j, napi_value samples_v, napi_v
 
 /* Wanted outputs for j->nframes frames. */
 static int job_alloc(napi_env env, job* j, napi_value feats) {
-  const uint32_t n = j->box->desc.buffer_size;
   if (!parse_features(env, feats, j)) return 0;
-  const size_t F = j->nframes, L = n / 2;
-  const size_t ss = j->box->desc.scalar_f64 ? 8 : 4;
+  j->aux.struct_size = sizeof j->aux;
   for (int i = 0; i < NSLOTS; ++i) {
     if (!j->want[i]) continue;
-    size_t b = 0;
-    if (i < MGX_NUM_SCALARS) b = F * ss;
-    else if (i == SLOT_LOUD) b = F * 24 * 4;
-    else if (i == SLOT_MFCC) b = F * j->box->desc.num_mfcc_coeffs * 4;
-    else if (i == SLOT_MEL) b = F * j->box->desc.num_mel_bands * 4;
-    else if (i == SLOT_AMP || i == SLOT_POW) b = F * L * 4;
-    else b = F * n * 4;
+    const size_t b = (size_t)j->nframes * field_bytes(&j->box->desc, i);
     j->bytes[i] = b;
     napi_value abv;
     void* data = NULL;
@@ -480,16 +488,8 @@ static int job_alloc(napi_env env, job* j, napi_value feats) {
       return 0;
     }
     j->bufs[i] = data;
+    set_field(&j->out, &j->aux, i, data);
   }
-  for (int i = 0; i < MGX_NUM_SCALARS; ++i) j->out.scalars[i] = j->bufs[i];
-  j->out.loudness_specific = (float*)j->bufs[SLOT_LOUD];
-  j->out.mfcc = (float*)j->bufs[SLOT_MFCC];
-  j->out.amplitude_spectrum = (float*)j->bufs[SLOT_AMP];
-  j->out.power_spectrum = (float*)j->bufs[SLOT_POW];
-  j->out.complex_real = (float*)j->bufs[SLOT_CRE];
-  j->out.complex_imag = (float*)j->bufs[SLOT_CIM];
-  j->aux.struct_size = sizeof j->aux;
-  j->aux.mel_bands = (float*)j->bufs[SLOT_MEL];
   return 1;
 }
 
@@ -724,45 +724,34 @@ static napi_value extract_into(napi_env env, napi_callback_info info) {
   }
   const uint64_t F = len / n;
   const size_t ss = box->desc.scalar_f64 ? 8 : 4;
-  size_t per[20];
-  for (int i = 0; i < 20; ++i)
-    per[i] = i < MGX_NUM_SCALARS ? ss : i == 13 ? 24 * 4 : i == 14 ? (size_t)box->desc.num_mfcc_coeffs * 4
-           : i == 19 ? (size_t)box->desc.num_mel_bands * 4 : i < 17 ? (size_t)(n / 2) * 4 : (size_t)n * 4;
-  void* ptr[20];
+  void* ptr[NSLOTS];
   const double* o = (const double*)offs;
-  for (int i = 0; i < 20; ++i) {
+  for (int i = 0; i < NSLOTS; ++i) {
     ptr[i] = NULL;
     if (i >= (int)olen || !(o[i] >= 0)) continue;
-    const double end = o[i] + (double)(per[i] * F);
+    const double end = o[i] + (double)(field_bytes(&box->desc, i) * F);
     if (o[i] != (double)(uint64_t)o[i] || end > (double)out_bytes || ((uint64_t)o[i] % (i < MGX_NUM_SCALARS ? ss : 4))) {
       napi_throw_range_error(env, NULL, "an output's offset is misaligned or runs past the end of out");
       return NULL;
     }
     ptr[i] = (unsigned char*)out + (uint64_t)o[i];
   }
-  if ((ptr[17] == NULL) != (ptr[18] == NULL)) {
+  if ((ptr[SLOT_CRE] == NULL) != (ptr[SLOT_CIM] == NULL)) {
     napi_throw_range_error(env, NULL, "complex real and imag go together");
+    return NULL;
+  }
+  if (ptr[SLOT_MEL] && box->group) {
+    napi_throw_error(env, NULL, "melBands is not supported on a plan created with `devices`: device groups take no auxiliary outputs");
     return NULL;
   }
   mgx_outputs mo;
   memset(&mo, 0, sizeof mo);
-  for (int i = 0; i < MGX_NUM_SCALARS; ++i) mo.scalars[i] = ptr[i];
-  mo.loudness_specific = (float*)ptr[13];
-  mo.mfcc = (float*)ptr[14];
-  mo.amplitude_spectrum = (float*)ptr[15];
-  mo.power_spectrum = (float*)ptr[16];
-  mo.complex_real = (float*)ptr[17];
-  mo.complex_imag = (float*)ptr[18];
-  if (ptr[19] && box->group) {
-    napi_throw_error(env, NULL, "melBands is not supported on a plan created with `devices`: device groups take no auxiliary outputs");
-    return NULL;
-  }
   mgx_aux_outputs ma;
   memset(&ma, 0, sizeof ma);
   ma.struct_size = sizeof ma;
-  ma.mel_bands = (float*)ptr[19];
+  for (int i = 0; i < NSLOTS; ++i) set_field(&mo, &ma, i, ptr[i]);
   const int rc = box->group ? mgx_group_extract_host(box->group, (const float*)data, F, &mo)
-                 : ptr[19]  ? mgx_extract_host_ex(box->plan, (const float*)data, F * n, n, &mo, &ma)
+                 : ptr[SLOT_MEL] ? mgx_extract_host_ex(box->plan, (const float*)data, F * n, n, &mo, &ma)
                             : mgx_extract_host(box->plan, (const float*)data, F, &mo);
   if (rc) return throw_mgx(env, rc);
   return argv[3];

@@ -103,65 +103,33 @@ int rccl_fail(ncclResult_t e, const char* what) {
     if (e_ != ncclSuccess) return rccl_fail(e_, what);  \
   } while (0)
 
-constexpr int kFields = 19;  // 13 scalars, loudness_specific, mfcc, amplitude, power, complex real, imag
+// The groups gather the mgx_outputs fields, the first kGroupFields of the field table (out_fields.h).
+using mgx::kGroupFields;
+using mgx::out_field;
+using mgx::out_field_bytes;
 
-// Bytes per frame of output array i (mgx_packed_layout numbering).
-uint64_t field_bytes(const mgx_plan_desc& d, int i) {
-  if (i < MGX_NUM_SCALARS) return d.scalar_f64 ? 8 : 4;
-  switch (i) {
-    case 13: return 4ull * d.num_bark_bands;
-    case 14: return 4ull * d.num_mfcc_coeffs;
-    case 15: case 16: return 4ull * (d.buffer_size / 2);
-    default: return 4ull * d.buffer_size;
-  }
-}
-
+// An MGX_OUT_* mask names the complex spectrum once, for its two fields (bit 17: fields 17 and 18).
 bool field_in(uint32_t mask, int i) { return (mask >> (i < 18 ? i : 17)) & 1u; }
-
-void*& field_ptr(mgx_outputs& o, int i) {
-  static void* none = nullptr;
-  if (i < MGX_NUM_SCALARS) return o.scalars[i];
-  switch (i) {
-    case 13: return reinterpret_cast<void*&>(o.loudness_specific);
-    case 14: return reinterpret_cast<void*&>(o.mfcc);
-    case 15: return reinterpret_cast<void*&>(o.amplitude_spectrum);
-    case 16: return reinterpret_cast<void*&>(o.power_spectrum);
-    case 17: return reinterpret_cast<void*&>(o.complex_real);
-    case 18: return reinterpret_cast<void*&>(o.complex_imag);
-    default: return none;
-  }
-}
+uint32_t mask_fields(uint32_t mask) { return (mask & MGX_OUT_ALL_MASK) | (mask & MGX_OUT_COMPLEX_SPECTRUM) << 1; }
 
 uint64_t packed_layout(const mgx_plan_desc& d, uint32_t mask, uint64_t nf, uint64_t* off) {
-  uint64_t at = 0;
-  for (int i = 0; i < kFields; ++i) {
-    if (!field_in(mask, i)) {
-      if (off) off[i] = UINT64_MAX;
-      continue;
-    }
-    if (off) off[i] = at;
-    at += (field_bytes(d, i) * nf + 255) / 256 * 256;
-  }
-  return at;
+  return mgx::out_layout(d, mask_fields(mask), nf, off, kGroupFields);
 }
 
 // Outputs of frames [f0, ...) of a structure-of-arrays record.
-mgx_outputs offset_outputs(const mgx_plan_desc& d, const mgx_outputs& o, uint32_t mask, uint64_t f0) {
-  mgx_outputs r{};
-  mgx_outputs src = o;
-  for (int i = 0; i < kFields; ++i)
-    if (field_in(mask, i) && field_ptr(src, i))
-      field_ptr(r, i) = static_cast<unsigned char*>(field_ptr(src, i)) + f0 * field_bytes(d, i);
+mgx::Outputs offset_outputs(const mgx_plan_desc& d, const mgx_outputs& o, uint32_t mask, uint64_t f0) {
+  mgx::Outputs r{};
+  const mgx::Outputs src = mgx::from_public(o);
+  for (int i = 0; i < kGroupFields; ++i)
+    if (field_in(mask, i) && out_field(src, i))
+      out_field(r, i) = static_cast<unsigned char*>(out_field(src, i)) + f0 * out_field_bytes(d, i);
   return r;
 }
 
 mgx_outputs packed_outputs(const mgx_plan_desc& d, unsigned char* base, uint32_t mask, uint64_t nf) {
-  uint64_t off[kFields];
+  uint64_t off[kGroupFields];
   packed_layout(d, mask, nf, off);
-  mgx_outputs r{};
-  for (int i = 0; i < kFields; ++i)
-    if (off[i] != UINT64_MAX) field_ptr(r, i) = base + off[i];
-  return r;
+  return mgx::public_part(mgx::out_at(base, off, kGroupFields));
 }
 
 void chunk_of(uint64_t count, uint32_t nch, uint32_t c, uint64_t* c0, uint64_t* cn) {
@@ -753,9 +721,9 @@ static int group_extract(mgx_group* g, const float* const* frames, const uint64_
   const bool root_local = g->m[0].rank == 0;
   if (root_local) {
     if (!root_out) return fail(MGX_E_INVALID_ARGUMENT, "root outputs are NULL on the root");
-    mgx_outputs chk = *root_out;
-    for (int i = 0; i < kFields; ++i)
-      if (field_in(mask, i) && !field_ptr(chk, i)) return fail(MGX_E_INVALID_ARGUMENT, "output %d is in the mask but NULL", i);
+    const mgx::Outputs chk = mgx::from_public(*root_out);
+    for (int i = 0; i < kGroupFields; ++i)
+      if (field_in(mask, i) && !out_field(chk, i)) return fail(MGX_E_INVALID_ARGUMENT, "output %d is in the mask but NULL", i);
   }
   for (size_t i = 0; i < g->m.size(); ++i)
     if (counts[g->m[i].rank] && !frames[i]) return fail(MGX_E_INVALID_ARGUMENT, "frames of local rank %zu are NULL", i);
@@ -833,16 +801,16 @@ static int group_extract(mgx_group* g, const float* const* frames, const uint64_
       uint64_t c0, cn;
       chunk_of(counts[p], nch, c, &c0, &cn);
       if (!cn) continue;
-      uint64_t off[kFields];
+      uint64_t off[kGroupFields];
       packed_layout(d, mask, cn, off);
       mgx::UnpackArgs ua{};
       ua.src = srcs ? srcs[p] : m.xfer + ((uint64_t)(p - 1) * 2 + (c & 1)) * slot;
-      mgx_outputs dst = offset_outputs(d, *root_out, mask, start[p] + c0);
-      for (int i = 0; i < kFields; ++i) {
+      const mgx::Outputs dst = offset_outputs(d, *root_out, mask, start[p] + c0);
+      for (int i = 0; i < kGroupFields; ++i) {
         if (off[i] == UINT64_MAX) continue;
         ua.src_off[ua.nseg] = off[i];
-        ua.dst[ua.nseg] = field_ptr(dst, i);
-        ua.dwords[ua.nseg] = field_bytes(d, i) * cn / 4;
+        ua.dst[ua.nseg] = out_field(dst, i);
+        ua.dwords[ua.nseg] = out_field_bytes(d, i) * cn / 4;
         ++ua.nseg;
       }
       HIP_OK(mgx::launch_unpack(ua, m.s_comm), "unpack kernel launch");
@@ -895,7 +863,7 @@ static int group_extract(mgx_group* g, const float* const* frames, const uint64_
       const hipStream_t st = sl ? m.s_alt : cs[i];
       if (m.rank == 0) {
         if (cn) {
-          const mgx_outputs o = offset_outputs(d, *root_out, mask, start[0] + c0);
+          const mgx_outputs o = mgx::public_part(offset_outputs(d, *root_out, mask, start[0] + c0));
           int rc = mgx_extract_device(m.plan, src, cn, &o, st);
           if (rc) return rc;
         }
@@ -1054,15 +1022,13 @@ int mgx_group_extract_host(mgx_group* g, const float* frames, uint64_t nframes, 
     return fail(MGX_E_UNSUPPORTED, "host batches need a single-process group (mgx_group_create)");
   if (nframes == 0) return MGX_OK;
   if (!frames) return fail(MGX_E_INVALID_ARGUMENT, "frames is NULL");
-  if ((o->complex_real == nullptr) != (o->complex_imag == nullptr))
-    return fail(MGX_E_INVALID_ARGUMENT, "complex_real and complex_imag must be given together");
+  const mgx::Outputs oh = mgx::from_public(*o);
+  const char* why = nullptr;
+  if (const int rc = mgx::outputs_ok(oh, &why)) return fail(rc, "%s", why);
   const mgx_plan_desc& d = g->d;
   const uint32_t R = g->nranks;
   const uint64_t N = d.buffer_size;
-  mgx_outputs oh = *o;
-  uint32_t mask = 0;
-  for (int i = 0; i < 18; ++i)
-    if (field_ptr(oh, i)) mask |= 1u << i;
+  const uint32_t mask = mgx::out_requested(oh) & MGX_OUT_ALL_MASK;  // (bit 17: the complex pair, both given)
   std::vector<uint64_t> start(R), cnt(R);
   for (uint32_t r = 0; r < R; ++r) mgx_shard_range(nframes, R, r, &start[r], &cnt[r]);
   // shards to the devices, one host thread per device (parallel PCIe copies)
@@ -1092,7 +1058,7 @@ int mgx_group_extract_host(mgx_group* g, const float* frames, uint64_t nframes, 
   // the gathered record on the root device
   Member& root = g->m[0];
   HIP_OK(hipSetDevice(root.device), "hipSetDevice");
-  uint64_t off[kFields];
+  uint64_t off[kGroupFields];
   const uint64_t bytes = packed_layout(d, mask, nframes, off);
   int rc = ensure(&root.h_out, &root.h_out_bytes, bytes, "hipMalloc(gathered outputs)");
   if (rc) return rc;
@@ -1106,9 +1072,9 @@ int mgx_group_extract_host(mgx_group* g, const float* frames, uint64_t nframes, 
     HIP_OK(hipStreamSynchronize(m.s_comp), "hipStreamSynchronize");
   }
   HIP_OK(hipSetDevice(root.device), "hipSetDevice");
-  for (int i = 0; i < kFields; ++i) {
+  for (int i = 0; i < kGroupFields; ++i) {
     if (off[i] == UINT64_MAX) continue;
-    HIP_OK(hipMemcpy(field_ptr(oh, i), root.h_out + off[i], field_bytes(d, i) * nframes, hipMemcpyDeviceToHost),
+    HIP_OK(hipMemcpy(out_field(oh, i), root.h_out + off[i], out_field_bytes(d, i) * nframes, hipMemcpyDeviceToHost),
            "hipMemcpy(outputs)");
   }
   return MGX_OK;

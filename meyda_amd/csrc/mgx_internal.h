@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "../../include/meyda_gpu.h"
+#include "out_fields.h"  // mgx::Outputs and the table of its fields
 
 namespace mgx {
 
@@ -56,23 +57,6 @@ struct DevTables {
   const void* lds_image;
   uint32_t lds_image_chunks; // 16-byte chunks of the image
 };
-
-// The output arrays a launch writes: the fields of mgx_outputs, then the ones that came after its layout was
-// fixed (mgx_aux_outputs of the mgx_extract_*_ex calls). The plan code and the kernels pass this around;
-// the public entry points build it from the caller's two structs (plan.cpp make_outputs).
-struct Outputs {
-  void* scalars[MGX_NUM_SCALARS];
-  float* loudness_specific;
-  float* mfcc;
-  float* amplitude_spectrum;
-  float* power_spectrum;
-  float* complex_real;
-  float* complex_imag;
-  float* mel_bands;  // num_frames x nfilt: the log mel energies the DCT reads (mfcc.js:53-65)
-};
-static_assert(offsetof(Outputs, mel_bands) == sizeof(mgx_outputs) && offsetof(Outputs, mfcc) == offsetof(mgx_outputs, mfcc) &&
-                  offsetof(Outputs, complex_imag) == offsetof(mgx_outputs, complex_imag),
-              "Outputs begins with mgx_outputs");
 
 struct KernelArgs {
   const float* frames;
@@ -192,7 +176,7 @@ hipError_t launch_pcm_decode(const void* pcm, uint64_t count, uint32_t format, u
                              uint32_t channel, float* out, hipStream_t stream);
 // Scatter of one packed transfer buffer into the root's outputs (group.cpp): segment i
 // copies dwords[i] dwords from src + src_off[i] to dst[i].
-constexpr int kMaxSegs = 19;
+constexpr int kMaxSegs = kGroupFields;
 struct UnpackArgs {
   const unsigned char* src;
   uint64_t src_off[kMaxSegs];

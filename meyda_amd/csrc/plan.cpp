@@ -528,22 +528,40 @@ struct GatherLaunch {
   const uint64_t* starts;
   uint64_t num_samples;
 };
+// What a launch may carry beyond its frames and outputs (extract_device_impl), each null when it does not
+struct LaunchOpts {
+  const uint32_t* done = nullptr;         // the small host path's completion word (device address)
+  const float* inline_frame = nullptr;    // the small path's one frame in host memory, for the kernel arguments
+  const ResidentLaunch* res = nullptr;
+  const GatherLaunch* gather = nullptr;
+};
 int extract_device_impl(mgx_plan* p, const float* frames, uint64_t nframes, uint64_t stride, const mgx::Outputs* o, void* stream,
-                        const uint32_t* done, const float* inline_frame = nullptr, const ResidentLaunch* res = nullptr,
-                        const GatherLaunch* gather = nullptr);
+                        const LaunchOpts& opt = LaunchOpts{});
 void resident_stop(mgx_plan* p);
 
-// The caller's two output structs as the one the plan code passes around. aux: NULL (no output beyond
-// mgx_outputs), or a mgx_aux_outputs of exactly this build's size -- the check that lets the struct grow.
-int make_outputs(const mgx_outputs* o, const mgx_aux_outputs* aux, mgx::Outputs* out) {
-  *out = mgx::Outputs{};
-  memcpy(out, o, sizeof *o);  // (Outputs begins with mgx_outputs: mgx_internal.h)
+// The plan's entry in the per-device tables (g_resident_live)
+int dev_slot(const mgx_plan* p) { return p->d.device >= 0 && p->d.device < kMaxDevices ? p->d.device : 0; }
+
+// What every mgx_extract_* entry point begins with: the plan and the outputs are there, and the caller's two
+// output structs become the one the plan code passes around. aux: NULL (no output beyond mgx_outputs), or a
+// mgx_aux_outputs of exactly this build's size -- the check that lets the struct grow.
+int make_outputs(const mgx_plan* p, const mgx_outputs* o, const mgx_aux_outputs* aux, mgx::Outputs* out) {
+  if (!p || !o) return fail(MGX_E_INVALID_ARGUMENT, "NULL plan or outputs");
+  *out = mgx::from_public(*o);
   if (!aux) return MGX_OK;
   if (aux->struct_size != sizeof(mgx_aux_outputs))
     return fail(MGX_E_INVALID_ARGUMENT, "mgx_aux_outputs.struct_size is %u, expected %zu", aux->struct_size, sizeof(mgx_aux_outputs));
   if (aux->reserved != 0) return fail(MGX_E_INVALID_ARGUMENT, "mgx_aux_outputs.reserved is %u, expected 0", aux->reserved);
   out->mel_bands = aux->mel_bands;
   return MGX_OK;
+}
+
+// The rule about the outputs themselves (mgx::outputs_ok) as an error. Each kind of call reports it where it
+// always has among its argument errors: after the empty call and the NULL inputs (for PCM before them).
+int check_outputs(const mgx::Outputs& o) {
+  const char* why = nullptr;
+  const int rc = mgx::outputs_ok(o, &why);
+  return rc ? fail(rc, "%s", why) : MGX_OK;
 }
 }  // namespace
 
@@ -767,16 +785,9 @@ int mgx_plan_create(const mgx_plan_desc* d, mgx_plan** out) {
     // (the pinned buffers, the CU-masked stream's hardware queue; profiles/r06_resident.txt): one call on a
     // silent frame with every output (the largest layout), then the launch is ended.
     std::vector<float> z((size_t)n, 0.0f);
-    std::vector<double> sc(MGX_NUM_SCALARS);
-    std::vector<float> ls(mgx::kBark), mc(nc), am(L), pw(L), cr(n), ci(n);
-    mgx_outputs o{};
-    for (int i = 0; i < MGX_NUM_SCALARS; ++i) o.scalars[i] = &sc[i];  // (8 bytes each: room for either width)
-    o.loudness_specific = ls.data();
-    o.mfcc = mc.data();
-    o.amplitude_spectrum = am.data();
-    o.power_spectrum = pw.data();
-    o.complex_real = cr.data();
-    o.complex_imag = ci.data();
+    uint64_t at[mgx::kOutFields];
+    std::vector<unsigned char> buf(mgx::out_layout(*d, mgx::kGroupFieldBits, 1, at));
+    const mgx_outputs o = mgx::public_part(mgx::out_at(buf.data(), at));
     int rc = mgx_extract_host(p, z.data(), 1, &o);
     resident_stop(p);
     if (rc) {
@@ -854,14 +865,13 @@ int mgx_extract_signal_device(mgx_plan* p, const float* samples, uint64_t num_sa
 
 int mgx_extract_device_ex(mgx_plan* p, const float* samples, uint64_t num_samples, uint32_t hop, const mgx_outputs* o,
                           const mgx_aux_outputs* aux, void* stream) {
-  if (!p || !o) return fail(MGX_E_INVALID_ARGUMENT, "NULL plan or outputs");
   mgx::Outputs x;
-  int rc = make_outputs(o, aux, &x);
+  int rc = make_outputs(p, o, aux, &x);
   if (rc) return rc;
   uint64_t nframes = 0;
   rc = mgx_signal_frames(num_samples, (uint32_t)p->n, hop, &nframes);
   if (rc) return rc;
-  return extract_device_impl(p, samples, nframes, hop, &x, stream, nullptr);
+  return extract_device_impl(p, samples, nframes, hop, &x, stream);
 }
 
 // A corpus as one array: the buffers of every signal, none across a signal's end
@@ -897,16 +907,17 @@ int mgx_signals_frame_starts(const uint64_t* offsets, uint64_t num_signals, uint
 
 int mgx_extract_gather_device(mgx_plan* p, const float* samples, uint64_t num_samples, const uint64_t* starts, uint64_t nframes,
                               const mgx_outputs* o, const mgx_aux_outputs* aux, void* stream) {
-  if (!p || !o) return fail(MGX_E_INVALID_ARGUMENT, "NULL plan or outputs");
   mgx::Outputs x;
-  const int rc = make_outputs(o, aux, &x);
+  const int rc = make_outputs(p, o, aux, &x);
   if (rc) return rc;
   if (nframes == 0) return MGX_OK;
   if (!starts) return fail(MGX_E_INVALID_ARGUMENT, "starts is NULL");
   if (num_samples < (uint64_t)p->n)
     return fail(MGX_E_INVALID_ARGUMENT, "%llu samples hold no buffer of %d", (unsigned long long)num_samples, p->n);
   const GatherLaunch g{starts, num_samples};
-  return extract_device_impl(p, samples, nframes, (uint64_t)p->n, &x, stream, nullptr, nullptr, nullptr, &g);
+  LaunchOpts opt;
+  opt.gather = &g;
+  return extract_device_impl(p, samples, nframes, (uint64_t)p->n, &x, stream, opt);
 }
 
 }  // extern "C"
@@ -946,17 +957,16 @@ int add_stream_scratch(mgx_plan* p, void* stream) {
 }
 
 // mgx_extract_device and mgx_extract_signal_device (stride: the samples from one frame's start to the next, N
-// for dense frames), and with `done` (the small host path) the launch's completion word; inline_frame
+// for dense frames), and with opt.done (the small host path) the launch's completion word; opt.inline_frame
 // (the small path's one frame in host memory) goes into the kernel arguments where the kernel takes it
-// (mgx::launch_extract); res: the plan's resident launch (resident_request). Any other launch ends the
+// (mgx::launch_extract); opt.res: the plan's resident launch (resident_request). Any other launch ends the
 // plan's resident one first, so the plan's own work never waits behind it or shares the device with it.
 int extract_device_impl(mgx_plan* p, const float* frames, uint64_t nframes, uint64_t stride, const mgx::Outputs* o, void* stream,
-                        const uint32_t* done, const float* inline_frame, const ResidentLaunch* res, const GatherLaunch* gather) {
-  if (!p || !o) return fail(MGX_E_INVALID_ARGUMENT, "NULL plan or outputs");
+                        const LaunchOpts& opt) {
+  const auto [done, inline_frame, res, gather] = opt;
   if (nframes == 0) return MGX_OK;
   if (!frames) return fail(MGX_E_INVALID_ARGUMENT, "frames is NULL");
-  if ((o->complex_real == nullptr) != (o->complex_imag == nullptr))
-    return fail(MGX_E_INVALID_ARGUMENT, "complex_real and complex_imag must be given together");
+  if (int rc = check_outputs(*o)) return rc;  // (the device entry points' check; the host paths come checked)
   if (!res) resident_stop(p);
   mgx::KernelArgs a{};
   a.frames = frames;
@@ -994,8 +1004,7 @@ int extract_device_impl(mgx_plan* p, const float* frames, uint64_t nframes, uint
   for (int i = 0; i < MGX_NUM_SCALARS; ++i) any_scalar = any_scalar || o->scalars[i];
   const uint64_t fb = (uint64_t)mgx::frames_per_batch(p->n);
   const uint64_t nb = (nframes + fb - 1) / fb;
-  const int dev_slot = p->d.device >= 0 && p->d.device < kMaxDevices ? p->d.device : 0;
-  const int cap = std::max(1, p->grid_cap - (res ? 0 : g_resident_live[dev_slot].load(std::memory_order_relaxed)));
+  const int cap = std::max(1, p->grid_cap - (res ? 0 : g_resident_live[dev_slot(p)].load(std::memory_order_relaxed)));
   const int grid = (int)std::min<uint64_t>(nb, (uint64_t)cap);
   a.wg_ranks = grid == p->grid_cap && p->cus > 0 ? p->grid_cap / p->cus : 1;
   // The scalars run once per window of a wave's batches (kernels.hip scalar_pass) when the launch
@@ -1135,13 +1144,9 @@ int ensure_host_staging(mgx_plan* p, uint64_t chunk, size_t out_bytes) {
 }
 
 // Device bytes per frame of the requested outputs (host staging layouts).
-size_t out_bytes_per_frame(const mgx_plan* p, const mgx::Outputs* o) {
-  const size_t ss = p->d.scalar_f64 ? 8 : 4;
+size_t out_bytes_per_frame(const mgx_plan* p, uint32_t fields) {
   size_t per = 0;
-  for (int i = 0; i < MGX_NUM_SCALARS; ++i) per += o->scalars[i] ? ss : 0;
-  per += (o->loudness_specific ? (size_t)mgx::kBark * 4 : 0) + (o->mfcc ? (size_t)p->d.num_mfcc_coeffs * 4 : 0) +
-         (o->mel_bands ? (size_t)p->d.num_mel_bands * 4 : 0) + (o->amplitude_spectrum ? (size_t)p->L * 4 : 0) + (o->power_spectrum ? (size_t)p->L * 4 : 0) +
-         (o->complex_real ? 2 * (size_t)p->n * 4 : 0);
+  for (int i = 0; i < mgx::kOutFields; ++i) per += (fields >> i) & 1u ? mgx::out_field_bytes(p->d, i) : 0;
   return per;
 }
 
@@ -1150,7 +1155,7 @@ size_t out_bytes_per_frame(const mgx_plan* p, const mgx::Outputs* o) {
 // synchronisation).
 void resident_ended(mgx_plan* p) {
   p->res_live = false;
-  g_resident_live[p->d.device >= 0 && p->d.device < kMaxDevices ? p->d.device : 0].fetch_sub(1, std::memory_order_relaxed);
+  g_resident_live[dev_slot(p)].fetch_sub(1, std::memory_order_relaxed);
 }
 
 void resident_stop(mgx_plan* p) {
@@ -1160,15 +1165,9 @@ void resident_stop(mgx_plan* p) {
   resident_ended(p);
 }
 
-// bit k: output k of mgx_outputs requested (the scalars, then loudness, mfcc, amplitude, power, complex)
-// (mel_bands is not among them: a request for it is served by a launch, extract_host_small)
-uint32_t output_key(const mgx::Outputs* o) {
-  uint32_t k = 0;
-  for (int i = 0; i < MGX_NUM_SCALARS; ++i) k |= o->scalars[i] ? 1u << i : 0u;
-  const void* v[] = {o->loudness_specific, o->mfcc, o->amplitude_spectrum, o->power_spectrum, o->complex_real, o->complex_imag};
-  for (int i = 0; i < 6; ++i) k |= v[i] ? 1u << (MGX_NUM_SCALARS + i) : 0u;
-  return k;
-}
+// bit k: field k of mgx_outputs requested. The resident launch serves those fields alone: a request for a
+// later one (mel_bands) is served by a launch of its own (extract_host_small), so it is no part of the key.
+uint32_t output_key(const mgx::Outputs* o) { return mgx::out_requested(*o) & mgx::kGroupFieldBits; }
 
 // One frame (in p->h_in) through the plan's resident launch (MGX_FLAG_RESIDENT), its outputs landing in the
 // small path's pinned layout h (device addresses d) under request number seq:
@@ -1228,10 +1227,13 @@ int resident_request(mgx_plan* p, const mgx::Outputs* o, const mgx::Outputs& d, 
   auto start = [&]() -> int {
     __atomic_store_n(exitw, 0u, __ATOMIC_RELEASE);
     const ResidentLaunch rl{seq};
-    const int rc = extract_device_impl(p, p->t.window, 1, (uint64_t)p->n, &d, p->s_res, p->d_done_map, nullptr, &rl);
+    LaunchOpts opt;
+    opt.done = p->d_done_map;
+    opt.res = &rl;
+    const int rc = extract_device_impl(p, p->t.window, 1, (uint64_t)p->n, &d, p->s_res, opt);
     if (rc) return rc;
     p->res_live = true;
-    g_resident_live[p->d.device >= 0 && p->d.device < kMaxDevices ? p->d.device : 0].fetch_add(1, std::memory_order_relaxed);
+    g_resident_live[dev_slot(p)].fetch_add(1, std::memory_order_relaxed);
     p->res_key = key;
     return MGX_OK;
   };
@@ -1263,20 +1265,8 @@ int resident_request(mgx_plan* p, const mgx::Outputs* o, const mgx::Outputs& d, 
   return MGX_OK;
 }
 
-// A small host batch (at most p->small_max frames): the frames into the plan's pinned input
-// buffer, one launch that reads them over PCIe and writes the features into the pinned output
-// buffer, one synchronisation, the features out to the caller's arrays. `fill(dst)` writes the
-// batch's float32 frames to host memory at dst. The buffers are coherent (fine-grained) host
-// memory mapped into the device, so no cache of either side holds a stale copy between calls.
-// stride: the samples from one frame's start to the next in what `fill` writes, (nframes - 1) stride + N
-// samples in all (N: dense frames; a signal's hop <= N: its samples as they are, each written once).
-template <typename Fill>
-int extract_host_small(mgx_plan* p, uint64_t nframes, uint64_t stride, const mgx::Outputs* o, Fill fill) {
-  const int n = p->n, L = p->L;
-  const size_t ss = p->d.scalar_f64 ? 8 : 4;
-  const size_t nb = mgx::kBark, nc = p->d.num_mfcc_coeffs;
-  const size_t in_bytes = ((nframes - 1) * (size_t)stride + (size_t)n) * sizeof(float);
-  const size_t out_bytes = out_bytes_per_frame(p, o) * nframes + 21 * 256;
+// The small path's pinned buffers (mapped into the device, coherent), grown to the call's sizes, and its stream.
+int small_buffers(mgx_plan* p, size_t in_bytes, size_t out_bytes) {
   hipError_t e = hipSetDevice(p->d.device);
   if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
   if (!p->s_comp) {
@@ -1294,7 +1284,7 @@ int extract_host_small(mgx_plan* p, uint64_t nframes, uint64_t stride, const mgx
     if (p->h_in) (void)hipHostFree(p->h_in);
     p->h_in = nullptr;
     p->h_in_bytes = 0;
-    const size_t want = std::max<size_t>(in_bytes, 16 * (size_t)n * sizeof(float));
+    const size_t want = std::max<size_t>(in_bytes, 16 * (size_t)p->n * sizeof(float));
     e = hipHostMalloc(reinterpret_cast<void**>(&p->h_in), want, hipHostMallocMapped | hipHostMallocCoherent);
     if (e != hipSuccess) return hip_fail(e, "hipHostMalloc(small batch frames)");
     e = hipHostGetDevicePointer(&p->d_in_map, p->h_in, 0);
@@ -1311,154 +1301,144 @@ int extract_host_small(mgx_plan* p, uint64_t nframes, uint64_t stride, const mgx
     if (e != hipSuccess) return hip_fail(e, "hipHostGetDevicePointer(small batch outputs)");
     p->h_out_bytes = out_bytes;
   }
-  int rc = fill(p->h_in);
-  if (rc) return rc;
-  void* const din = p->d_in_map;
-  void* const dout = p->d_out_map;
-  const size_t nm = p->d.num_mel_bands;
-  mgx::Outputs d{};
-  const mgx::Outputs h = [&] {  // the same layout, host addresses
-    mgx::Outputs r{};
-    size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t at = off; off += (bytes + 255) / 256 * 256; return at; };
-    size_t at[20];
-    for (int k = 0; k < MGX_NUM_SCALARS; ++k) at[k] = o->scalars[k] ? take(nframes * ss) : 0;
-    at[13] = o->loudness_specific ? take(nframes * nb * 4) : 0;
-    at[14] = o->mfcc ? take(nframes * nc * 4) : 0;
-    at[15] = o->amplitude_spectrum ? take(nframes * L * 4) : 0;
-    at[16] = o->power_spectrum ? take(nframes * L * 4) : 0;
-    at[17] = o->complex_real ? take(nframes * (size_t)n * 4) : 0;
-    at[18] = o->complex_imag ? take(nframes * (size_t)n * 4) : 0;
-    at[19] = o->mel_bands ? take(nframes * nm * 4) : 0;
-    unsigned char* dv = static_cast<unsigned char*>(dout);
-    for (int k = 0; k < MGX_NUM_SCALARS; ++k) {
-      d.scalars[k] = o->scalars[k] ? dv + at[k] : nullptr;
-      r.scalars[k] = o->scalars[k] ? p->h_out + at[k] : nullptr;
-    }
-    auto both = [&](bool want, size_t a, float*& dd, float*& hh) {
-      dd = want ? reinterpret_cast<float*>(dv + a) : nullptr;
-      hh = want ? reinterpret_cast<float*>(p->h_out + a) : nullptr;
-    };
-    both(o->loudness_specific, at[13], d.loudness_specific, r.loudness_specific);
-    both(o->mfcc, at[14], d.mfcc, r.mfcc);
-    both(o->amplitude_spectrum, at[15], d.amplitude_spectrum, r.amplitude_spectrum);
-    both(o->power_spectrum, at[16], d.power_spectrum, r.power_spectrum);
-    both(o->complex_real, at[17], d.complex_real, r.complex_real);
-    both(o->complex_imag, at[18], d.complex_imag, r.complex_imag);
-    both(o->mel_bands, at[19], d.mel_bands, r.mel_bands);
-    return r;
-  }();
-  if (!p->h_done) {
-    uint32_t* hd = nullptr;
-    e = hipHostMalloc(reinterpret_cast<void**>(&hd), 64, hipHostMallocMapped | hipHostMallocCoherent);
-    if (e != hipSuccess) return hip_fail(e, "hipHostMalloc(completion word)");
-    *hd = 0;
-    e = hipMalloc(reinterpret_cast<void**>(&p->d_done_count), sizeof(uint32_t));
-    // (on the stream the launches run on: a null-stream memset of device memory may return before it has
-    // run, and the non-blocking s_comp does not wait for it -- the first launch's waves could count first)
-    if (e == hipSuccess) e = hipMemsetAsync(p->d_done_count, 0, sizeof(uint32_t), p->s_comp);
-    if (e != hipSuccess) {
-      (void)hipHostFree(hd);
-      return hip_fail(e, "completion counter");
-    }
-    e = hipHostGetDevicePointer(reinterpret_cast<void**>(&p->d_done_map), hd, 0);
-    if (e != hipSuccess) {
-      (void)hipHostFree(hd);
-      return hip_fail(e, "hipHostGetDevicePointer(completion word)");
-    }
-    p->h_done = hd;
+  return MGX_OK;
+}
+
+// The small path's completion word (mgx_plan::h_done) and the device counter behind it, made once.
+int small_done_word(mgx_plan* p) {
+  if (p->h_done) return MGX_OK;
+  uint32_t* hd = nullptr;
+  hipError_t e = hipHostMalloc(reinterpret_cast<void**>(&hd), 64, hipHostMallocMapped | hipHostMallocCoherent);
+  if (e != hipSuccess) return hip_fail(e, "hipHostMalloc(completion word)");
+  *hd = 0;
+  e = hipMalloc(reinterpret_cast<void**>(&p->d_done_count), sizeof(uint32_t));
+  // (on the stream the launches run on: a null-stream memset of device memory may return before it has
+  // run, and the non-blocking s_comp does not wait for it -- the first launch's waves could count first)
+  if (e == hipSuccess) e = hipMemsetAsync(p->d_done_count, 0, sizeof(uint32_t), p->s_comp);
+  if (e != hipSuccess) {
+    (void)hipHostFree(hd);
+    return hip_fail(e, "completion counter");
   }
-  uint32_t* const ddone = p->d_done_map;
+  e = hipHostGetDevicePointer(reinterpret_cast<void**>(&p->d_done_map), hd, 0);
+  if (e != hipSuccess) {
+    (void)hipHostFree(hd);
+    return hip_fail(e, "hipHostGetDevicePointer(completion word)");
+  }
+  p->h_done = hd;
+  return MGX_OK;
+}
+
+// One frame without spectrum outputs (at most 13 + 24 + 32 + 64 words): the host waits on the output words
+// themselves -- each preset to an all-ones NaN and polled until the kernel's store has landed -- and the
+// launch releases no completion word, which spares the system-scope release (a wait for the outputs'
+// write acknowledgements) and the word's own trip back. Stores of 4 and 8 aligned bytes arrive whole: a
+// field's words are 8 bytes for an f64 scalar and 4 otherwise. An output that is itself that NaN (a NaN
+// input can carry any payload) only ends the spin at its limit.
+// Before the launch: the one frame's requested fields (h: their host addresses), all ones.
+void preset_output_words(const mgx_plan* p, uint32_t fields, const mgx::Outputs& h) {
+  for (int i = 0; i < mgx::kOutFields; ++i)
+    if ((fields >> i) & 1u) memset(mgx::out_field(h, i), 0xFF, mgx::out_field_bytes(p->d, i));
+  std::atomic_thread_fence(std::memory_order_release);
+}
+
+// After it: every word of every requested field in field order, then the stream if the spin ran out.
+int wait_output_words(mgx_plan* p, uint32_t fields, const mgx::Outputs& h) {
+  constexpr uint64_t kSent = ~(uint64_t)0;
+  const auto t0 = std::chrono::steady_clock::now();
+  bool late = false;
+  unsigned spins = 0;
+  auto wait_word = [&](const void* w, size_t bytes) {
+    for (;; ++spins) {
+      const uint64_t v = bytes == 8 ? __atomic_load_n(static_cast<const uint64_t*>(w), __ATOMIC_ACQUIRE)
+                                    : (uint64_t)__atomic_load_n(static_cast<const uint32_t*>(w), __ATOMIC_ACQUIRE);
+      if (v != (bytes == 8 ? kSent : (uint64_t)0xFFFFFFFFu)) return;
+      __builtin_ia32_pause();
+      if (late || ((spins & 63) == 63 && std::chrono::steady_clock::now() - t0 > std::chrono::microseconds(kSmallSpinUs))) {
+        late = true;
+        return;
+      }
+    }
+  };
+  for (int i = 0; i < mgx::kOutFields; ++i) {
+    if (!((fields >> i) & 1u)) continue;
+    const size_t word = i < MGX_NUM_SCALARS && p->d.scalar_f64 ? 8 : 4, bytes = mgx::out_field_bytes(p->d, i);
+    const unsigned char* w = static_cast<const unsigned char*>(mgx::out_field(h, i));
+    for (size_t at = 0; at < bytes; at += word) wait_word(w + at, word);
+  }
+  if (late) {  // a busy device, a failed launch, or an output equal to the preset: the stream decides
+    const hipError_t e = hipStreamSynchronize(p->s_comp);
+    if (e != hipSuccess) return hip_fail(e, "small host batch");
+  }
+  return MGX_OK;
+}
+
+// The last wave of the launch releases done_seq to the host word after every output store is
+// visible (kernels.hip done_signal): polling it returns ~9 us sooner than waiting for the
+// stream (tools/ubench/small_latency.hip). Past 20 ms (a busy device) the wait blocks on the
+// stream instead, which also reports a failed launch. The spin pauses the core between reads
+// (a contended device leaves N-API worker threads waiting here) and gives up after kSmallSpinUs.
+int wait_done_word(mgx_plan* p) {
+  const auto t0 = std::chrono::steady_clock::now();
+  for (unsigned spins = 0;; ++spins) {
+    if (__atomic_load_n(p->h_done, __ATOMIC_ACQUIRE) == p->done_seq) return MGX_OK;
+    __builtin_ia32_pause();
+    if ((spins & 63) == 63 && std::chrono::steady_clock::now() - t0 > std::chrono::microseconds(kSmallSpinUs)) break;
+  }
+  const hipError_t e = hipStreamSynchronize(p->s_comp);
+  if (e != hipSuccess) return hip_fail(e, "small host batch");
+  if (__atomic_load_n(p->h_done, __ATOMIC_ACQUIRE) != p->done_seq)
+    return fail(MGX_E_DEVICE, "small host batch: the launch completed without its completion word");
+  return MGX_OK;
+}
+
+// A small host batch (at most p->small_max frames): the frames into the plan's pinned input
+// buffer, one launch that reads them over PCIe and writes the features into the pinned output
+// buffer, one synchronisation, the features out to the caller's arrays. `fill(dst)` writes the
+// batch's float32 frames to host memory at dst. The buffers are coherent (fine-grained) host
+// memory mapped into the device, so no cache of either side holds a stale copy between calls.
+// stride: the samples from one frame's start to the next in what `fill` writes, (nframes - 1) stride + N
+// samples in all (N: dense frames; a signal's hop <= N: its samples as they are, each written once).
+template <typename Fill>
+int extract_host_small(mgx_plan* p, uint64_t nframes, uint64_t stride, const mgx::Outputs* o, Fill fill) {
+  const uint32_t fields = mgx::out_requested(*o);
+  const size_t in_bytes = ((nframes - 1) * (size_t)stride + (size_t)p->n) * sizeof(float);
+  const size_t out_bytes = out_bytes_per_frame(p, fields) * nframes + mgx::kOutLayoutSlack;
+  int rc = small_buffers(p, in_bytes, out_bytes);
+  if (rc) return rc;
+  rc = fill(p->h_in);
+  if (rc) return rc;
+  // one layout, the device's addresses (d) and the host's (h)
+  uint64_t off[mgx::kOutFields];
+  mgx::out_layout(p->d, fields, nframes, off);
+  const mgx::Outputs d = mgx::out_at(static_cast<unsigned char*>(p->d_out_map), off);
+  const mgx::Outputs h = mgx::out_at(p->h_out, off);
+  rc = small_done_word(p);
+  if (rc) return rc;
   // never 0 (the word's initial value) nor the resident launch's stop word
   p->done_seq = (p->done_seq + 1 == 0 || p->done_seq + 1 == mgx::kResStop) ? 1 : p->done_seq + 1;
-  // One frame without spectrum outputs (at most 13 + 24 + 32 + 64 words): the host waits on the output words
-  // themselves -- each preset to an all-ones NaN and polled until the kernel's store has landed -- and the
-  // launch releases no completion word, which spares the system-scope release (a wait for the outputs'
-  // write acknowledgements) and the word's own trip back. Stores of 4 and 8 aligned bytes arrive whole. An
-  // output that is itself that NaN (a NaN input can carry any payload) only ends the spin at its limit.
-  const bool word_wait = nframes == 1 && !o->amplitude_spectrum && !o->power_spectrum && !o->complex_real && !o->complex_imag;
-  constexpr uint64_t kSent = ~(uint64_t)0;
+  const bool word_wait = nframes == 1 && !(fields & mgx::kSpectrumFieldBits);  // (wait_output_words)
   // MGX_FLAG_RESIDENT: the resident workgroup serves one-frame calls for the mgx_outputs fields; one that asks
-  // for mel_bands takes the launch below (which ends the resident one first, as any other launch does)
-  const bool res = p->resident && nframes == 1 && !o->mel_bands;
-  if (word_wait && !res) {
-    for (int k = 0; k < MGX_NUM_SCALARS; ++k)
-      if (o->scalars[k]) memset(h.scalars[k], 0xFF, ss);
-    if (o->loudness_specific) memset(h.loudness_specific, 0xFF, nb * 4);
-    if (o->mfcc) memset(h.mfcc, 0xFF, nc * 4);
-    if (o->mel_bands) memset(h.mel_bands, 0xFF, nm * 4);
-    std::atomic_thread_fence(std::memory_order_release);
-  }
+  // for a later field (mel_bands) takes the launch below (which ends the resident one first, as any other launch does)
+  const bool res = p->resident && nframes == 1 && !(fields & ~mgx::kGroupFieldBits);
   if (res) {
     rc = resident_request(p, o, d, p->done_seq);
     if (rc) return rc;
   } else {
+    if (word_wait) preset_output_words(p, fields, h);
     // (one frame: also handed over in the kernel arguments, read there by the kernels that take it)
-    rc = extract_device_impl(p, static_cast<const float*>(din), nframes, stride, &d, p->s_comp, word_wait ? nullptr : ddone,
-                             nframes == 1 ? p->h_in : nullptr);
+    LaunchOpts opt;
+    opt.done = word_wait ? nullptr : p->d_done_map;
+    opt.inline_frame = nframes == 1 ? p->h_in : nullptr;
+    rc = extract_device_impl(p, static_cast<const float*>(p->d_in_map), nframes, stride, &d, p->s_comp, opt);
     if (rc) {
       (void)hipStreamSynchronize(p->s_comp);
       return rc;
     }
+    rc = word_wait ? wait_output_words(p, fields, h) : wait_done_word(p);
+    if (rc) return rc;
   }
-  if (!res && word_wait) {
-    const auto t0 = std::chrono::steady_clock::now();
-    bool late = false;
-    unsigned spins = 0;
-    auto wait_word = [&](const void* w, size_t bytes) {
-      for (;; ++spins) {
-        const uint64_t v = bytes == 8 ? __atomic_load_n(static_cast<const uint64_t*>(w), __ATOMIC_ACQUIRE)
-                                      : (uint64_t)__atomic_load_n(static_cast<const uint32_t*>(w), __ATOMIC_ACQUIRE);
-        if (v != (bytes == 8 ? kSent : (uint64_t)0xFFFFFFFFu)) return;
-        __builtin_ia32_pause();
-        if (late || ((spins & 63) == 63 && std::chrono::steady_clock::now() - t0 > std::chrono::microseconds(kSmallSpinUs))) {
-          late = true;
-          return;
-        }
-      }
-    };
-    for (int k = 0; k < MGX_NUM_SCALARS; ++k)
-      if (o->scalars[k]) wait_word(h.scalars[k], ss);
-    for (size_t i = 0; o->loudness_specific && i < nb; ++i) wait_word(h.loudness_specific + i, 4);
-    for (size_t i = 0; o->mfcc && i < nc; ++i) wait_word(h.mfcc + i, 4);
-    for (size_t i = 0; o->mel_bands && i < nm; ++i) wait_word(h.mel_bands + i, 4);
-    if (late) {  // a busy device, a failed launch, or an output equal to the preset: the stream decides
-      e = hipStreamSynchronize(p->s_comp);
-      if (e != hipSuccess) return hip_fail(e, "small host batch");
-    }
-  }
-  // The last wave of the launch releases done_seq to the host word after every output store is
-  // visible (kernels.hip done_signal): polling it returns ~9 us sooner than waiting for the
-  // stream (tools/ubench/small_latency.hip). Past 20 ms (a busy device) the wait blocks on the
-  // stream instead, which also reports a failed launch. The spin pauses the core between reads
-  // (a contended device leaves N-API worker threads waiting here) and gives up after kSmallSpinUs.
-  if (!res && !word_wait) {
-    const auto t0 = std::chrono::steady_clock::now();
-    bool seen = false;
-    for (unsigned spins = 0;; ++spins) {
-      if (__atomic_load_n(p->h_done, __ATOMIC_ACQUIRE) == p->done_seq) {
-        seen = true;
-        break;
-      }
-      __builtin_ia32_pause();
-      if ((spins & 63) == 63 && std::chrono::steady_clock::now() - t0 > std::chrono::microseconds(kSmallSpinUs)) break;
-    }
-    if (!seen) {
-      e = hipStreamSynchronize(p->s_comp);
-      if (e != hipSuccess) return hip_fail(e, "small host batch");
-      if (__atomic_load_n(p->h_done, __ATOMIC_ACQUIRE) != p->done_seq)
-        return fail(MGX_E_DEVICE, "small host batch: the launch completed without its completion word");
-    }
-  }
-  for (int k = 0; k < MGX_NUM_SCALARS; ++k)
-    if (o->scalars[k]) memcpy(o->scalars[k], h.scalars[k], nframes * ss);
-  if (o->loudness_specific) memcpy(o->loudness_specific, h.loudness_specific, nframes * nb * 4);
-  if (o->mfcc) memcpy(o->mfcc, h.mfcc, nframes * nc * 4);
-  if (o->mel_bands) memcpy(o->mel_bands, h.mel_bands, nframes * nm * 4);
-  if (o->amplitude_spectrum) memcpy(o->amplitude_spectrum, h.amplitude_spectrum, nframes * L * 4);
-  if (o->power_spectrum) memcpy(o->power_spectrum, h.power_spectrum, nframes * L * 4);
-  if (o->complex_real) memcpy(o->complex_real, h.complex_real, nframes * (size_t)n * 4);
-  if (o->complex_imag) memcpy(o->complex_imag, h.complex_imag, nframes * (size_t)n * 4);
+  for (int i = 0; i < mgx::kOutFields; ++i)
+    if ((fields >> i) & 1u) memcpy(mgx::out_field(*o, i), mgx::out_field(h, i), nframes * mgx::out_field_bytes(p->d, i));
   return MGX_OK;
 }
 
@@ -1484,16 +1464,15 @@ struct GatherChunks {
 template <typename Fill>
 int extract_host_chunked(mgx_plan* p, uint64_t nframes, uint64_t stride, uint64_t chunk_max, const mgx::Outputs* o, Fill fill,
                          const GatherChunks* gc = nullptr) {
-  const int n = p->n, L = p->L;
-  const size_t ss = p->d.scalar_f64 ? 8 : 4;
-  const size_t nb = mgx::kBark, nc = p->d.num_mfcc_coeffs, nm = p->d.num_mel_bands;
+  const int n = p->n;
+  const uint32_t fields = mgx::out_requested(*o);
   // device bytes per frame for the requested outputs
-  const size_t per = out_bytes_per_frame(p, o);
+  const size_t per = out_bytes_per_frame(p, fields);
   const uint64_t chunk = std::min<uint64_t>(nframes, chunk_max);
   // (the slot in whole frames of N floats: the chunk's span, at most kHostChunk frames' worth)
   uint64_t slot_frames = ((chunk - 1) * stride + (uint64_t)n + (uint64_t)n - 1) / (uint64_t)n;
   if (gc) slot_frames = (*std::max_element(gc->span.begin(), gc->span.end()) + (uint64_t)n - 1) / (uint64_t)n;
-  int rc = ensure_host_staging(p, slot_frames, per * chunk + 21 * 256);
+  int rc = ensure_host_staging(p, slot_frames, per * chunk + mgx::kOutLayoutSlack);
   if (rc) return rc;
   const uint64_t nch = gc ? gc->lo.size() : (nframes + chunk - 1) / chunk;
   // chunk i's first frame and count
@@ -1511,23 +1490,17 @@ int extract_host_chunked(mgx_plan* p, uint64_t nframes, uint64_t stride, uint64_
   for (uint64_t i = 0; i < nch && e == hipSuccess; ++i) {
     const int sl = (int)(i & 1);
     const uint64_t f0 = first(i), cnt = count(i);
-    mgx::Outputs d{};
-    size_t off = 0;
-    auto take = [&](size_t bytes) { unsigned char* q = p->s_out[sl] + off; off += (bytes + 255) / 256 * 256; return q; };
-    for (int k = 0; k < MGX_NUM_SCALARS; ++k) d.scalars[k] = o->scalars[k] ? take(cnt * ss) : nullptr;
-    d.loudness_specific = o->loudness_specific ? reinterpret_cast<float*>(take(cnt * nb * 4)) : nullptr;
-    d.mfcc = o->mfcc ? reinterpret_cast<float*>(take(cnt * nc * 4)) : nullptr;
-    d.amplitude_spectrum = o->amplitude_spectrum ? reinterpret_cast<float*>(take(cnt * L * 4)) : nullptr;
-    d.power_spectrum = o->power_spectrum ? reinterpret_cast<float*>(take(cnt * L * 4)) : nullptr;
-    d.complex_real = o->complex_real ? reinterpret_cast<float*>(take(cnt * n * 4)) : nullptr;
-    d.complex_imag = o->complex_imag ? reinterpret_cast<float*>(take(cnt * n * 4)) : nullptr;
-    d.mel_bands = o->mel_bands ? reinterpret_cast<float*>(take(cnt * nm * 4)) : nullptr;
+    uint64_t off[mgx::kOutFields];
+    mgx::out_layout(p->d, fields, cnt, off);
+    const mgx::Outputs d = mgx::out_at(p->s_out[sl], off);
     // extraction of chunk i: after its frames arrived and chunk i-2's outputs left the slot
     e = hipStreamWaitEvent(p->s_comp, p->ev_loaded[sl], 0);
     if (e == hipSuccess && i >= 2) e = hipStreamWaitEvent(p->s_comp, p->ev_back[sl], 0);
     if (e != hipSuccess) break;
     const GatherLaunch g{p->s_starts[sl], gc ? gc->span[i] : 0};
-    rc = extract_device_impl(p, p->s_frames[sl], cnt, stride, &d, p->s_comp, nullptr, nullptr, nullptr, gc ? &g : nullptr);
+    LaunchOpts opt;
+    opt.gather = gc ? &g : nullptr;
+    rc = extract_device_impl(p, p->s_frames[sl], cnt, stride, &d, p->s_comp, opt);
     if (rc) return fail_sync(rc);
     e = hipEventRecord(p->ev_done[sl], p->s_comp);
     // chunk i+1's frames into the other slot once chunk i-1's extraction has read them
@@ -1540,18 +1513,12 @@ int extract_host_chunked(mgx_plan* p, uint64_t nframes, uint64_t stride, uint64_
     }
     // chunk i's outputs back to the caller's arrays
     if (e == hipSuccess) e = hipStreamWaitEvent(p->s_copy, p->ev_done[sl], 0);
-    auto back = [&](void* host, const void* dev, size_t bytes) {
-      return host ? hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, p->s_copy) : hipSuccess;
-    };
-    for (int k = 0; k < MGX_NUM_SCALARS && e == hipSuccess; ++k)
-      if (o->scalars[k]) e = back(static_cast<unsigned char*>(o->scalars[k]) + f0 * ss, d.scalars[k], cnt * ss);
-    if (e == hipSuccess && o->loudness_specific) e = back(o->loudness_specific + f0 * nb, d.loudness_specific, cnt * nb * 4);
-    if (e == hipSuccess && o->mfcc) e = back(o->mfcc + f0 * nc, d.mfcc, cnt * nc * 4);
-    if (e == hipSuccess && o->amplitude_spectrum) e = back(o->amplitude_spectrum + f0 * L, d.amplitude_spectrum, cnt * L * 4);
-    if (e == hipSuccess && o->power_spectrum) e = back(o->power_spectrum + f0 * L, d.power_spectrum, cnt * L * 4);
-    if (e == hipSuccess && o->complex_real) e = back(o->complex_real + f0 * n, d.complex_real, cnt * n * 4);
-    if (e == hipSuccess && o->complex_imag) e = back(o->complex_imag + f0 * n, d.complex_imag, cnt * n * 4);
-    if (e == hipSuccess && o->mel_bands) e = back(o->mel_bands + f0 * nm, d.mel_bands, cnt * nm * 4);
+    for (int k = 0; k < mgx::kOutFields && e == hipSuccess; ++k) {
+      if (!((fields >> k) & 1u)) continue;
+      const uint64_t fb = mgx::out_field_bytes(p->d, k);
+      e = hipMemcpyAsync(static_cast<unsigned char*>(mgx::out_field(*o, k)) + f0 * fb, mgx::out_field(d, k), cnt * fb,
+                         hipMemcpyDeviceToHost, p->s_copy);
+    }
     if (e == hipSuccess) e = hipEventRecord(p->ev_back[sl], p->s_copy);
   }
   if (e == hipSuccess) e = hipStreamSynchronize(p->s_copy);
@@ -1588,9 +1555,8 @@ int mgx_extract_signal_host(mgx_plan* p, const float* samples, uint64_t num_samp
 
 int mgx_extract_host_ex(mgx_plan* p, const float* samples, uint64_t num_samples, uint32_t hop, const mgx_outputs* outputs,
                         const mgx_aux_outputs* aux) {
-  if (!p || !outputs) return fail(MGX_E_INVALID_ARGUMENT, "NULL plan or outputs");
   mgx::Outputs x;
-  int rc = make_outputs(outputs, aux, &x);
+  int rc = make_outputs(p, outputs, aux, &x);
   if (rc) return rc;
   const mgx::Outputs* const o = &x;
   uint64_t nframes = 0;
@@ -1598,8 +1564,7 @@ int mgx_extract_host_ex(mgx_plan* p, const float* samples, uint64_t num_samples,
   if (rc) return rc;
   if (nframes == 0) return MGX_OK;
   if (!samples) return fail(MGX_E_INVALID_ARGUMENT, "samples is NULL");
-  if ((o->complex_real == nullptr) != (o->complex_imag == nullptr))
-    return fail(MGX_E_INVALID_ARGUMENT, "complex_real and complex_imag must be given together");
+  if ((rc = check_outputs(x))) return rc;
   const int n = p->n;
   const uint64_t h = hop;
   if (nframes <= p->small_max) {
@@ -1624,9 +1589,8 @@ int mgx_extract_host_ex(mgx_plan* p, const float* samples, uint64_t num_samples,
 
 int mgx_extract_gather_host(mgx_plan* p, const float* samples, uint64_t num_samples, const uint64_t* starts, uint64_t nframes,
                             const mgx_outputs* outputs, const mgx_aux_outputs* aux) {
-  if (!p || !outputs) return fail(MGX_E_INVALID_ARGUMENT, "NULL plan or outputs");
   mgx::Outputs x;
-  int rc = make_outputs(outputs, aux, &x);
+  int rc = make_outputs(p, outputs, aux, &x);
   if (rc) return rc;
   const mgx::Outputs* const o = &x;
   if (nframes == 0) return MGX_OK;
@@ -1634,8 +1598,7 @@ int mgx_extract_gather_host(mgx_plan* p, const float* samples, uint64_t num_samp
   if (!samples) return fail(MGX_E_INVALID_ARGUMENT, "samples is NULL");
   const uint64_t n = (uint64_t)p->n;
   if (num_samples < n) return fail(MGX_E_INVALID_ARGUMENT, "%llu samples hold no buffer of %d", (unsigned long long)num_samples, p->n);
-  if ((o->complex_real == nullptr) != (o->complex_imag == nullptr))
-    return fail(MGX_E_INVALID_ARGUMENT, "complex_real and complex_imag must be given together");
+  if ((rc = check_outputs(x))) return rc;
   // (the host sees the table: a start whose buffer leaves the samples is refused here, before any copy)
   for (uint64_t f = 0; f < nframes; ++f)
     if (starts[f] > num_samples - n)
@@ -1767,8 +1730,7 @@ int extract_host_pcm_impl(mgx_plan* p, const void* pcm, uint64_t pcm_bytes, uint
   const uint32_t bps = sample_bytes(format);
   if (!bps) return fail(MGX_E_INVALID_ARGUMENT, "unknown PCM format %u", format);
   if (channels == 0 || channel >= channels) return fail(MGX_E_INVALID_ARGUMENT, "channel %u of %u", channel, channels);
-  if ((o->complex_real == nullptr) != (o->complex_imag == nullptr))
-    return fail(MGX_E_INVALID_ARGUMENT, "complex_real and complex_imag must be given together");
+  if (int rc = check_outputs(*o)) return rc;
   const int n = p->n;
   const uint64_t nframes = sample_frames < (uint64_t)n ? 0 : (sample_frames - (uint64_t)n) / hop + 1;
   if (nframes == 0) return MGX_OK;
@@ -1820,10 +1782,10 @@ int mgx_extract_signal_host_pcm(mgx_plan* p, const void* pcm, uint64_t pcm_bytes
 int mgx_extract_host_pcm_ex(mgx_plan* p, const void* pcm, uint64_t pcm_bytes, uint64_t sample_frames, uint32_t format,
                             uint32_t channels, uint32_t channel, uint32_t hop, const mgx_outputs* o,
                             const mgx_aux_outputs* aux) {
-  if (!p || !o) return fail(MGX_E_INVALID_ARGUMENT, "NULL plan or outputs");
-  if (hop == 0) return fail(MGX_E_INVALID_ARGUMENT, "hop is 0 (a hop of at least one sample)");
+  // (a NULL plan or outputs is reported before the hop, the hop before the auxiliary struct)
+  if (p && o && hop == 0) return fail(MGX_E_INVALID_ARGUMENT, "hop is 0 (a hop of at least one sample)");
   mgx::Outputs x;
-  const int rc = make_outputs(o, aux, &x);
+  const int rc = make_outputs(p, o, aux, &x);
   if (rc) return rc;
   return extract_host_pcm_impl(p, pcm, pcm_bytes, sample_frames, format, channels, channel, hop, &x);
 }

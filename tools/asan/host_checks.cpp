@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "../../include/meyda_gpu.h"
+#include "../../meyda_amd/csrc/out_fields.h"
 
 static int failures = 0;
 #define CHECK(c)                                                         \
@@ -219,6 +220,88 @@ static void frame_starts() {
   printf("frame starts: %ld tables\n", n);
 }
 
+// The table of output fields (meyda_amd/csrc/out_fields.h, included as the library includes it): its accessor
+// against the structs' members by name, its layout against the public mgx_packed_layout (itself pinned by
+// tests/test_group_host.py against independent arithmetic), its field sets.
+static void out_fields() {
+  using namespace mgx;
+  // field access: exactly one pointer member per field, where the public struct has it
+  mgx_outputs named[kGroupFields];
+  memset(named, 0, sizeof named);
+  void* const mark = &named;
+  for (int i = 0; i < MGX_NUM_SCALARS; ++i) named[i].scalars[i] = mark;
+  named[13].loudness_specific = static_cast<float*>(mark);
+  named[14].mfcc = static_cast<float*>(mark);
+  named[15].amplitude_spectrum = static_cast<float*>(mark);
+  named[16].power_spectrum = static_cast<float*>(mark);
+  named[17].complex_real = static_cast<float*>(mark);
+  named[18].complex_imag = static_cast<float*>(mark);
+  for (int i = 0; i < kOutFields; ++i) {
+    Outputs o;
+    memset(&o, 0, sizeof o);
+    out_field(o, i) = mark;
+    void* members[sizeof(Outputs) / sizeof(void*)];
+    static_assert(sizeof members == sizeof o, "Outputs holds pointers only");
+    memcpy(members, &o, sizeof o);
+    int set = 0;
+    for (void* m : members) set += m != nullptr;
+    CHECK(set == 1);
+    CHECK(out_field(static_cast<const Outputs&>(o), i) == mark);
+    if (i < kGroupFields) CHECK(memcmp(&o, &named[i], sizeof(mgx_outputs)) == 0);
+    else CHECK(o.mel_bands == mark && i == 19);
+    // field sets: the requested bits round-trip through the accessor
+    CHECK(out_requested(o) == 1u << i);
+    const char* why = nullptr;
+    CHECK((outputs_ok(o, &why) == MGX_OK) == (i != 17 && i != 18));
+  }
+  Outputs pair{}, none{}, mel{};
+  pair.complex_real = pair.complex_imag = mel.mel_bands = static_cast<float*>(mark);
+  const char* why = nullptr;
+  CHECK(outputs_ok(pair, &why) == MGX_OK && outputs_ok(none, &why) == MGX_OK && why == nullptr);
+  pair.complex_imag = nullptr;
+  CHECK(outputs_ok(pair, &why) == MGX_E_INVALID_ARGUMENT && why && strstr(why, "given together"));
+  CHECK(out_requested(none) == 0 && (out_requested(mel) & kGroupFieldBits) == 0);  // mel_bands alone: resident key 0
+  // layout against the public call
+  std::mt19937 rng(0x6F757466);
+  long n = 0;
+  for (uint32_t N : {256u, 512u, 1024u, 2048u})
+    for (uint32_t f64 : {0u, 1u})
+      for (const auto& mc : {std::pair<uint32_t, uint32_t>{1, 1}, {26, 13}, {40, 20}, {64, 32}})
+        for (uint64_t F : {1ull, 7ull, 513ull, 65536ull}) {
+          mgx_plan_desc d;
+          mgx_plan_desc_init(&d);
+          d.buffer_size = N;
+          d.scalar_f64 = f64;
+          d.num_mel_bands = mc.first;
+          d.num_mfcc_coeffs = mc.second;
+          std::vector<uint32_t> masks;
+          for (int b = 0; b < 18; ++b) masks.push_back(1u << b);
+          masks.push_back(MGX_OUT_ALL_MASK);
+          for (int r = 0; r < 64; ++r) masks.push_back(rng() & MGX_OUT_ALL_MASK);
+          for (uint32_t mask : masks) {
+            const uint32_t bits = mask | ((mask >> 17) & 1u) << 18;  // (MGX_OUT_COMPLEX_SPECTRUM: fields 17 and 18)
+            uint64_t want[kGroupFields], got[kOutFields], with[kOutFields];
+            const uint64_t total = mgx_packed_layout(&d, mask, F, want);
+            CHECK(out_layout(d, bits, F, got, kGroupFields) == total);
+            CHECK(memcmp(want, got, sizeof want) == 0);
+            // with field 19: last, 256-byte aligned, its own rounded bytes more
+            const uint64_t all = out_layout(d, bits | 1u << 19, F, with);
+            CHECK(memcmp(want, with, sizeof want) == 0);
+            CHECK(with[19] == total && with[19] % 256 == 0);
+            CHECK(all == total + (4ull * mc.first * F + 255) / 256 * 256);
+            CHECK(out_layout(d, bits, F, with) == total && with[19] == UINT64_MAX);
+            // the pointers built from it
+            unsigned char* const base = reinterpret_cast<unsigned char*>(uintptr_t(1) << 40);
+            const Outputs at = out_at(base, got, kGroupFields);
+            for (int i = 0; i < kOutFields; ++i)
+              CHECK(out_field(at, i) == (i < kGroupFields && got[i] != UINT64_MAX ? base + got[i] : nullptr));
+            ++n;
+          }
+        }
+  static_assert(kOutLayoutSlack == 21 * 256, "one rounding per field, and a spare");
+  printf("out fields: %ld layouts\n", n);
+}
+
 static void validation() {
   mgx_plan* p = nullptr;
   CHECK(mgx_plan_create(nullptr, &p) == MGX_E_INVALID_ARGUMENT);
@@ -244,6 +327,7 @@ int main() {
   host_tables();
   arithmetic();
   frame_starts();
+  out_fields();
   validation();
   printf("host_checks: %s (%d failures)\n", failures ? "FAILED" : "ok", failures);
   return failures ? 1 : 0;
