@@ -114,7 +114,7 @@ typedef enum mgx_info_type { MGX_TYPE_NUMBER = 0, MGX_TYPE_ARRAY = 1, MGX_TYPE_M
 
 typedef struct mgx_plan_desc {
   uint32_t struct_size;      /* = sizeof(mgx_plan_desc) */
-  uint32_t buffer_size;      /* N: power of two; the GPU path supports 256 <= N <= 2048 */
+  uint32_t buffer_size;      /* N: power of two; the GPU path supports 256 <= N <= 4096 */
   double sample_rate;        /* audioContext.sampleRate */
   uint32_t window;           /* mgx_window (Meyda.windowingFunction) */
   uint32_t precision;        /* mgx_precision */
@@ -136,7 +136,9 @@ typedef struct mgx_plan_desc {
                                         double products, Math.log in double, the sequential DCT (MFCC
                                         bit-identical wherever the power spectrum is; slower, see
                                         DESIGN.md §5.3). Default off: segmented-scan mel sums, float32
-                                        hardware log, the matrix-core DCT, all within 1e-5. */
+                                        hardware log, the matrix-core DCT, all within 1e-5. Up to
+                                        buffer_size 2048: at 4096 mgx_plan_create refuses the flag
+                                        (MGX_E_UNSUPPORTED), whatever the plan's precision and mode. */
 #define MGX_FLAG_RESIDENT 4u        /* the real-time path (src/meyda.js:69-91, one buffer per call): one-frame
                                         mgx_extract_host calls are served by one workgroup that stays on the
                                         device between calls, polling a mailbox in pinned host memory, instead
@@ -149,8 +151,8 @@ typedef struct mgx_plan_desc {
                                         synchronisation made meanwhile waits for that end. mgx_plan_create
                                         pays the path's one-time set-up (~13 ms: pinned buffers, a hardware
                                         queue, one warm-up call), not the first real-time call. Faithful per-buffer
-                                        plans without MGX_FLAG_MFCC_REFERENCE only (MGX_E_UNSUPPORTED
-                                        otherwise). */
+                                        plans without MGX_FLAG_MFCC_REFERENCE only, up to buffer_size 2048
+                                        (MGX_E_UNSUPPORTED otherwise: at 4096 the flag is refused). */
 
 typedef struct mgx_plan mgx_plan;
 
@@ -199,7 +201,7 @@ int mgx_plan_get_desc(const mgx_plan* plan, mgx_plan_desc* out_desc);
  * Asynchronous on `stream` (hipStream_t or NULL). The launch uses per-stream device scratch,
  * one set per distinct stream the plan launches on: the scalar features' windows (5 KB per
  * resident wave, ~20 MB), for a plan with MGX_FLAG_MFCC_REFERENCE the power-row ring of its mel
- * chains (~2 KB x 8 per resident wave, tens of MB), and at N = 2048 the tail pool's ticket
+ * chains (~2 KB x 8 per resident wave, tens of MB), and at N >= 2048 the tail pool's ticket
  * counter (8 bytes). The whole set is allocated by the first call on its stream, whatever that
  * call's size or outputs (hipMalloc, which may synchronise the device: make one untimed call per
  * stream first, outside any stream capture), and kept until mgx_plan_destroy, which waits for
@@ -212,7 +214,11 @@ int mgx_extract_device(mgx_plan* plan, const float* frames, uint64_t num_frames,
  * written. Up to 512 frames run one launch over plan-owned pinned host memory
  * (a single frame of N <= 1024 samples inside the kernel arguments, or with
  * MGX_FLAG_RESIDENT handed to the plan's resident workgroup); larger
- * batches stage through plan-owned device buffers in chunks. A one-frame call
+ * batches stage through plan-owned device buffers in chunks: two slots of 65,536
+ * frames up to N = 2048, and of the same bytes (512 MiB each) above it, 32,768
+ * frames at N = 4096. (The pinned buffers of the one-launch path grow with N and the
+ * outputs asked for: 512 frames at N = 4096 with every spectrum are 8 MiB of samples
+ * and 24 MiB of outputs.) A one-frame call
  * without spectrum outputs may return while the tail of its launch still runs
  * on the plan's stream: later calls on the plan are ordered after it, and
  * mgx_plan_destroy waits for it. */
@@ -303,7 +309,8 @@ int mgx_extract_signal_device(mgx_plan* plan, const float* samples, uint64_t num
  * samples. Each sample crosses PCIe once per chunk it belongs to, not once per buffer: a
  * chunk of K buffers copies its span of (K - 1) * hop + N samples into the staging slot of
  * the dense path and is extracted there at stride hop, so neighbouring chunks re-send only
- * the N - hop samples they share. The slots stay the dense path's (65,536 * N floats): for
+ * the N - hop samples they share. The slots stay the dense path's (65,536 * N floats up to
+ * N = 2048, 32,768 * N at 4096: a chunk holds at most that many buffers at any hop): for
  * hop > N a chunk holds as many buffers as its span allows there (fewer, down to one for a
  * hop beyond the slot), and a batch small enough for the one-launch path (512 buffers)
  * gathers its buffers densely into the pinned input buffer instead. */
@@ -387,8 +394,8 @@ int mgx_extract_gather_device(mgx_plan* plan, const float* samples, uint64_t num
  * index). Up to 512 buffers are gathered densely into the pinned input buffer and run the one-launch path
  * of mgx_extract_host (one buffer: the kernel-argument frame, or the resident workgroup of a
  * MGX_FLAG_RESIDENT plan). Larger batches go through the two staging slots of the dense path in chunks: a
- * chunk is the longest run of consecutive buffers of at most 65,536 whose span, max(start) + N - min(start),
- * fits a slot (65,536 * N floats; one buffer always fits). The span crosses PCIe once per chunk, with the
+ * chunk is the longest run of consecutive buffers of at most 65,536 (32,768 at N = 4096) whose span,
+ * max(start) + N - min(start), fits a slot (that many times N floats; one buffer always fits). The span crosses PCIe once per chunk, with the
  * chunk's starts (8 bytes per buffer) beside it. Sorted starts -- what mgx_signals_frame_starts gives -- fill
  * their chunks; starts in arbitrary order are served correctly, but every jump of more than a slot ends a
  * chunk, down to one buffer per chunk. */

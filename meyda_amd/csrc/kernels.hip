@@ -63,13 +63,24 @@ constexpr int rev_bits(int x, int bits) {
 // (the register part an immediate offset). Chosen per N by a search over the LDS bank
 // rule of ds_write2_b64 / ds_read2_b64 (4 groups of 16 lanes, banks (a/4) mod 32): the
 // exchanges then take the conflict-free minimum of LDS cycles at N = 512, 1024 and 2048.
+// N = 4096 by the same rule, reasoned rather than searched: 16 consecutive lanes differ in location
+// bits 7..10 when pass 0's layout writes (rev6(lane) << 5) and in bits 0..3 at every other access, so
+// loc >> 7 brings bits 7..10 down to the 16 entry residues (2048's loc >> 6 would leave bit 10 out: 2-way
+// on that write) and adds nothing to bits 0..3: 16 distinct bank pairs per lane group at every access.
 template <int N>
 __host__ __device__ constexpr int phys(int loc) {
   return N == 256 ? loc + 2 * (loc >> 4) + (loc >> 6)
        : N == 512 ? loc + 4 * (loc >> 4) + (loc >> 6)
        : N == 1024 ? loc + 2 * (loc >> 4) + (loc >> 7)
+       : N == 4096 ? loc + (loc >> 7)
        : loc + (loc >> 6);
 }
+
+// Padding of the prefix row (pd below): one double per 2^kPdShift entries. Per 16 up to N = 2048; at
+// N = 4096 (R = 32 entries per lane) per 32: lane l's run then starts at entry 33 l, 16 distinct residues
+// for 16 consecutive lanes, where 34 l (one per 16) has 8 -- and the row is 64 entries shorter.
+template <int N>
+constexpr int kPdShift = N == 4096 ? 5 : 4;
 
 template <int N>
 struct Geo {
@@ -88,7 +99,10 @@ struct Geo {
   // N = 256 fits 6 waves (<= 80 VGPRs; measured 2.5 % faster than 5); at N = 512 a bound of
   // 5 waves measured slower than 4 until the LDS twiddles took the passes' global loads out
   // (81 VGPRs then, 3.9 % faster than 4 waves at 98).
-  static constexpr int WPE = N <= 256 ? 6 : N <= 512 ? 5 : N <= 1024 ? 4 : 3;
+  // N = 4096: LDS allows 2 workgroups per CU (SLOT_PHYS below), i.e. 2 waves per SIMD and up to 256
+  // registers: the frame's 64 sample and 64 window registers, then the 64 of the 32 slots beside their
+  // f64 butterflies (the compile-time resource report of the instances: profiles/n4096.txt).
+  static constexpr int WPE = N <= 256 ? 6 : N <= 512 ? 5 : N <= 1024 ? 4 : N <= 2048 ? 3 : 2;
   // Slot buffer entries (8 bytes): the padded exchange image, the natural-order half
   // spectrum X[0..L] (complex output), the padded prefix row (pd) and the mel scratch.
   static constexpr int cmax(int a, int b) { return a > b ? a : b; }
@@ -96,7 +110,12 @@ struct Geo {
   // needs, against the 11.5 KB table it replaces; the workgroup keeps 5 per CU with the
   // LDS twiddles)
   static constexpr int SLOT_PHYS =
-      cmax(cmax(cmax(phys<N>(L - 1) + 1, L + 1), cmax(L + 2 * (L >> 5) + 1, R * 64 + 2)), N == 512 ? 5 * 72 : 0);
+      cmax(cmax(cmax(phys<N>(L - 1) + 1, L + 1), cmax(L + (L >> kPdShift<N>) + 1, R * 64 + 2)), N == 512 ? 5 * 72 : 0);
+  // N = 4096: 2113 entries (the prefix row), 4 x 2113 x 8 = 67,616 bytes of slot buffers per workgroup;
+  // with the 16 records (8,320), the constants (256) and a 13 x 26 DCT table (1,664) 77,856 bytes: two
+  // workgroups in the CU's 160 KB (81,920 each) with 4,064 to spare, and still two at 13 x 64 (3,328).
+  // Nothing else fits that margin -- pass 1's twiddle image alone (TwLds: 5 stages of 64 mixed and up to
+  // 480 generic entries) is 18 KB -- so TW_LDS stays off at this size and the passes read the plan tables.
   // Moment sums through an LDS transpose (5 rows of 64 doubles per wave, row stride 72 so
   // the rows read together fall in different banks) rather than 5 DPP wave sums: measured
   // faster at every N (at 2048 once it ran in the slot buffer: a table of its own cost 3 waves
@@ -138,9 +157,11 @@ struct Geo {
   // (profiles/r03_group_sync.txt): 1024 +0.0 % (time-only -3.8 %), 256 -0.1 %; the all-feature
   // launch at 512 +1.6 % and at 2048 (3 waves per SIMD) +2.3 %, so those keep none.
   static constexpr int GROUP_SYNC = (N == 1024 || N == 256) ? 2 : 0;
-  static constexpr bool LPREMAT = N == 2048;  // measured: N = 2048 1 % faster, N = 256 7 % slower
+  // (N = 4096 takes 2048's settings of PF, WIN_REG, BLIM_REG, GROUP_SYNC and LPREMAT, none measured apart
+  // yet: a frame prefetch or a register window would each hold 64 more VGPRs for the launch)
+  static constexpr bool LPREMAT = N >= 2048;  // measured: N = 2048 1 % faster, N = 256 7 % slower
   static constexpr int MIX = 1;  // bfly_mixed_tame (form 0 was faster at N = 1024 at 128 live VGPRs)
-  static_assert(R >= 2 && (R & (R - 1)) == 0, "N must be a power of two in [256, 2048]");
+  static_assert(R >= 2 && (R & (R - 1)) == 0, "N must be a power of two in [256, 4096]");
 };
 
 // Location bits of pass p: register bits [0, m) drive location bits [q0, q0+m); the
@@ -238,14 +259,15 @@ struct TwLdsF {
 // the slot buffer: lane l reads the row (ds_read2_b64) and writes the prefix
 // (ds_write2_b64) as R consecutive entries; both instructions serve 16 consecutive lanes
 // per LDS cycle with banks (a/4) mod 32 (MI355X_MICROARCH.md §LDS). The prefix row's 1
-// double of padding per 16 gives those 16 lanes 16 distinct bank pairs at every R (the
+// double of padding per 16 gives those 16 lanes 16 distinct bank pairs at every R up to 16 (R = 32: kPdShift; the
 // former 2 per 32 left 2-way conflicts: 32 extra LDS cycles per frame at N = 1024,
 // SQ_LDS_BANK_CONFLICT). The amplitude row keeps 4 floats per 64 (2-way on its reads): 2
 // per 32 removes those too but changed the surrounding code generation and measured
 // 2.5 % slower; the LDS is not what bounds the kernel.
 __device__ __forceinline__ int pa(int k) { return k + 4 * (k >> 6); }
 __device__ __forceinline__ int pa_inv(int k) { return k - 4 * (k / 68); }  // pa(b) = 68 (b >> 6) + (b & 63)
-__device__ __forceinline__ int pd(int d) { return d + (d >> 4); }
+template <int N>
+__device__ __forceinline__ int pd(int d) { return d + (d >> kPdShift<N>); }
 
 
 // Wave priority (s_setprio) in the frame's low-ILP sections: a wave in an LDS round trip or a
@@ -284,6 +306,11 @@ struct KlTab {
     else w[r >> 1] = (uint32_t)v;
   }
   __device__ __forceinline__ int operator()(int r) const { return (int)((w[r >> 1] >> (16 * (r & 1))) & 0xFFFFu); }
+  // N = 4096 does not keep the table (kFrameBins): its 16 registers live across the frame loop were spilled
+  // -- unpacked ahead of the loop, 32 of them -- and read back from scratch one by one, a vector-memory wait
+  // per slot twice per frame. Each frame loads the lane's 32 bins instead (frame_phase1), in one burst at
+  // immediate offsets of one lane address, behind the amplitudes' arithmetic.
+  static constexpr bool kFrameBins = N == 4096;
 };
 
 // A frame's samples: read once and never again. A batch larger than the 256 MiB MALL cannot stay
@@ -1176,6 +1203,11 @@ __device__ __forceinline__ void frame_phase1(KArgs* ap, float (&x)[Geo<N>::CH], 
   using PG = PassGeo<N>;
   constexpr int L = G::L, R = G::R, CH = G::CH;
   constexpr bool TWL = Geo<N>::TW_LDS;
+  // N = 4096: the lane id through an empty asm in every frame, so that no lane address derived from it (the
+  // rows' LDS positions, the outputs' offsets) is formed ahead of the frame loop and held across it: with
+  // every one of the 256 registers in use those were kept in scratch and read back where the frame uses
+  // them, a vector-memory wait each.
+  if constexpr (N == 4096) lane = opaque(lane);
   float* amp = reinterpret_cast<float*>(buf);  // the frame's amplitude row, once the FFT is done
   double* pbuf = reinterpret_cast<double*>(buf);
 
@@ -1331,6 +1363,14 @@ __device__ __forceinline__ void frame_phase1(KArgs* ap, float (&x)[Geo<N>::CH], 
     }
     MGX_MARK(fft_done);
     MGX_STAMP(4);
+    // (KlTab<N>::kFrameBins, N = 4096: the spectrum bin of each of the lane's slots, loaded per frame)
+    constexpr bool kFrameBins = KlTab<N>::kFrameBins;
+    int kbin[kFrameBins ? R : 1];
+    if constexpr (kFrameBins) {
+      const auto kt = gbl(ap->t.klist) + lpf[G::NPASS - 1];
+#pragma unroll
+      for (int r = 0; r < R; ++r) kbin[r] = kt[PG::rpart(G::NPASS - 1, r)];
+    }
     prio_hi<32>();
     const bool want_cplx = ap->out.complex_real != nullptr;
     // src/meyda.js:104-114: |X_k| for k < N/2, rounded to float32.
@@ -1379,7 +1419,8 @@ __device__ __forceinline__ void frame_phase1(KArgs* ap, float (&x)[Geo<N>::CH], 
           // kl holds pa(bin). (opaque: the complex output's 2R addresses, derived here, were otherwise
           // hoisted out of the frame loop and held in R VGPRs for the whole launch -- spilled at N = 2048
           // -- by every launch, with or without a complex output)
-          buf[pa_inv(opaque(kl(r)))] = v[r];
+          if constexpr (kFrameBins) buf[kbin[r]] = v[r];
+          else buf[pa_inv(opaque(kl(r)))] = v[r];
         }
       }
       wave_sync();
@@ -1397,7 +1438,10 @@ __device__ __forceinline__ void frame_phase1(KArgs* ap, float (&x)[Geo<N>::CH], 
     }
     prio_hi<2>();
 #pragma unroll
-    for (int r = 0; r < R; ++r) amp[kl(r)] = ar[r];  // kl(r) = pa(bin)
+    for (int r = 0; r < R; ++r) {  // kl(r) = pa(bin)
+      if constexpr (kFrameBins) amp[pa(kbin[r])] = ar[r];
+      else amp[kl(r)] = ar[r];
+    }
   }
   wave_sync();
 
@@ -1570,7 +1614,7 @@ __device__ __forceinline__ void frame_phase1(KArgs* ap, float (&x)[Geo<N>::CH], 
     double pk = excl;  // P(R lane + jj), accumulated again rather than kept (registers)
 #pragma unroll
     for (int jj = 0; jj < R; ++jj) {
-      pbuf[pd(R * lane + jj)] = pk;
+      pbuf[pd<N>(R * lane + jj)] = pk;
       cnt += __popcll(__ballot(pk <= thr));
       pk += (double)av[jj];
     }
@@ -1944,7 +1988,7 @@ __device__ void stage_tables(KArgs* ap, unsigned char* base) {
   constexpr size_t at = LY::kc_off + 128;
   int* klim = reinterpret_cast<int*>(base);
   // the bark limits as byte offsets of their entries in the padded prefix row (band sums)
-  if (threadIdx.x >= 64 && threadIdx.x < 64 + kBark + 1) klim[threadIdx.x - 64] = 8 * pd(gbl(ap->t.bblim)[threadIdx.x - 64]);
+  if (threadIdx.x >= 64 && threadIdx.x < 64 + kBark + 1) klim[threadIdx.x - 64] = 8 * pd<N>(gbl(ap->t.bblim)[threadIdx.x - 64]);
   if constexpr (Geo<N>::TW_LDS && FAITH && !LITERAL) {  // the tame passes' twiddles (TwLds)
     stage_twiddles<N, 1, 0>(reinterpret_cast<double2*>(base + (LY::twl_off - at)), gbl(ap->t.tw), gbl(ap->t.twm));
   } else if constexpr (Geo<N>::TW_LDS && !FAITH && !LITERAL) {  // the fast precision's (TwLdsF)
@@ -2275,7 +2319,7 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(RES ? 
   // The workgroup's LDS tables, from the plan's image (lds_image_kernel) in one pass of 16-byte loads,
   // issued before the first frame's: a one-frame launch (the real-time path) waits for one round trip of
   // table loads, behind which its frame's loads are already in flight, instead of a chain of them.
-  constexpr int kImgK = 4;  // chunks per thread in the first pass (16 KB: every plan's image at N <= 2048)
+  constexpr int kImgK = 4;  // chunks per thread in the first pass (16 KB: every plan's image; N = 4096 stages no twiddles)
   const auto img = gbl(static_cast<const u32x4*>(img_p));
   u32x4* const limg = reinterpret_cast<u32x4*>(smem + LY::kc_off + 128);
   u32x4 iv[kImgK];
@@ -2698,7 +2742,7 @@ hipError_t launch_n(const KernelArgs& a, int grid, hipStream_t stream, const flo
                        lds, stream, a);
     return hipGetLastError();
   }
-  if constexpr (FAITH && !LITERAL && !CHAIN) {
+  if constexpr (N <= kResidentMaxN && FAITH && !LITERAL && !CHAIN) {
     if (res) {  // MGX_FLAG_RESIDENT: the one-workgroup server of one-frame requests
       hipLaunchKernelGGL((extract_kernel<N, FAITH, LITERAL, SUB, LIGHT, NOTIME, CHAIN, false, true>), dim3(1), dim3(kThreads), lds,
                          stream, a);
@@ -2802,6 +2846,7 @@ size_t lds_image_bytes(int n, int ncoef, int nfilt) {
     case 512: return lds_image_bytes_n<512>(ncoef, nfilt);
     case 1024: return lds_image_bytes_n<1024>(ncoef, nfilt);
     case 2048: return lds_image_bytes_n<2048>(ncoef, nfilt);
+    case 4096: return lds_image_bytes_n<4096>(ncoef, nfilt);
     default: return 0;
   }
 }
@@ -2812,6 +2857,7 @@ hipError_t launch_lds_image(int n, int precision, int mode, const KernelArgs& a,
     case 512: return launch_image_n<512>(precision, mode, a, image, stream);
     case 1024: return launch_image_n<1024>(precision, mode, a, image, stream);
     case 2048: return launch_image_n<2048>(precision, mode, a, image, stream);
+    case 4096: return launch_image_n<4096>(precision, mode, a, image, stream);
     default: return hipErrorInvalidValue;
   }
 }
@@ -2822,6 +2868,7 @@ size_t extract_lds_bytes(int n, int ncoef, int nfilt, bool chain) {
     case 512: return Lds<512>::bytes(ncoef, nfilt);
     case 1024: return Lds<1024>::bytes(ncoef, nfilt);
     case 2048: return Lds<2048>::bytes(ncoef, nfilt);
+    case 4096: return Lds<4096>::bytes(ncoef, nfilt);
     default: return 0;
   }
 }
@@ -2832,6 +2879,7 @@ int frames_per_batch(int n) {
     case 512: return Geo<512>::FB;
     case 1024: return Geo<1024>::FB;
     case 2048: return Geo<2048>::FB;
+    case 4096: return Geo<4096>::FB;
     default: return 0;
   }
 }
@@ -2842,6 +2890,7 @@ int extract_blocks_per_cu(int n, int precision, int mode, int ncoef, int nfilt, 
     case 512: return occupancy_prec<512>(precision, mode, ncoef, nfilt, chain);
     case 1024: return occupancy_prec<1024>(precision, mode, ncoef, nfilt, chain);
     case 2048: return occupancy_prec<2048>(precision, mode, ncoef, nfilt, false);
+    case 4096: return occupancy_prec<4096>(precision, mode, ncoef, nfilt, false);
     default: return 0;
   }
 }
@@ -2857,6 +2906,8 @@ hipError_t launch_extract(int n, int precision, int mode, const KernelArgs& a, i
     case 512: return launch_prec<512>(precision, mode, a, grid, stream, inline_frame, resident, gather);
     case 1024: return launch_prec<1024>(precision, mode, a, grid, stream, inline_frame, resident, gather);
     case 2048: return launch_prec<2048>(precision, mode, a, grid, stream, nullptr, resident, gather);
+    // (no inline frame, as at 2048; no resident form: mgx_plan_create refuses MGX_FLAG_RESIDENT at 4096)
+    case 4096: return resident ? hipErrorInvalidValue : launch_prec<4096>(precision, mode, a, grid, stream, nullptr, false, gather);
     default: return hipErrorInvalidValue;
   }
 }

@@ -28,6 +28,9 @@ constexpr int kRecBytes = 520;  // sizeof(FrameRec) (kernels.hip)
 constexpr int kRecLmOff = 248;  // offsetof(FrameRec, lm)
 constexpr int kChainPairMaxMel = 31;  // paired batches keep two halves of FrameRec::lm (flag at 31)
 constexpr int kChainMaxN = 2048;
+// MGX_FLAG_RESIDENT up to here: the resident wait keeps two reads of the mailbox in flight (2 N / 64 8-byte
+// words per lane, kernels.hip res_wait), 512 registers at N = 4096; plan.cpp refuses the flag above it.
+constexpr int kResidentMaxN = 2048;
 constexpr int kChainSkip = 1 << 30;  // FrameRec.zcr flag bit: a non-finite frame keeps its phase-1 mel sums
 // dwords of one lane's mel record for R bins per lane (R weights, R slot bytes, R keep bytes,
 // 8 bytes of scan keeps and slots), padded to whole 16-byte loads

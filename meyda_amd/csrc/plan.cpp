@@ -46,7 +46,10 @@ namespace {
 using mgx::fail;
 using mgx::hip_fail;
 
-const uint64_t kHostChunk = 65536;              // frames per host-staging chunk
+const uint64_t kHostChunk = 65536;              // frames per host-staging chunk (up to N = 2048: host_chunk)
+// A staging slot never exceeds the bytes it has at N = 2048 (512 MiB, two of them): above it a chunk holds
+// as many frames fewer, 32,768 at N = 4096 (host_chunk below).
+const uint64_t kHostSlotFloats = kHostChunk * 2048;
 // Host batches of at most this many frames (a real-time buffer, or a streaming batch of K
 // buffers) skip the device staging: the frames are copied into plan-owned pinned host memory
 // that the kernel reads over PCIe itself, and it writes the features back there (no DMA copies,
@@ -635,8 +638,15 @@ int mgx_plan_create(const mgx_plan_desc* d, mgx_plan** out) {
   int rc = validate(d);
   if (rc) return rc;
   const int n = (int)d->buffer_size;
-  if (n < 256 || n > 2048)
-    return fail(MGX_E_UNSUPPORTED, "buffer_size %d: the GPU path supports 256..2048", n);
+  if (n < 256 || n > 4096)
+    return fail(MGX_E_UNSUPPORTED, "buffer_size %d: the GPU path supports 256..4096", n);
+  // The two plan kinds without a 4096 form, refused here (ahead of the device, as the range) rather than
+  // dropped: the reference-order chains' control word holds row offsets up to N = kChainMaxN (chain_schedule),
+  // and the resident wait's two mailbox reads in flight do not fit the registers above kResidentMaxN.
+  if ((d->flags & MGX_FLAG_MFCC_REFERENCE) && n > mgx::kChainMaxN)
+    return fail(MGX_E_UNSUPPORTED, "MGX_FLAG_MFCC_REFERENCE: not at buffer_size %d (up to %d)", n, mgx::kChainMaxN);
+  if ((d->flags & MGX_FLAG_RESIDENT) && n > mgx::kResidentMaxN)
+    return fail(MGX_E_UNSUPPORTED, "MGX_FLAG_RESIDENT: not at buffer_size %d (up to %d)", n, mgx::kResidentMaxN);
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(MGX_E_NO_DEVICE, "no HIP device available");
   if (d->device < 0 || d->device >= ndev) return fail(MGX_E_INVALID_ARGUMENT, "device %d out of range (%d devices)", d->device, ndev);
@@ -926,7 +936,7 @@ namespace {
 
 // A stream's scratch set (mgx_plan::ChainRing), the whole set at once: the scalar windows (kScalWords words
 // for each wave of the largest grid), the reference-order MFCC's power-row ring (2 FPW x N/2 floats per wave;
-// MGX_FLAG_MFCC_REFERENCE plans) and the tail pool's ticket counter (N = 2048 plans), zeroed in stream order
+// MGX_FLAG_MFCC_REFERENCE plans) and the tail pool's ticket counter (N >= 2048 plans), zeroed in stream order
 // before the first launch. On failure nothing is kept and the next call on the stream tries again.
 int add_stream_scratch(mgx_plan* p, void* stream) {
   mgx_plan::ChainRing r{};
@@ -946,7 +956,7 @@ int add_stream_scratch(mgx_plan* p, void* stream) {
     e = hipMalloc(reinterpret_cast<void**>(&r.rows), (size_t)p->grid_cap * 4 * 2 * fpw * (size_t)p->L * sizeof(float));
     if (e != hipSuccess) { r.rows = nullptr; undo(); return hip_fail(e, "hipMalloc(mel chain rows)"); }
   }
-  if (p->n == 2048) {
+  if (p->n >= 2048) {
     e = hipMalloc(reinterpret_cast<void**>(&r.pool_ctr), sizeof(uint64_t));
     if (e != hipSuccess) r.pool_ctr = nullptr;
     else e = hipMemsetAsync(r.pool_ctr, 0, sizeof(uint64_t), (hipStream_t)stream);
@@ -1063,8 +1073,9 @@ int extract_device_impl(mgx_plan* p, const float* frames, uint64_t nframes, uint
   if (a.chain_groups > 0 && a.need_spectrum && a.need_mel) a.chain_rows = ring->rows;
   // The tail pool at N = 2048 (the kernels without a frame prefetch; not the reference-order ones): the
   // last pool_pct percent of the groups taken by ticket (kernels.hip; 15 %: -2.7 % per launch against the static
-  // shares alone, outputs identical, profiles/r05_tail_pool.txt).
-  if (p->n == 2048 && !(a.chain_groups > 0 && a.need_spectrum && a.need_mel) && p->pool_pct > 0) {
+  // shares alone, outputs identical, profiles/r05_tail_pool.txt). N = 4096, without a prefetch either, takes
+  // 2048's setting.
+  if (p->n >= 2048 && !(a.chain_groups > 0 && a.need_spectrum && a.need_mel) && p->pool_pct > 0) {
     // (nb here counts groups of 16 frames, the kernel's groups; the pool's tickets are batches of 4 frames)
     const uint64_t ng_all = nb, pg = ng_all * (uint64_t)p->pool_pct / 100;
     if (pg > 0 && pg < ng_all && ring->pool_ctr) {
@@ -1104,7 +1115,7 @@ int extract_device_impl(mgx_plan* p, const float* frames, uint64_t nframes, uint
 
 namespace {
 
-// Host batches: `nframes` frames through two plan-owned device slots, kHostChunk frames at a
+// Host batches: `nframes` frames through two plan-owned device slots, host_chunk frames at a
 // time. `fill(f0, cnt, slot, stream)` enqueues the copy of frames [f0, f0 + cnt) into slot
 // `slot` (p->s_frames[slot]) on the copy stream. Chunk i+1's host-to-device copy runs while
 // chunk i is extracted on the compute stream; chunk i's outputs then return to the host
@@ -1442,13 +1453,16 @@ int extract_host_small(mgx_plan* p, uint64_t nframes, uint64_t stride, const mgx
   return MGX_OK;
 }
 
-// The frames of a chunk, for a signal cut at `hop` (signal_chunk_frames(p, n) = kHostChunk for dense
-// frames): a chunk of K frames occupies (K - 1) hop + N floats of its slot, and a slot holds kHostChunk N,
-// so up to hop = N a chunk keeps its kHostChunk frames, and a larger hop (samples skipped) gets as many
+// Dense frames per chunk: kHostChunk while kHostChunk N floats fit a slot (N <= 2048), then as many as do.
+uint64_t host_chunk(const mgx_plan* p) { return std::min<uint64_t>(kHostChunk, kHostSlotFloats / (uint64_t)p->n); }
+
+// The frames of a chunk, for a signal cut at `hop` (signal_chunk_frames(p, n) = host_chunk(p) for dense
+// frames): a chunk of K frames occupies (K - 1) hop + N floats of its slot, and a slot holds host_chunk N,
+// so up to hop = N a chunk keeps its host_chunk frames, and a larger hop (samples skipped) gets as many
 // frames as still fit, one at least.
 uint64_t signal_chunk_frames(const mgx_plan* p, uint64_t hop) {
-  const uint64_t n = (uint64_t)p->n;
-  return hop <= n ? kHostChunk : std::max<uint64_t>(1, (kHostChunk * n - n) / hop + 1);
+  const uint64_t n = (uint64_t)p->n, hc = host_chunk(p);
+  return hop <= n ? hc : std::max<uint64_t>(1, (hc * n - n) / hop + 1);
 }
 
 // The chunks of a gather call (mgx_extract_gather_host): chunk i is frames [bounds[i], bounds[i + 1]), whose
@@ -1611,16 +1625,16 @@ int mgx_extract_gather_host(mgx_plan* p, const float* samples, uint64_t num_samp
       for (uint64_t f = 0; f < nframes; ++f) memcpy(dst + f * n, samples + starts[f], (size_t)n * sizeof(float));
       return MGX_OK;
     });
-  // Chunks: the longest runs of consecutive buffers of at most kHostChunk whose span, max start + N - min start,
-  // fits a slot of the dense path (kHostChunk N floats; one buffer always does). Sorted starts no further apart
+  // Chunks: the longest runs of consecutive buffers of at most host_chunk whose span, max start + N - min start,
+  // fits a slot of the dense path (host_chunk N floats; one buffer always does). Sorted starts no further apart
   // than N fill their chunks; any other order is served, in as many chunks as its jumps make.
   GatherChunks gc;
   std::vector<uint64_t> rel(nframes);  // every start less its chunk's lowest: what the chunk's launch reads
-  const uint64_t slot = kHostChunk * n;
+  const uint64_t hc = host_chunk(p), slot = hc * n;
   uint64_t longest = 0;
   for (uint64_t f0 = 0; f0 < nframes;) {
     uint64_t lo = starts[f0], hi = starts[f0], f1 = f0 + 1;
-    for (; f1 < nframes && f1 - f0 < kHostChunk; ++f1) {
+    for (; f1 < nframes && f1 - f0 < hc; ++f1) {
       const uint64_t l = std::min(lo, starts[f1]), h = std::max(hi, starts[f1]);
       if (h - l + n > slot) break;
       lo = l;

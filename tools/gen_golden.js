@@ -22,6 +22,11 @@
 //     For config C4 we evaluate the reference's mfcc source text in a vm
 //     context with that one literal changed to 40 (in memory only). Those
 //     vectors are labelled "reference-algorithm, numFilters substituted".
+//
+// usage: gen_golden.js            N = 512, 1024, 2048 into tests/golden/ and its manifest.json
+//        gen_golden.js --n4096    N = 4096 alone, into tests/golden/N4096/ with a manifest of its own
+//                                 (tests/golden/N4096/manifest.json): the same families with fewer frames,
+//                                 every file within the committed-file limit; nothing else is touched
 'use strict';
 const fs = require('fs');
 const path = require('path');
@@ -235,6 +240,7 @@ function concat(Type, arrs) {
 }
 
 function main() {
+  const only4096 = process.argv.includes('--n4096');
   fs.mkdirSync(OUT, { recursive: true });
   const wavs = {};
   for (const s of ['sound1', 'sound2', 'sound3']) wavs[s] = readWav(REF + 'audio/' + s + '.wav');
@@ -251,9 +257,10 @@ function main() {
   for (const s of Object.keys(wavs)) {
     manifest.wav[s] = { samples: wavs[s].pcm.length, dataOffset: wavs[s].dataOffset, fmt: wavs[s].fmt };
   }
-  const plan = { 512: [32, 16], 1024: [32, 16], 2048: [16, 8] };
-  for (const N of [512, 1024, 2048]) {
-    const [nNoise, nWav] = plan[N];
+  // [noise frames, frames per wav source, frames of the hamming / literal variants]
+  const plan = { 512: [32, 16, 8], 1024: [32, 16, 8], 2048: [16, 8, 8], 4096: [8, 4, 4] };
+  for (const N of only4096 ? [4096] : [512, 1024, 2048]) {
+    const [nNoise, nWav, nVar] = plan[N];
     const M = makeMeyda(N);
     const frames = [], labels = [];
     noiseFrames(N, nNoise).forEach((x, f) => { frames.push(x); labels.push('noise:' + f); });
@@ -272,14 +279,15 @@ function main() {
     recs.forEach((r, f) => SCALARS.forEach((k, j) => { scal[f * SCALARS.length + j] = r[k]; }));
     const nCx = Math.min(F, 16);
 
-    // hamming window variant on the first 8 noise frames + the edges
-    const hamIdx = [0, 1, 2, 3, 4, 5, 6, 7].concat(labels.map((l, i) => (l.startsWith('edge:') ? i : -1)).filter((i) => i >= 0));
+    // hamming window variant on the first 8 noise frames (4 at N = 4096) + the edges
+    const first = Array.from({ length: nVar }, (_, i) => i);
+    const hamIdx = first.concat(labels.map((l, i) => (l.startsWith('edge:') ? i : -1)).filter((i) => i >= 0));
     const hamRecs = hamIdx.map((i) => runIntended(M, N, frames[i], 'hamming'));
     const hamScal = new Float64Array(hamIdx.length * SCALARS.length);
     hamRecs.forEach((r, f) => SCALARS.forEach((k, j) => { hamScal[f * SCALARS.length + j] = r[k]; }));
 
-    // literal (snapshot) path on the first 8 frames: no FFT per buffer
-    const litIdx = [0, 1, 2, 3, 4, 5, 6, 7];
+    // literal (snapshot) path on the first 8 frames (4 at N = 4096): no FFT per buffer
+    const litIdx = first;
     const M2 = makeMeyda(N);
     const lit = litIdx.map((i) => runLiteral(M2, frames[i]));
 
@@ -323,6 +331,6 @@ function main() {
     };
     console.log('N=' + N + ': ' + F + ' frames');
   }
-  fs.writeFileSync(path.join(OUT, 'manifest.json'), JSON.stringify(manifest, null, 1) + '\n');
+  fs.writeFileSync(path.join(OUT, only4096 ? 'N4096/manifest.json' : 'manifest.json'), JSON.stringify(manifest, null, 1) + '\n');
 }
 main();
