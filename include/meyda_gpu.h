@@ -29,6 +29,9 @@
  *   mgx_extract_gather_* the same over buffers that start where a    src/meyda.js:69-91 (one source,
  *   mgx_signals_frame_starts  table says: every buffer of every     one buffer per call)
  *                        clip of a corpus in one launch
+ *   mgx_summarize_*      the gather calls with every clip's rows     no counterpart, as with the groups:
+ *                        pooled on the device: mean, variance, min   the per-clip pooling loop of a host
+ *                        and max of each output over a clip          application over Meyda.get's results
  *   mgx_group_*          several devices, RCCL gather of the        src/meyda.js:17-97 (one plan
  *                        per-frame records to the root device       per device), :69-91 (buffers
  *                                                                   are independent: shardable)
@@ -401,6 +404,84 @@ int mgx_extract_gather_device(mgx_plan* plan, const float* samples, uint64_t num
  * chunk, down to one buffer per chunk. */
 int mgx_extract_gather_host(mgx_plan* plan, const float* samples, uint64_t num_samples, const uint64_t* starts,
                             uint64_t num_frames, const mgx_outputs* outputs, const mgx_aux_outputs* aux);
+
+/* ---- Per-signal summaries: mean, variance, min, max of each output over a clip -------------
+ * Replaces, in a host application, the loop that pools the per-buffer results of a clip into a clip
+ * descriptor (mean and variance of the MFCCs and the scalars; the mean spectrum is the long-term average
+ * spectrum). The reference has no counterpart, as with the groups. Both calls are mgx_extract_gather_device /
+ * _host with a pooling step behind them: a segmented reduction over the per-frame records on the device, keyed
+ * by frame_offsets (num_signals + 1 entries, as mgx_signals_frame_starts writes them): signal s owns rows
+ * [frame_offsets[s], frame_offsets[s + 1]) of every output.
+ *
+ * The statistics are a fixed list, not features (MGX_NUM_FEATURES and the name table are as they were). */
+typedef enum mgx_stat {
+  MGX_STAT_MEAN = 0,
+  MGX_STAT_VARIANCE = 1,  /* population variance (ddof = 0) */
+  MGX_STAT_MIN = 2,
+  MGX_STAT_MAX = 3,
+  MGX_NUM_STATS = 4
+} mgx_stat;
+
+/* The summaries of a call, one array per pooled field: field[(s * MGX_NUM_STATS + k) * w + c] is statistic k of
+ * column c of signal s, w being the field's floats per frame (1 for a scalar). Every value is a float64, whatever
+ * scalar_f64 says. A NULL pointer: the field is not pooled (and, unless asked for per frame, not computed). The
+ * complex spectrum has no summary. Size-checked as mgx_aux_outputs is, so it can grow.
+ *
+ * The values of a column are taken as float64 (every float32 converts exactly). Mean and variance are float64
+ * accumulations within 4 F u max|x| and 16 F u R^2 of the exact ones (F rows, u = 2^-53, R = max - min); the
+ * variance is never negative, and exactly 0 for a constant column and for a signal of one buffer; min and max
+ * are the column's by value. A column with a NaN gives NaN in all four; one with +-Infinity and no NaN (the
+ * melBands of a silent buffer) gives mean, min and max as the sum and the comparisons give them and a NaN
+ * variance; a signal without buffers gives NaN in all four. A signal's summary is a function of its rows alone:
+ * each signal's rows are cut, from its first row, into blocks of 256; a block is summed in ascending row order
+ * as (sum of (x - K), sum of (x - K)^2, min, max), K being the signal's first row, and the blocks are added in
+ * ascending order. No atomics, and so the same bits from the device call, the host call, a repeated call, any
+ * grid, and wherever the host path's chunks end. */
+typedef struct mgx_summary_outputs {
+  uint32_t struct_size;  /* = sizeof(mgx_summary_outputs); anything else: MGX_E_INVALID_ARGUMENT */
+  uint32_t reserved;     /* 0 */
+  double* scalars[MGX_NUM_SCALARS];  /* each num_signals x MGX_NUM_STATS */
+  double* loudness_specific;         /* num_signals x MGX_NUM_STATS x num_bark_bands */
+  double* mfcc;                      /* ... x num_mfcc_coeffs */
+  double* amplitude_spectrum;        /* ... x N/2 */
+  double* power_spectrum;            /* ... x N/2 */
+  double* mel_bands;                 /* ... x num_mel_bands */
+} mgx_summary_outputs;
+
+/* The bytes of `workspace` a mgx_summarize_device call with these arguments needs: the per-frame arrays of the
+ * fields that are pooled but not requested per frame (outputs and aux, either may be NULL), the table as the
+ * kernels read it, the signals' shifts K and the block partials; a multiple of 256, non-decreasing in num_frames,
+ * and 0 when there is nothing to keep (no pooled field, no signal, or no buffer). Host only (no device). */
+int mgx_summary_workspace_bytes(const mgx_plan* plan, const mgx_outputs* outputs, const mgx_aux_outputs* aux,
+                                const mgx_summary_outputs* summary, uint64_t num_frames, uint64_t num_signals,
+                                uint64_t* bytes);
+
+/* mgx_extract_gather_device, then the summaries. Every pointer is a device pointer, frame_offsets included;
+ * asynchronous on `stream`. outputs and aux may be NULL or hold NULL fields; every per-frame field they name
+ * is written exactly as mgx_extract_gather_device writes it, bit for bit. Per-frame fields that are pooled
+ * but not named, and the partial results, live in `workspace` (256-byte aligned, workspace_bytes of at least
+ * mgx_summary_workspace_bytes, else MGX_E_INVALID_ARGUMENT): the call keeps no host-side state and allocates
+ * nothing, so it is capturable into a graph under the first-call rule of mgx_extract_device. The host cannot
+ * see the table, so the kernels read it as its running maximum limited to num_frames -- entry s as
+ * min(max(frame_offsets[0..s]), num_frames): an offset above num_frames is num_frames, an entry below an
+ * earlier one gives an empty signal, no row beyond num_frames is read, and nothing outside the num_signals + 1
+ * entries is. Every summary array named is written whole (NaN for a signal without buffers, so for every signal
+ * when num_frames is 0). num_signals = 0 is the gather call. */
+int mgx_summarize_device(mgx_plan* plan, const float* samples, uint64_t num_samples, const uint64_t* starts,
+                         uint64_t num_frames, const uint64_t* frame_offsets, uint64_t num_signals,
+                         const mgx_outputs* outputs, const mgx_aux_outputs* aux,
+                         const mgx_summary_outputs* summary, void* workspace, uint64_t workspace_bytes, void* stream);
+
+/* mgx_extract_gather_host, then the summaries: host pointers throughout; returns when everything is written.
+ * The table is checked before any copy: it must be non-decreasing with its last entry at most num_frames
+ * (MGX_E_INVALID_ARGUMENT, the message names the index), as a start whose buffer leaves the samples is. The
+ * call goes through the staging slots of the chunked path whatever its size (not the one-launch path or the
+ * resident workgroup, which it ends as any launch does); each chunk's records are reduced where they lie on
+ * the device, a block that a chunk's end cuts going on in the next chunk from its stored state, so only the
+ * summaries cross back, plus the per-frame fields named in outputs and aux. */
+int mgx_summarize_host(mgx_plan* plan, const float* samples, uint64_t num_samples, const uint64_t* starts,
+                       uint64_t num_frames, const uint64_t* frame_offsets, uint64_t num_signals,
+                       const mgx_outputs* outputs, const mgx_aux_outputs* aux, const mgx_summary_outputs* summary);
 
 /* ---- Multi-device groups -------------------------------
  * Replaces nothing in the reference (single-threaded browser code); it exists because

@@ -15,6 +15,9 @@
  *   extractWav(plan, wavBytes, features[, channel]) / extractWavAsync(...)
  *                                        -> the features of every full buffer of a .wav file;
  *                                           the raw PCM is decoded on the device
+ *   summarizeGather(plan, samples, starts, frameOffsets, features) / summarizeGatherAsync(...)
+ *                                        -> { name: Float64Array(S x 4 x width) }: mean, variance, min, max
+ *                                           of each field over every signal's buffers (mgx_summarize_host)
  *   wavParse(wavBytes)                   -> { pcmFormat, channels, sampleRate, bitsPerSample, ... }
  *   hostTables(opts)                     -> { hanning, hamming, window, barkScale, barkLimits, melBins, dct }
  *   isPowerOfTwo(n), deviceCount(), featureNames(), featureInfo(name), abiVersion()
@@ -266,6 +269,13 @@ typedef struct {
   /* extractGather: `frames` is nsamples samples, buffer f starts at starts[f] (malloc'd, nframes entries) */
   uint64_t* starts;
   int gather;
+  /* summarizeGather: a gather job whose outputs are the signals' summaries (mgx_summary_outputs: per wanted
+   * field nsignals x MGX_NUM_STATS x width doubles); signal s owns buffers [frame_offsets[s], frame_offsets[s + 1])
+   * (malloc'd, nsignals + 1 entries). The per-frame rows stay on the device. */
+  int summary;
+  uint64_t* frame_offsets;
+  uint64_t nsignals;
+  mgx_summary_outputs sum;
   mgx_outputs out;
   mgx_aux_outputs aux;  /* melBands (SLOT_MEL): the job then makes the mgx_extract_*_ex call */
   /* The outputs are written straight into JS ArrayBuffers (napi_create_arraybuffer), held by
@@ -287,6 +297,8 @@ typedef struct {
 static void job_free_buffers(napi_env env, job* j) {
   free(j->starts);
   j->starts = NULL;
+  free(j->frame_offsets);
+  j->frame_offsets = NULL;
   for (int i = 0; i < NSLOTS; ++i)
     if (j->refs[i]) {
       napi_delete_reference(env, j->refs[i]);
@@ -317,6 +329,12 @@ static int parse_features(napi_env env, napi_value feats, job* j) {
     if (f < 0) {
       char msg[128];
       snprintf(msg, sizeof msg, "unknown feature '%s'", name);
+      napi_throw_type_error(env, NULL, msg);
+      return 0;
+    }
+    if (j->summary && (f == MGX_COMPLEX_SPECTRUM || f == MGX_BUFFER)) {
+      char msg[128];
+      snprintf(msg, sizeof msg, "'%s' has no summary", name);
       napi_throw_type_error(env, NULL, msg);
       return 0;
     }
@@ -473,13 +491,40 @@ static int job_prepare_gather(napi_env env, job* j, napi_value samples_v, napi_v
   return job_alloc(env, j, feats);
 }
 
-/* Wanted outputs for j->nframes frames. */
+/* summarizeGather(plan, samples, starts, frameOffsets, features): extractGather's inputs and the table of the
+ * signals' buffers (a Float64Array of nsignals + 1 offsets, as signalsFrameStarts returns it). */
+static int job_prepare_summary(napi_env env, job* j, napi_value samples_v, napi_value starts_v, napi_value offsets_v,
+                               napi_value feats) {
+  size_t count = 0;
+  j->summary = 1;
+  j->sum.struct_size = sizeof j->sum;
+  j->frame_offsets = u64_of_f64(env, offsets_v, "frameOffsets", &count);
+  if (!j->frame_offsets) return 0;
+  if (count < 1) {
+    napi_throw_range_error(env, NULL, "frameOffsets holds one entry more than there are signals");
+    return 0;
+  }
+  j->nsignals = count - 1;
+  return job_prepare_gather(env, j, samples_v, starts_v, feats);
+}
+
+/* Field i of a summary (the complex spectrum has none) */
+static void set_summary_field(mgx_summary_outputs* s, int i, double* p) {
+  double** const arrays[NSLOTS - SLOT_LOUD] = {&s->loudness_specific, &s->mfcc, &s->amplitude_spectrum, &s->power_spectrum,
+                                               NULL,                  NULL,     &s->mel_bands};
+  if (i < MGX_NUM_SCALARS) s->scalars[i] = p;
+  else if (arrays[i - SLOT_LOUD]) *arrays[i - SLOT_LOUD] = p;
+}
+
+/* Wanted outputs for j->nframes frames (a summary job: for j->nsignals signals). */
 static int job_alloc(napi_env env, job* j, napi_value feats) {
   if (!parse_features(env, feats, j)) return 0;
   j->aux.struct_size = sizeof j->aux;
   for (int i = 0; i < NSLOTS; ++i) {
     if (!j->want[i]) continue;
-    const size_t b = (size_t)j->nframes * field_bytes(&j->box->desc, i);
+    size_t b = (size_t)j->nframes * field_bytes(&j->box->desc, i);
+    if (j->summary)
+      b = (size_t)j->nsignals * MGX_NUM_STATS * sizeof(double) * (i < MGX_NUM_SCALARS ? 1 : field_bytes(&j->box->desc, i) / 4);
     j->bytes[i] = b;
     napi_value abv;
     void* data = NULL;
@@ -488,7 +533,8 @@ static int job_alloc(napi_env env, job* j, napi_value feats) {
       return 0;
     }
     j->bufs[i] = data;
-    set_field(&j->out, &j->aux, i, data);
+    if (j->summary) set_summary_field(&j->sum, i, (double*)data);
+    else set_field(&j->out, &j->aux, i, data);
   }
   return 1;
 }
@@ -574,7 +620,10 @@ static void job_run(job* j) {
     return;
   }
   const uint32_t n = j->box->desc.buffer_size;
-  if (j->gather)
+  if (j->summary)
+    j->rc = mgx_summarize_host(j->box->plan, j->frames, j->nsamples, j->starts, j->nframes, j->frame_offsets, j->nsignals, NULL,
+                               NULL, &j->sum);
+  else if (j->gather)
     j->rc = mgx_extract_gather_host(j->box->plan, j->frames, j->nsamples, j->starts, j->nframes, &j->out,
                                     j->want[SLOT_MEL] ? &j->aux : NULL);
   else if (j->box->group)
@@ -612,6 +661,14 @@ static napi_value job_result(napi_env env, job* j) {
       "perceptualSharpness"};
   napi_value obj;
   if (napi_create_object(env, &obj) != napi_ok) return NULL;
+  if (j->summary) {  /* every summary is float64: the same names, each nsignals x 4 x width */
+    static const char* arrays[NSLOTS - SLOT_LOUD] = {"loudness.specific", "mfcc", "amplitudeSpectrum", "powerSpectrum", NULL, NULL, "melBands"};
+    for (int i = 0; i < NSLOTS; ++i) {
+      const char* nm = i < MGX_NUM_SCALARS ? names[i] : arrays[i - SLOT_LOUD];
+      if (j->want[i] && nm) napi_set_named_property(env, obj, nm, typed(env, j, i, napi_float64_array, 8));
+    }
+    return obj;
+  }
   const int f64 = j->box->desc.scalar_f64;
   for (int i = 0; i < MGX_NUM_SCALARS; ++i)
     if (j->want[i]) napi_set_named_property(env, obj, names[i], typed(env, j, i, f64 ? napi_float64_array : napi_float32_array, f64 ? 8 : 4));
@@ -626,12 +683,13 @@ static napi_value job_result(napi_env env, job* j) {
 }
 
 /* kind: the input of an extraction job */
-enum { IN_FRAMES = 0, IN_WAV = 1, IN_SIGNAL = 2, IN_GATHER = 3 };
+enum { IN_FRAMES = 0, IN_WAV = 1, IN_SIGNAL = 2, IN_GATHER = 3, IN_SUMMARY = 4 };
 
 static int job_prepare_kind(napi_env env, job* j, int kind, size_t argc, napi_value* argv) {
   if (kind == IN_WAV) return job_prepare_wav(env, j, argv[1], argv[2], argc > 3 ? argv[3] : NULL, argc > 4 ? argv[4] : NULL);
   if (kind == IN_SIGNAL) return job_prepare_signal(env, j, argv[1], argv[2], argv[3]);
   if (kind == IN_GATHER) return job_prepare_gather(env, j, argv[1], argv[2], argv[3]);
+  if (kind == IN_SUMMARY) return job_prepare_summary(env, j, argv[1], argv[2], argv[3], argv[4]);
   return job_prepare(env, j, argv[1], argv[2]);
 }
 
@@ -639,8 +697,9 @@ static napi_value extract_common(napi_env env, napi_callback_info info, int kind
   size_t argc = 5;
   napi_value argv[5];
   CHECK(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
-  if (argc < (kind == IN_SIGNAL || kind == IN_GATHER ? 4u : 3u)) {
+  if (argc < (kind == IN_SUMMARY ? 5u : kind == IN_SIGNAL || kind == IN_GATHER ? 4u : 3u)) {
     napi_throw_type_error(env, NULL, kind == IN_WAV ? "extractWav(plan, wavBytes, features[, channel[, hop]])"
+                                   : kind == IN_SUMMARY ? "summarizeGather(plan, samples, starts, frameOffsets, features)"
                                    : kind == IN_GATHER ? "extractGather(plan, samples, starts, features)"
                                    : kind == IN_SIGNAL ? "extractSignal(plan, samples, hop, features)"
                                                        : "extract(plan, frames, features)");
@@ -761,6 +820,7 @@ static napi_value extract_sync(napi_env env, napi_callback_info info) { return e
 static napi_value extract_wav_sync(napi_env env, napi_callback_info info) { return extract_common(env, info, IN_WAV); }
 static napi_value extract_signal_sync(napi_env env, napi_callback_info info) { return extract_common(env, info, IN_SIGNAL); }
 static napi_value extract_gather_sync(napi_env env, napi_callback_info info) { return extract_common(env, info, IN_GATHER); }
+static napi_value summarize_gather_sync(napi_env env, napi_callback_info info) { return extract_common(env, info, IN_SUMMARY); }
 
 static void async_execute(napi_env env, void* data) {
   (void)env;
@@ -791,8 +851,9 @@ static napi_value extract_async_common(napi_env env, napi_callback_info info, in
   size_t argc = 5;
   napi_value argv[5];
   CHECK(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
-  if (argc < (kind == IN_SIGNAL || kind == IN_GATHER ? 4u : 3u)) {
+  if (argc < (kind == IN_SUMMARY ? 5u : kind == IN_SIGNAL || kind == IN_GATHER ? 4u : 3u)) {
     napi_throw_type_error(env, NULL, kind == IN_WAV ? "extractWavAsync(plan, wavBytes, features[, channel[, hop]])"
+                                   : kind == IN_SUMMARY ? "summarizeGatherAsync(plan, samples, starts, frameOffsets, features)"
                                    : kind == IN_GATHER ? "extractGatherAsync(plan, samples, starts, features)"
                                    : kind == IN_SIGNAL ? "extractSignalAsync(plan, samples, hop, features)"
                                                        : "extractAsync(plan, frames, features)");
@@ -826,6 +887,7 @@ static napi_value extract_async(napi_env env, napi_callback_info info) { return 
 static napi_value extract_wav_async(napi_env env, napi_callback_info info) { return extract_async_common(env, info, IN_WAV); }
 static napi_value extract_signal_async(napi_env env, napi_callback_info info) { return extract_async_common(env, info, IN_SIGNAL); }
 static napi_value extract_gather_async(napi_env env, napi_callback_info info) { return extract_async_common(env, info, IN_GATHER); }
+static napi_value summarize_gather_async(napi_env env, napi_callback_info info) { return extract_async_common(env, info, IN_SUMMARY); }
 
 /* signalsFrameStarts(lengths, bufferSize, hop): mgx_signals_frame_starts (host only) for signals stored one after
  * another; lengths: a Float64Array. Returns {starts, frameOffsets}, Float64Arrays. */
@@ -1054,6 +1116,8 @@ static napi_value init(napi_env env, napi_value exports) {
       {"signalFrames", NULL, signal_frames, NULL, NULL, NULL, napi_enumerable, NULL},
       {"extractGather", NULL, extract_gather_sync, NULL, NULL, NULL, napi_enumerable, NULL},
       {"extractGatherAsync", NULL, extract_gather_async, NULL, NULL, NULL, napi_enumerable, NULL},
+      {"summarizeGather", NULL, summarize_gather_sync, NULL, NULL, NULL, napi_enumerable, NULL},
+      {"summarizeGatherAsync", NULL, summarize_gather_async, NULL, NULL, NULL, napi_enumerable, NULL},
       {"signalsFrameStarts", NULL, signals_frame_starts, NULL, NULL, NULL, napi_enumerable, NULL},
       {"wavParse", NULL, wav_parse, NULL, NULL, NULL, napi_enumerable, NULL},
       {"hostTables", NULL, host_tables, NULL, NULL, NULL, napi_enumerable, NULL},

@@ -38,6 +38,7 @@ EXPORTS = ["mgx_plan_desc_init", "mgx_plan_create", "mgx_plan_destroy", "mgx_pla
            "mgx_extract_signal_host_pcm",
            "mgx_extract_device_ex", "mgx_extract_host_ex", "mgx_extract_host_pcm_ex",
            "mgx_signals_frame_starts", "mgx_extract_gather_device", "mgx_extract_gather_host",
+           "mgx_summary_workspace_bytes", "mgx_summarize_device", "mgx_summarize_host",
            "mgx_shard_range", "mgx_packed_layout", "mgx_comm_unique_id", "mgx_group_create",
            "mgx_group_create_rank", "mgx_group_create_loopback", "mgx_group_create_loopback_rccl", "mgx_group_destroy",
            "mgx_group_info", "mgx_group_comm_info", "mgx_group_extract_device", "mgx_group_extract_host"]
@@ -96,6 +97,20 @@ def _set_mel_bands(outputs, ptr):
     a.struct_size = ctypes.sizeof(AuxOutputs)
     a.mel_bands = ptr
     outputs.aux = a  # (a Python attribute of the Outputs instance: the C struct is unchanged)
+
+
+STATS = ["mean", "variance", "min", "max"]  # mgx_stat
+# the fields a summary pools (mgx_summary_outputs), by feature name; "loudness" stands for specific and total
+SUMMARY_FEATURES = SCALAR_NAMES + ["loudness", "mfcc", "amplitudeSpectrum", "powerSpectrum", "melBands"]
+
+
+class SummaryOutputs(ctypes.Structure):
+    """mgx_summary_outputs: per pooled field, num_signals x 4 x width float64 (the mgx_summarize_* calls)."""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("reserved", ctypes.c_uint32),
+                ("scalars", ctypes.c_void_p * NUM_SCALARS),
+                ("loudness_specific", ctypes.c_void_p), ("mfcc", ctypes.c_void_p),
+                ("amplitude_spectrum", ctypes.c_void_p), ("power_spectrum", ctypes.c_void_p),
+                ("mel_bands", ctypes.c_void_p)]
 
 
 class HostTables(ctypes.Structure):
@@ -182,6 +197,14 @@ def lib():
                                                 ctypes.c_uint64, ctypes.POINTER(Outputs), aux, ctypes.c_void_p]
         L.mgx_extract_gather_host.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p,
                                               ctypes.c_uint64, ctypes.POINTER(Outputs), aux]
+        summ = ctypes.POINTER(SummaryOutputs)
+        L.mgx_summary_workspace_bytes.argtypes = [ctypes.c_void_p, ctypes.POINTER(Outputs), aux, summ, ctypes.c_uint64,
+                                                  ctypes.c_uint64, u64p]
+        L.mgx_summarize_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64,
+                                           ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(Outputs), aux, summ,
+                                           ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p]
+        L.mgx_summarize_host.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64,
+                                         ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(Outputs), aux, summ]
         L.mgx_shard_range.argtypes = [ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, u64p, u64p]
         L.mgx_packed_layout.argtypes = [ctypes.POINTER(PlanDesc), ctypes.c_uint32, ctypes.c_uint64, u64p]
         L.mgx_packed_layout.restype = ctypes.c_uint64
@@ -419,6 +442,96 @@ class Plan:
         starts, frame_offsets = signals_frame_starts([x.size for x in signals], self.n, hop)
         samples = np.concatenate(signals) if signals else np.empty(0, np.float32)
         return self.extract_gather(samples, starts, features), frame_offsets
+
+    # ------------------------------------------------------- per-signal summaries
+    def _summary_outputs(self, S, features, alloc):
+        """A SummaryOutputs over arrays alloc(shape) (float64; .data_ptr() or .ctypes.data), and the arrays by
+        name: (S, 4, width) each, statistic k of signal s at [s, k] (STATS). "loudness" pools specific and total."""
+        widths = {"loudness.specific": NUM_BARK, "mfcc": self.desc.num_mfcc_coeffs, "amplitudeSpectrum": self.n // 2,
+                  "powerSpectrum": self.n // 2, "melBands": self.desc.num_mel_bands}
+        slots = {"loudness.specific": "loudness_specific", "mfcc": "mfcc", "amplitudeSpectrum": "amplitude_spectrum",
+                 "powerSpectrum": "power_spectrum", "melBands": "mel_bands"}
+        so = SummaryOutputs()
+        so.struct_size = ctypes.sizeof(SummaryOutputs)
+        out = {}
+        for f in features:
+            if f not in SUMMARY_FEATURES:
+                raise ValueError("%r has no summary" % (f,))
+            for name in (["loudness.specific", "loudness.total"] if f == "loudness" else [f]):
+                arr = alloc((S, len(STATS), widths.get(name, 1)))
+                out[name] = arr
+                ptr = arr.data_ptr() if hasattr(arr, "data_ptr") else arr.ctypes.data
+                if name in SCALAR_NAMES:
+                    so.scalars[SCALAR_NAMES.index(name)] = ptr
+                else:
+                    setattr(so, slots[name], ptr)
+        return out, so
+
+    def summary_workspace_bytes(self, outputs, summary, num_frames, num_signals):
+        """mgx_summary_workspace_bytes (host only): the device workspace of summarize_device with these arguments."""
+        b = ctypes.c_uint64()
+        check(lib().mgx_summary_workspace_bytes(self._h, ctypes.byref(outputs), _aux_ref(outputs), ctypes.byref(summary),
+                                                num_frames, num_signals, ctypes.byref(b)))
+        return b.value
+
+    def summarize_device(self, samples_ptr, num_samples, starts_ptr, num_frames, offsets_ptr, num_signals, outputs, summary,
+                         workspace_ptr, workspace_bytes, stream=None):
+        """mgx_summarize_device on device pointers (async on `stream`)."""
+        check(lib().mgx_summarize_device(self._h, ctypes.c_void_p(samples_ptr), num_samples, ctypes.c_void_p(starts_ptr),
+                                         num_frames, ctypes.c_void_p(offsets_ptr), num_signals, ctypes.byref(outputs),
+                                         _aux_ref(outputs), ctypes.byref(summary), ctypes.c_void_p(workspace_ptr),
+                                         workspace_bytes, ctypes.c_void_p(stream or 0)))
+
+    def summarize_gather_torch(self, samples, starts, frame_offsets, features, per_frame=(), stream=None):
+        """extract_gather_torch with every signal's rows pooled on the device: signal s owns rows
+        [frame_offsets[s], frame_offsets[s + 1]) (int64 CUDA tensors, or anything numpy turns into one). Returns
+        (summaries, rows): per pooled field a float64 CUDA tensor (S, 4, width) of mean, variance, min, max, and
+        the per-frame tensors of the features named in `per_frame`. The workspace is allocated here and handed to
+        torch's allocator again when this returns, which orders its reuse after the launch on torch's current
+        stream: a caller who passes another stream synchronises it before allocating again."""
+        import torch
+        assert samples.is_cuda and samples.dtype == torch.float32 and samples.is_contiguous() and samples.dim() == 1
+        dev = samples.device
+
+        def table(v):
+            if not torch.is_tensor(v):
+                v = torch.from_numpy(np.ascontiguousarray(v, dtype=np.uint64).view(np.int64)).to(dev)
+            assert v.is_cuda and v.dtype == torch.int64 and v.is_contiguous() and v.dim() == 1
+            return v
+        starts, frame_offsets = table(starts), table(frame_offsets)
+        F, S = starts.shape[0], frame_offsets.shape[0] - 1
+        rows, o = self.alloc_outputs(F, per_frame, device=dev)
+        summ, so = self._summary_outputs(S, features, lambda shape: torch.empty(shape, dtype=torch.float64, device=dev))
+        nbytes = self.summary_workspace_bytes(o, so, F, S)
+        ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+        if stream is None:
+            stream = torch.cuda.current_stream(dev).cuda_stream
+        self.summarize_device(samples.data_ptr(), samples.shape[0], starts.data_ptr(), F, frame_offsets.data_ptr(), S, o, so,
+                              ws.data_ptr(), nbytes, stream)
+        return summ, rows
+
+    def summarize_gather(self, samples, starts, frame_offsets, features, per_frame=()):
+        """Host numpy in / numpy out (mgx_summarize_host): (summaries, rows) as summarize_gather_torch gives them."""
+        samples = np.ascontiguousarray(samples, dtype=np.float32)
+        starts = np.ascontiguousarray(starts, dtype=np.uint64)
+        frame_offsets = np.ascontiguousarray(frame_offsets, dtype=np.uint64)
+        assert samples.ndim == 1 and starts.ndim == 1 and frame_offsets.ndim == 1 and frame_offsets.size >= 1
+        S = frame_offsets.size - 1
+        rows, o = self._host_outputs(starts.size, per_frame)
+        summ, so = self._summary_outputs(S, features, lambda shape: np.empty(shape, np.float64))
+        check(lib().mgx_summarize_host(self._h, samples.ctypes.data, samples.size, starts.ctypes.data, starts.size,
+                                       frame_offsets.ctypes.data, S, ctypes.byref(o), _aux_ref(o), ctypes.byref(so)))
+        return summ, rows
+
+    def summarize_signals(self, signals, hop, features, per_frame=()):
+        """A list of 1-D host signals in one call, pooled per signal: returns (summaries, frame_offsets), summaries
+        being {name: ndarray (S, 4, width)} of mean, variance, min, max (STATS) over each signal's buffers; with
+        `per_frame`, (summaries, frame_offsets, rows), rows as extract_signals gives them for those features."""
+        signals = [np.ascontiguousarray(x, dtype=np.float32).ravel() for x in signals]
+        starts, frame_offsets = signals_frame_starts([x.size for x in signals], self.n, hop)
+        samples = np.concatenate(signals) if signals else np.empty(0, np.float32)
+        summ, rows = self.summarize_gather(samples, starts, frame_offsets, features, per_frame)
+        return (summ, frame_offsets, rows) if per_frame else (summ, frame_offsets)
 
     def extract_signal(self, samples, hop, features):
         """Host numpy signal in / numpy out, buffers every `hop` samples (stages the signal, not the buffers)."""

@@ -2942,6 +2942,197 @@ hipError_t launch_synth(float* out, uint64_t count, uint64_t seed, uint64_t firs
   return hipGetLastError();
 }
 
+// ---- Per-signal summaries (mgx_summarize_*): mean, variance, min, max of every pooled column per signal ----
+// A segmented reduction over the per-frame records in two steps (mgx_internal.h SummaryArgs): a partial per
+// block of kSummaryBlock rows of a signal, then the signal's partials added in block order. One thread owns one
+// column of one block and goes down its rows in ascending order, so consecutive lanes read consecutive floats of
+// a row (the array fields), and no sum depends on the grid, on what else is in the launch, or on where a host
+// chunk ended: a block cut by a chunk goes on from its stored state with the same additions in the same order.
+// No atomics: every word of `part` has one writer.
+namespace {
+
+constexpr double kSumInf = __builtin_huge_val();
+
+struct SummaryCol {
+  const void* src;
+  double* dst;
+  uint32_t width, cc, f64;
+};
+
+// Column c's field (wave-uniform reads of the arguments, selected per lane)
+__device__ __forceinline__ SummaryCol summary_col(const SummaryArgs& a, uint32_t c) {
+  SummaryCol r{a.f[0].src, a.f[0].dst, a.f[0].width, c, a.f[0].f64};
+#pragma unroll
+  for (int i = 1; i < kSummaryFields; ++i)
+    if (i < (int)a.nfields && c >= a.f[i].col0) r = SummaryCol{a.f[i].src, a.f[i].dst, a.f[i].width, c - a.f[i].col0, a.f[i].f64};
+  return r;
+}
+
+__device__ __forceinline__ double summary_value(const SummaryCol& f, uint64_t row) {
+  const uint64_t i = row * f.width + f.cc;
+  return f.f64 ? static_cast<const double*>(f.src)[i] : (double)static_cast<const float*>(f.src)[i];
+}
+
+// The caller's device table as the kernels read it: its running maximum, limited to num_frames. One workgroup;
+// thread t owns entries [t per, (t + 1) per). Nothing beyond the n = num_signals + 1 entries is read.
+__global__ __launch_bounds__(256) void summary_table_kernel(const uint64_t* __restrict__ raw, uint64_t* __restrict__ table,
+                                                            uint64_t n, uint64_t limit) {
+  __shared__ uint64_t seg[256];
+  const uint64_t per = (n + 255) / 256, b = threadIdx.x * per, e = b + per < n ? b + per : n;
+  uint64_t m = 0;
+  for (uint64_t i = b; i < e; ++i) m = raw[i] > m ? raw[i] : m;
+  seg[threadIdx.x] = m;
+  __syncthreads();
+  uint64_t run = 0;
+  for (unsigned t = 0; t < threadIdx.x; ++t) run = seg[t] > run ? seg[t] : run;
+  for (uint64_t i = b; i < e; ++i) {
+    run = raw[i] > run ? raw[i] : run;
+    table[i] = run < limit ? run : limit;
+  }
+}
+
+// blockIdx.x: the slot (a.slot0 + x), blockIdx.y: 256 columns
+__global__ __launch_bounds__(256) void summary_partial_kernel(SummaryArgs a) {
+  const uint64_t q = a.slot0 + blockIdx.x;
+  const uint64_t* __restrict__ tb = a.table;
+  // the slot's signal: the last s with table[s] / B + s <= q (strictly increasing in s)
+  if (tb[0] / kSummaryBlock > q) return;
+  uint64_t lo = 0, hi = a.num_signals;
+  while (hi - lo > 1) {
+    const uint64_t mid = lo + (hi - lo) / 2;
+    if (tb[mid] / kSummaryBlock + mid <= q) lo = mid;
+    else hi = mid;
+  }
+  const uint64_t s = lo, first = tb[s], end = tb[s + 1];
+  const uint64_t r0 = first + (q - (first / kSummaryBlock + s)) * kSummaryBlock;
+  if (r0 >= end) return;  // (an empty signal's slot, or one past the signal's last block)
+  const uint64_t r1 = r0 + kSummaryBlock < end ? r0 + kSummaryBlock : end;
+  // the block's rows inside this launch
+  const uint64_t w0 = r0 > a.row0 ? r0 : a.row0, w1 = r1 < a.row0 + a.rows ? r1 : a.row0 + a.rows;
+  if (w0 >= w1) return;
+  const uint32_t c = blockIdx.y * 256 + threadIdx.x;
+  if (c >= a.cols) return;
+  const SummaryCol f = summary_col(a, c);
+  // K: the column's value in the signal's first row, from the rows themselves when the launch holds that row
+  double* const shift = a.shift + s * a.cols + c;
+  double K;
+  if (first >= a.row0) {
+    K = summary_value(f, first - a.row0);
+    if (!(fabs(K) < kSumInf)) K = 0.0;
+    if (r0 == first) *shift = K;
+  } else {
+    K = *shift;
+  }
+  double* const p = a.part + q * kSummaryWords * a.cols + c;
+  const uint64_t cols = a.cols;
+  double s1 = 0.0, s2 = 0.0, mn = kSumInf, mx = -kSumInf;
+  uint64_t flags = 0;
+  if (w0 != r0) {  // the block began in an earlier launch
+    s1 = p[0];
+    s2 = p[cols];
+    mn = p[2 * cols];
+    mx = p[3 * cols];
+    flags = reinterpret_cast<const uint64_t*>(p)[4 * cols];
+  }
+  // the rows, eight loads in flight per lane ahead of the additions (whose order is the rows')
+  auto add = [&](double x) {
+    const bool finite = fabs(x) < kSumInf;
+    const double d = finite ? x - K : 0.0;
+    s1 += d;
+    s2 += d * d;
+    mn = x < mn ? x : mn;  // (a NaN compares false: it leaves both; its flag decides the result)
+    mx = x > mx ? x : mx;
+    flags |= x != x ? 1u : x == kSumInf ? 2u : x == -kSumInf ? 4u : 0u;
+  };
+  auto rows = [&](auto* src) {
+    const uint64_t width = f.width;
+    auto* at = src + (w0 - a.row0) * width + f.cc;
+    uint64_t r = w0;
+    for (; r + 8 <= w1; r += 8, at += 8 * width) {
+      double x[8];
+#pragma unroll
+      for (int i = 0; i < 8; ++i) x[i] = (double)at[i * width];
+#pragma unroll
+      for (int i = 0; i < 8; ++i) add(x[i]);
+    }
+    for (; r < w1; ++r, at += width) add((double)*at);
+  };
+  if (f.f64) rows(static_cast<const double*>(f.src));
+  else rows(static_cast<const float*>(f.src));
+  p[0] = s1;
+  p[cols] = s2;
+  p[2 * cols] = mn;
+  p[3 * cols] = mx;
+  reinterpret_cast<uint64_t*>(p)[4 * cols] = flags;
+}
+
+// blockIdx.x: the signal, blockIdx.y: 256 columns
+__global__ __launch_bounds__(256) void summary_final_kernel(SummaryArgs a) {
+  const uint64_t s = blockIdx.x;
+  const uint32_t c = blockIdx.y * 256 + threadIdx.x;
+  if (c >= a.cols) return;
+  const SummaryCol f = summary_col(a, c);
+  uint64_t first = 0, end = 0;
+  if (a.num_frames > 0) {
+    first = a.table[s];
+    end = a.table[s + 1];
+  }
+  const uint64_t cnt = end - first, cols = a.cols;
+  const double nan = __builtin_nan("");
+  double mean = nan, var = nan, mn = nan, mx = nan;
+  if (cnt > 0) {
+    const uint64_t nb = (cnt + kSummaryBlock - 1) / kSummaryBlock;
+    const double* p = a.part + (first / kSummaryBlock + s) * kSummaryWords * cols + c;
+    double s1 = 0.0, s2 = 0.0;
+    uint64_t flags = 0;
+    mn = kSumInf;
+    mx = -kSumInf;
+    for (uint64_t j = 0; j < nb; ++j, p += kSummaryWords * cols) {
+      s1 += p[0];
+      s2 += p[cols];
+      mn = p[2 * cols] < mn ? p[2 * cols] : mn;
+      mx = p[3 * cols] > mx ? p[3 * cols] : mx;
+      flags |= reinterpret_cast<const uint64_t*>(p)[4 * cols];
+    }
+    const double n = (double)cnt, m1 = s1 / n;
+    mean = a.shift[s * cols + c] + m1;
+    var = (s2 - s1 * m1) / n;
+    var = var < 0.0 ? 0.0 : var;
+    if (flags & 1u) {
+      mean = var = mn = mx = nan;
+    } else if (flags) {  // +-Infinity and no NaN: the mean as the sum gives it, no variance
+      mean = (flags & 6u) == 6u ? nan : (flags & 2u) ? kSumInf : -kSumInf;
+      var = nan;
+    }
+  }
+  double* const d = f.dst + s * MGX_NUM_STATS * f.width + f.cc;
+  d[MGX_STAT_MEAN * f.width] = mean;
+  d[MGX_STAT_VARIANCE * f.width] = var;
+  d[MGX_STAT_MIN * f.width] = mn;
+  d[MGX_STAT_MAX * f.width] = mx;
+}
+
+}  // namespace
+
+hipError_t launch_summary_table(const uint64_t* raw, uint64_t* table, uint64_t num_signals, uint64_t num_frames, hipStream_t stream) {
+  hipLaunchKernelGGL(summary_table_kernel, dim3(1), dim3(256), 0, stream, raw, table, num_signals + 1, num_frames);
+  return hipGetLastError();
+}
+
+hipError_t launch_summary_partial(const SummaryArgs& a, hipStream_t stream) {
+  if (a.nslots == 0 || a.cols == 0 || a.num_signals == 0 || a.rows == 0) return hipSuccess;
+  if (a.nslots > 0x7FFFFFFFull) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(summary_partial_kernel, dim3((unsigned)a.nslots, (a.cols + 255) / 256), dim3(256), 0, stream, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_summary_final(const SummaryArgs& a, hipStream_t stream) {
+  if (a.cols == 0 || a.num_signals == 0) return hipSuccess;
+  if (a.num_signals > 0x7FFFFFFFull) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(summary_final_kernel, dim3((unsigned)a.num_signals, (a.cols + 255) / 256), dim3(256), 0, stream, a);
+  return hipGetLastError();
+}
+
 }  // namespace mgx
 
 #if MGX_WAVE_TIMES

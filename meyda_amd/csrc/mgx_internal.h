@@ -188,6 +188,43 @@ struct UnpackArgs {
   int nseg;
 };
 hipError_t launch_unpack(const UnpackArgs& a, hipStream_t stream);
+
+// Per-signal summaries (mgx_summarize_*; kernels.hip summary_*_kernel). The pooled fields are columns
+// 0 .. cols - 1, field after field; signal s owns rows [table[s], table[s + 1]) of every field, cut from its
+// first row into blocks of kSummaryBlock rows. Block j of signal s has the slot table[s] / kSummaryBlock + s + j:
+// strictly increasing over the blocks of a non-decreasing table, and below num_frames / kSummaryBlock +
+// num_signals. Per slot and column the partial kernel keeps kSummaryWords 8-byte words, part[(slot *
+// kSummaryWords + k) * cols + c]: the sums of (x - K) and of (x - K)^2 over the block's finite rows in ascending
+// row order, their min and max, and the non-finite flags (1 NaN, 2 +Infinity, 4 -Infinity); K is column c of
+// the signal's first row (0 when that is not finite), kept in shift[s * cols + c]. The final kernel adds a
+// signal's partials in ascending block order. Every sum is thus a function of the signal's rows alone.
+constexpr uint64_t kSummaryBlock = 256;
+constexpr int kSummaryWords = 5;
+constexpr int kSummaryFields = MGX_NUM_SCALARS + 5;  // the scalars, loudness_specific, mfcc, amplitude, power, mel_bands
+struct SummaryField {
+  const void* src;  // the per-frame array, at the launch's first row (SummaryArgs::row0)
+  double* dst;      // num_signals x MGX_NUM_STATS x width
+  uint32_t width;   // floats per frame
+  uint32_t col0;    // the field's first column
+  uint32_t f64;     // the per-frame values are doubles (the scalars of a scalar_f64 plan)
+  uint32_t pad;
+};
+struct SummaryArgs {
+  SummaryField f[kSummaryFields];
+  uint32_t nfields, cols;
+  const uint64_t* table;  // num_signals + 1 offsets, non-decreasing and at most num_frames (device memory)
+  uint64_t num_signals, num_frames;
+  // A partial launch covers rows [row0, row0 + rows) of the call (a host chunk; the whole call for a device
+  // launch): a block that began in an earlier launch goes on from its stored state, and a signal that began
+  // there reads its K from `shift`. slot0, nslots: the slots those rows can belong to.
+  uint64_t row0, rows, slot0, nslots;
+  double* shift;
+  double* part;
+};
+// table[s] = min(max(raw[0..s]), num_frames) for s <= num_signals: the caller's device table made non-decreasing
+hipError_t launch_summary_table(const uint64_t* raw, uint64_t* table, uint64_t num_signals, uint64_t num_frames, hipStream_t stream);
+hipError_t launch_summary_partial(const SummaryArgs& a, hipStream_t stream);
+hipError_t launch_summary_final(const SummaryArgs& a, hipStream_t stream);
 size_t extract_lds_bytes(int n, int ncoef, int nfilt, bool chain);
 size_t lds_image_bytes(int n, int ncoef, int nfilt);  // DevTables::lds_image, a multiple of 16
 hipError_t launch_lds_image(int n, int precision, int mode, const KernelArgs& a, void* image, hipStream_t stream);

@@ -16,6 +16,7 @@
 #include <chrono>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <string>
 #include <vector>
 
@@ -487,6 +488,10 @@ struct mgx_plan {
   unsigned char* s_pcm[2] = {nullptr, nullptr};  // raw PCM slots for mgx_extract_host_pcm
   uint64_t* s_starts[2] = {nullptr, nullptr};    // a chunk's starts for mgx_extract_gather_host (kHostChunk entries each)
   uint64_t s_pcm_bytes = 0;
+  // mgx_summarize_host: the table, the shifts, the partials and the summaries themselves on the device (one
+  // allocation, grown when a call needs more)
+  unsigned char* s_sum = nullptr;
+  size_t s_sum_bytes = 0;
   hipStream_t s_copy = nullptr, s_comp = nullptr;
   hipEvent_t ev_loaded[2] = {nullptr, nullptr}, ev_done[2] = {nullptr, nullptr}, ev_back[2] = {nullptr, nullptr};
   // small host batches (kSmallBatchFrames): pinned, device-mapped, coherent host buffers
@@ -836,6 +841,7 @@ int mgx_plan_destroy(mgx_plan* p) {
     for (hipEvent_t ev : {p->ev_loaded[i], p->ev_done[i], p->ev_back[i]})
       if (ev) (void)hipEventDestroy(ev);
   }
+  if (p->s_sum) (void)hipFree(p->s_sum);
   if (p->s_copy) (void)hipStreamDestroy(p->s_copy);
   if (p->s_comp) (void)hipStreamDestroy(p->s_comp);
   if (p->s_res) (void)hipStreamDestroy(p->s_res);
@@ -1475,11 +1481,20 @@ struct GatherChunks {
 // stride: the samples between the starts of consecutive frames in a slot (N: dense frames; a signal's
 // hop: `fill` then writes a chunk's (cnt - 1) stride + N samples); chunk_max: frames per chunk.
 // gc: the chunks are gc's instead (chunk_max: the longest of them), each launched over its slot's table of starts.
+// hook (mgx_summarize_host): its `pooled` fields are computed and laid out in the slot beside the ones the caller
+// named, but do not cross back; after(f0, cnt, d) enqueues the chunk's reduction on the compute stream, over the
+// chunk's records where they lie (d). Without a hook nothing here differs from what it was.
+struct ChunkHook {
+  uint32_t pooled;
+  std::function<int(uint64_t f0, uint64_t cnt, const mgx::Outputs& d)> after;
+};
+
 template <typename Fill>
 int extract_host_chunked(mgx_plan* p, uint64_t nframes, uint64_t stride, uint64_t chunk_max, const mgx::Outputs* o, Fill fill,
-                         const GatherChunks* gc = nullptr) {
+                         const GatherChunks* gc = nullptr, const ChunkHook* hook = nullptr) {
   const int n = p->n;
-  const uint32_t fields = mgx::out_requested(*o);
+  const uint32_t back = mgx::out_requested(*o);  // the fields that return to the caller's arrays
+  const uint32_t fields = back | (hook ? hook->pooled : 0u);
   // device bytes per frame for the requested outputs
   const size_t per = out_bytes_per_frame(p, fields);
   const uint64_t chunk = std::min<uint64_t>(nframes, chunk_max);
@@ -1516,6 +1531,7 @@ int extract_host_chunked(mgx_plan* p, uint64_t nframes, uint64_t stride, uint64_
     opt.gather = gc ? &g : nullptr;
     rc = extract_device_impl(p, p->s_frames[sl], cnt, stride, &d, p->s_comp, opt);
     if (rc) return fail_sync(rc);
+    if (hook && (rc = hook->after(f0, cnt, d))) return fail_sync(rc);
     e = hipEventRecord(p->ev_done[sl], p->s_comp);
     // chunk i+1's frames into the other slot once chunk i-1's extraction has read them
     if (e == hipSuccess && i + 1 < nch) {
@@ -1528,7 +1544,7 @@ int extract_host_chunked(mgx_plan* p, uint64_t nframes, uint64_t stride, uint64_
     // chunk i's outputs back to the caller's arrays
     if (e == hipSuccess) e = hipStreamWaitEvent(p->s_copy, p->ev_done[sl], 0);
     for (int k = 0; k < mgx::kOutFields && e == hipSuccess; ++k) {
-      if (!((fields >> k) & 1u)) continue;
+      if (!((back >> k) & 1u)) continue;
       const uint64_t fb = mgx::out_field_bytes(p->d, k);
       e = hipMemcpyAsync(static_cast<unsigned char*>(mgx::out_field(*o, k)) + f0 * fb, mgx::out_field(d, k), cnt * fb,
                          hipMemcpyDeviceToHost, p->s_copy);
@@ -1553,6 +1569,53 @@ uint32_t sample_bytes(uint32_t format) {
 
 uint16_t rd16(const unsigned char* b) { return (uint16_t)(b[0] | (b[1] << 8)); }
 uint32_t rd32(const unsigned char* b) { return (uint32_t)b[0] | ((uint32_t)b[1] << 8) | ((uint32_t)b[2] << 16) | ((uint32_t)b[3] << 24); }
+
+// The chunked path of mgx_extract_gather_host (starts checked by the caller; hook: extract_host_chunked).
+int gather_host_chunked(mgx_plan* p, const float* samples, const uint64_t* starts, uint64_t nframes, const mgx::Outputs* o,
+                        const ChunkHook* hook) {
+  // Chunks: the longest runs of consecutive buffers of at most host_chunk whose span, max start + N - min start,
+  // fits a slot of the dense path (host_chunk N floats; one buffer always does). Sorted starts no further apart
+  // than N fill their chunks; any other order is served, in as many chunks as its jumps make.
+  GatherChunks gc;
+  std::vector<uint64_t> rel(nframes);  // every start less its chunk's lowest: what the chunk's launch reads
+  const uint64_t n = (uint64_t)p->n, hc = host_chunk(p), slot = hc * n;
+  uint64_t longest = 0;
+  for (uint64_t f0 = 0; f0 < nframes;) {
+    uint64_t lo = starts[f0], hi = starts[f0], f1 = f0 + 1;
+    for (; f1 < nframes && f1 - f0 < hc; ++f1) {
+      const uint64_t l = std::min(lo, starts[f1]), h = std::max(hi, starts[f1]);
+      if (h - l + n > slot) break;
+      lo = l;
+      hi = h;
+    }
+    for (uint64_t f = f0; f < f1; ++f) rel[f] = starts[f] - lo;
+    gc.bounds.push_back(f0);
+    gc.lo.push_back(lo);
+    gc.span.push_back(hi - lo + n);
+    longest = std::max(longest, f1 - f0);
+    f0 = f1;
+  }
+  gc.bounds.push_back(nframes);
+  if (!p->s_starts[0]) {
+    hipError_t e = hipSetDevice(p->d.device);
+    for (int i = 0; i < 2 && e == hipSuccess; ++i) {
+      e = hipMalloc(reinterpret_cast<void**>(&p->s_starts[i]), kHostChunk * sizeof(uint64_t));
+      if (e != hipSuccess) p->s_starts[i] = nullptr;
+    }
+    if (e != hipSuccess) {
+      if (p->s_starts[0]) (void)hipFree(p->s_starts[0]);
+      p->s_starts[0] = nullptr;
+      return hip_fail(e, "hipMalloc(staging starts)");
+    }
+  }
+  uint64_t ci = 0;  // (fill is called for the chunks in order, once each)
+  return extract_host_chunked(p, nframes, n, longest, o, [&](uint64_t f0, uint64_t cnt, int sl, hipStream_t st) {
+    const uint64_t i = ci++;
+    hipError_t e = hipMemcpyAsync(p->s_frames[sl], samples + gc.lo[i], gc.span[i] * sizeof(float), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(p->s_starts[sl], rel.data() + f0, cnt * sizeof(uint64_t), hipMemcpyHostToDevice, st);
+    return e == hipSuccess ? MGX_OK : hip_fail(e, "hipMemcpyAsync(samples, starts)");
+  }, &gc, hook);
+}
 
 }  // namespace
 
@@ -1625,48 +1688,255 @@ int mgx_extract_gather_host(mgx_plan* p, const float* samples, uint64_t num_samp
       for (uint64_t f = 0; f < nframes; ++f) memcpy(dst + f * n, samples + starts[f], (size_t)n * sizeof(float));
       return MGX_OK;
     });
-  // Chunks: the longest runs of consecutive buffers of at most host_chunk whose span, max start + N - min start,
-  // fits a slot of the dense path (host_chunk N floats; one buffer always does). Sorted starts no further apart
-  // than N fill their chunks; any other order is served, in as many chunks as its jumps make.
-  GatherChunks gc;
-  std::vector<uint64_t> rel(nframes);  // every start less its chunk's lowest: what the chunk's launch reads
-  const uint64_t hc = host_chunk(p), slot = hc * n;
-  uint64_t longest = 0;
-  for (uint64_t f0 = 0; f0 < nframes;) {
-    uint64_t lo = starts[f0], hi = starts[f0], f1 = f0 + 1;
-    for (; f1 < nframes && f1 - f0 < hc; ++f1) {
-      const uint64_t l = std::min(lo, starts[f1]), h = std::max(hi, starts[f1]);
-      if (h - l + n > slot) break;
-      lo = l;
-      hi = h;
-    }
-    for (uint64_t f = f0; f < f1; ++f) rel[f] = starts[f] - lo;
-    gc.bounds.push_back(f0);
-    gc.lo.push_back(lo);
-    gc.span.push_back(hi - lo + n);
-    longest = std::max(longest, f1 - f0);
-    f0 = f1;
+  return gather_host_chunked(p, samples, starts, nframes, o, nullptr);
+}
+
+}  // extern "C"
+
+namespace {
+
+// mgx_summarize_*: the caller's summary struct as the kernels' list of fields (each with its destination, its
+// width and its first column; the sources are set per launch), and the pooled fields as bits of the table of
+// output fields (out_fields.h).
+struct SummaryFields {
+  mgx::SummaryArgs a{};
+  int index[mgx::kSummaryFields];  // field i of a.f in the numbering of mgx::out_field
+  uint32_t pooled = 0;
+};
+
+// The summary struct itself: there, and of exactly this build's size (the check that lets it grow). What every
+// summary entry point begins with, ahead of the plan.
+int check_summary(const mgx_summary_outputs* s) {
+  if (!s) return fail(MGX_E_INVALID_ARGUMENT, "summary is NULL");
+  if (s->struct_size != sizeof(mgx_summary_outputs))
+    return fail(MGX_E_INVALID_ARGUMENT, "mgx_summary_outputs.struct_size is %u, expected %zu", s->struct_size,
+                sizeof(mgx_summary_outputs));
+  if (s->reserved != 0) return fail(MGX_E_INVALID_ARGUMENT, "mgx_summary_outputs.reserved is %u, expected 0", s->reserved);
+  return MGX_OK;
+}
+
+void summary_fields(const mgx_plan* p, const mgx_summary_outputs* s, SummaryFields* sf) {
+  // (the summary's arrays in the table's numbering: the scalars, then loudness_specific 13, mfcc 14, the
+  // amplitude and power spectra 15 and 16, mel_bands 19)
+  double* const arrays[] = {s->loudness_specific, s->mfcc, s->amplitude_spectrum, s->power_spectrum, s->mel_bands};
+  const int array_index[] = {13, 14, 15, 16, 19};
+  static_assert(MGX_NUM_SCALARS + sizeof arrays / sizeof *arrays == mgx::kSummaryFields, "one entry per summary field");
+  uint32_t col = 0, nf = 0;
+  for (int i = 0; i < mgx::kSummaryFields; ++i) {
+    double* const dst = i < MGX_NUM_SCALARS ? s->scalars[i] : arrays[i - MGX_NUM_SCALARS];
+    if (!dst) continue;
+    const int idx = i < MGX_NUM_SCALARS ? i : array_index[i - MGX_NUM_SCALARS];
+    mgx::SummaryField& f = sf->a.f[nf];
+    f.dst = dst;
+    f.width = idx < MGX_NUM_SCALARS ? 1u : (uint32_t)(mgx::out_field_bytes(p->d, idx) / 4);
+    f.col0 = col;
+    f.f64 = idx < MGX_NUM_SCALARS && p->d.scalar_f64;
+    col += f.width;
+    sf->index[nf++] = idx;
+    sf->pooled |= 1u << idx;
   }
-  gc.bounds.push_back(nframes);
-  if (!p->s_starts[0]) {
-    hipError_t e = hipSetDevice(p->d.device);
-    for (int i = 0; i < 2 && e == hipSuccess; ++i) {
-      e = hipMalloc(reinterpret_cast<void**>(&p->s_starts[i]), kHostChunk * sizeof(uint64_t));
-      if (e != hipSuccess) p->s_starts[i] = nullptr;
-    }
-    if (e != hipSuccess) {
-      if (p->s_starts[0]) (void)hipFree(p->s_starts[0]);
-      p->s_starts[0] = nullptr;
-      return hip_fail(e, "hipMalloc(staging starts)");
-    }
+  sf->a.nfields = nf;
+  sf->a.cols = col;
+}
+
+// The buffer a summary call works in. The device call's (the caller's workspace): the per-frame arrays of the
+// fields `extra` (pooled, not requested per frame), then the table as the kernels read it, the signals' shifts
+// and the block partials. The host call's (mgx_plan::s_sum): no per-frame arrays (the staging slots hold them),
+// and the summaries themselves at the end. Everything 256-byte aligned; total: a multiple of 256.
+struct SummaryLayout {
+  uint64_t frames[mgx::kOutFields];
+  uint64_t table, shift, part, result, total;
+};
+
+SummaryLayout summary_layout(const mgx_plan_desc& d, uint32_t extra, uint32_t cols, uint64_t nframes, uint64_t nsignals, bool result) {
+  SummaryLayout l{};
+  auto take = [&l](uint64_t bytes) {
+    const uint64_t at = l.total;
+    l.total += (bytes + 255) / 256 * 256;
+    return at;
+  };
+  if (cols == 0 || nsignals == 0 || nframes == 0) return l;
+  take(mgx::out_layout(d, extra, nframes, l.frames));
+  l.table = take((nsignals + 1) * sizeof(uint64_t));
+  l.shift = take(nsignals * cols * sizeof(double));
+  l.part = take((nframes / mgx::kSummaryBlock + nsignals + 1) * mgx::kSummaryWords * cols * sizeof(double));
+  if (result) l.result = take(nsignals * MGX_NUM_STATS * cols * sizeof(double));
+  return l;
+}
+
+// The checks both summary calls share with the gather calls, in their order
+int summary_inputs(const mgx_plan* p, const float* samples, uint64_t num_samples, const uint64_t* starts, uint64_t nframes,
+                   const uint64_t* frame_offsets, uint64_t nsignals) {
+  if (nsignals > 0 && !frame_offsets) return fail(MGX_E_INVALID_ARGUMENT, "frame_offsets is NULL");
+  if (nframes == 0) return MGX_OK;
+  if (!starts) return fail(MGX_E_INVALID_ARGUMENT, "starts is NULL");
+  if (!samples) return fail(MGX_E_INVALID_ARGUMENT, "samples is NULL");
+  if (num_samples < (uint64_t)p->n)
+    return fail(MGX_E_INVALID_ARGUMENT, "%llu samples hold no buffer of %d", (unsigned long long)num_samples, p->n);
+  return MGX_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mgx_summary_workspace_bytes(const mgx_plan* p, const mgx_outputs* o, const mgx_aux_outputs* aux, const mgx_summary_outputs* summary,
+                                uint64_t nframes, uint64_t nsignals, uint64_t* bytes) {
+  if (!bytes) return fail(MGX_E_INVALID_ARGUMENT, "bytes is NULL");
+  const mgx_outputs none{};
+  mgx::Outputs x;
+  int rc = check_summary(summary);
+  if (rc || (rc = make_outputs(p, o ? o : &none, aux, &x))) return rc;
+  SummaryFields sf;
+  summary_fields(p, summary, &sf);
+  *bytes = summary_layout(p->d, sf.pooled & ~mgx::out_requested(x), sf.a.cols, nframes, nsignals, false).total;
+  return MGX_OK;
+}
+
+int mgx_summarize_device(mgx_plan* p, const float* samples, uint64_t num_samples, const uint64_t* starts, uint64_t nframes,
+                         const uint64_t* frame_offsets, uint64_t nsignals, const mgx_outputs* o, const mgx_aux_outputs* aux,
+                         const mgx_summary_outputs* summary, void* workspace, uint64_t workspace_bytes, void* stream) {
+  const mgx_outputs none{};
+  mgx::Outputs x;
+  int rc = check_summary(summary);
+  if (rc || (rc = make_outputs(p, o ? o : &none, aux, &x))) return rc;
+  SummaryFields sf;
+  summary_fields(p, summary, &sf);
+  if ((rc = summary_inputs(p, samples, num_samples, starts, nframes, frame_offsets, nsignals))) return rc;
+  if ((rc = check_outputs(x))) return rc;
+  const SummaryLayout l = summary_layout(p->d, sf.pooled & ~mgx::out_requested(x), sf.a.cols, nframes, nsignals, false);
+  if (workspace_bytes < l.total || (l.total > 0 && !workspace))
+    return fail(MGX_E_INVALID_ARGUMENT, "the workspace holds %llu bytes, the call needs %llu (mgx_summary_workspace_bytes)",
+                (unsigned long long)workspace_bytes, (unsigned long long)l.total);
+  if (l.total > 0 && reinterpret_cast<uintptr_t>(workspace) % 256 != 0)
+    return fail(MGX_E_INVALID_ARGUMENT, "the workspace is not 256-byte aligned");
+  unsigned char* const ws = static_cast<unsigned char*>(workspace);
+  // the launch's outputs: the caller's per-frame arrays, and for the other pooled fields the workspace's
+  mgx::Outputs u = x;
+  if (l.total > 0)
+    for (int i = 0; i < mgx::kOutFields; ++i)
+      if (l.frames[i] != UINT64_MAX) mgx::out_field(u, i) = ws + l.frames[i];
+  if (nframes > 0) {
+    const GatherLaunch g{starts, num_samples};
+    LaunchOpts opt;
+    opt.gather = &g;
+    // (with nothing to pool for, the launch writes the caller's fields alone: the gather call)
+    if ((rc = extract_device_impl(p, samples, nframes, (uint64_t)p->n, l.total > 0 ? &u : &x, stream, opt))) return rc;
   }
-  uint64_t ci = 0;  // (fill is called for the chunks in order, once each)
-  return extract_host_chunked(p, nframes, n, longest, o, [&](uint64_t f0, uint64_t cnt, int sl, hipStream_t st) {
-    const uint64_t i = ci++;
-    hipError_t e = hipMemcpyAsync(p->s_frames[sl], samples + gc.lo[i], gc.span[i] * sizeof(float), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(p->s_starts[sl], rel.data() + f0, cnt * sizeof(uint64_t), hipMemcpyHostToDevice, st);
-    return e == hipSuccess ? MGX_OK : hip_fail(e, "hipMemcpyAsync(samples, starts)");
-  }, &gc);
+  if (nsignals == 0 || sf.a.cols == 0) return MGX_OK;
+  hipError_t e = hipSetDevice(p->d.device);
+  if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
+  mgx::SummaryArgs& a = sf.a;
+  a.num_signals = nsignals;
+  a.num_frames = nframes;
+  if (nframes > 0) {
+    for (uint32_t i = 0; i < a.nfields; ++i) a.f[i].src = mgx::out_field(u, sf.index[i]);
+    uint64_t* const table = reinterpret_cast<uint64_t*>(ws + l.table);
+    a.table = table;
+    a.shift = reinterpret_cast<double*>(ws + l.shift);
+    a.part = reinterpret_cast<double*>(ws + l.part);
+    a.row0 = 0;
+    a.rows = nframes;
+    a.slot0 = 0;
+    a.nslots = nframes / mgx::kSummaryBlock + nsignals;
+    e = mgx::launch_summary_table(frame_offsets, table, nsignals, nframes, (hipStream_t)stream);
+    if (e == hipSuccess) e = mgx::launch_summary_partial(a, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, "summary kernel launch");
+  }
+  e = mgx::launch_summary_final(a, (hipStream_t)stream);
+  return e == hipSuccess ? MGX_OK : hip_fail(e, "summary kernel launch");
+}
+
+int mgx_summarize_host(mgx_plan* p, const float* samples, uint64_t num_samples, const uint64_t* starts, uint64_t nframes,
+                       const uint64_t* frame_offsets, uint64_t nsignals, const mgx_outputs* outputs, const mgx_aux_outputs* aux,
+                       const mgx_summary_outputs* summary) {
+  const mgx_outputs none{};
+  mgx::Outputs x;
+  int rc = check_summary(summary);
+  if (rc || (rc = make_outputs(p, outputs ? outputs : &none, aux, &x))) return rc;
+  SummaryFields sf;
+  summary_fields(p, summary, &sf);
+  if ((rc = summary_inputs(p, samples, num_samples, starts, nframes, frame_offsets, nsignals))) return rc;
+  if ((rc = check_outputs(x))) return rc;
+  // (the host sees both tables: they are checked here, before any copy)
+  const uint64_t n = (uint64_t)p->n;
+  for (uint64_t f = 0; f < nframes; ++f)
+    if (starts[f] > num_samples - n)
+      return fail(MGX_E_INVALID_ARGUMENT, "starts[%llu] = %llu: a buffer of %d leaves the %llu samples", (unsigned long long)f,
+                  (unsigned long long)starts[f], p->n, (unsigned long long)num_samples);
+  for (uint64_t s = 0; s < nsignals; ++s)
+    if (frame_offsets[s + 1] < frame_offsets[s])
+      return fail(MGX_E_INVALID_ARGUMENT, "frame_offsets[%llu] = %llu is below frame_offsets[%llu] = %llu", (unsigned long long)(s + 1),
+                  (unsigned long long)frame_offsets[s + 1], (unsigned long long)s, (unsigned long long)frame_offsets[s]);
+  if (nsignals > 0 && frame_offsets[nsignals] > nframes)
+    return fail(MGX_E_INVALID_ARGUMENT, "frame_offsets[%llu] = %llu is above the %llu buffers", (unsigned long long)nsignals,
+                (unsigned long long)frame_offsets[nsignals], (unsigned long long)nframes);
+  resident_stop(p);
+  mgx::SummaryArgs& a = sf.a;
+  if (nframes == 0) {
+    // no buffers: every signal is empty, NaN in all four (nothing for the device to do)
+    for (uint32_t i = 0; i < a.nfields; ++i)
+      std::fill_n(a.f[i].dst, nsignals * MGX_NUM_STATS * a.f[i].width, std::nan(""));
+    return MGX_OK;
+  }
+  if (nsignals == 0 || a.cols == 0) return gather_host_chunked(p, samples, starts, nframes, &x, nullptr);
+  const SummaryLayout l = summary_layout(p->d, 0, a.cols, nframes, nsignals, true);
+  hipError_t e = hipSetDevice(p->d.device);
+  if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
+  // the staging streams first: the table's copy and the last kernel go on the compute stream
+  if ((rc = ensure_host_staging(p, 1, mgx::kOutLayoutSlack))) return rc;
+  if (p->s_sum_bytes < l.total) {
+    if (p->s_sum) (void)hipFree(p->s_sum);
+    p->s_sum = nullptr;
+    p->s_sum_bytes = 0;
+    e = hipMalloc(reinterpret_cast<void**>(&p->s_sum), l.total);
+    if (e != hipSuccess) { p->s_sum = nullptr; return hip_fail(e, "hipMalloc(summary buffers)"); }
+    p->s_sum_bytes = l.total;
+  }
+  a.num_signals = nsignals;
+  a.num_frames = nframes;
+  a.table = reinterpret_cast<const uint64_t*>(p->s_sum + l.table);
+  a.shift = reinterpret_cast<double*>(p->s_sum + l.shift);
+  a.part = reinterpret_cast<double*>(p->s_sum + l.part);
+  e = hipMemcpyAsync(p->s_sum + l.table, frame_offsets, (nsignals + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, p->s_comp);
+  if (e != hipSuccess) return hip_fail(e, "hipMemcpyAsync(frame_offsets)");
+  ChunkHook hook;
+  hook.pooled = sf.pooled;
+  hook.after = [&](uint64_t f0, uint64_t cnt, const mgx::Outputs& d) {
+    // the chunk's rows [f0, f0 + cnt) and the slots they can belong to: from the block that holds the first of
+    // them that a signal owns to the block that holds the last (the kernel passes over a slot without rows here)
+    const uint64_t* const tb = frame_offsets;
+    const uint64_t c0 = f0, c1 = f0 + cnt, B = mgx::kSummaryBlock;
+    const uint64_t* const it = std::upper_bound(tb + 1, tb + nsignals + 1, c0);  // the first signal that ends after c0
+    if (it == tb + nsignals + 1) return (int)MGX_OK;
+    const uint64_t s_lo = (uint64_t)(it - (tb + 1)), a_lo = tb[s_lo];
+    if (a_lo >= c1) return (int)MGX_OK;
+    const uint64_t s_hi = (uint64_t)(std::lower_bound(tb, tb + nsignals, c1) - tb) - 1;  // the last signal that begins before c1
+    const uint64_t a_hi = tb[s_hi], e_hi = std::min(c1, tb[s_hi + 1]), last = e_hi > a_hi ? e_hi - 1 : a_hi;
+    mgx::SummaryArgs c = a;
+    for (uint32_t i = 0; i < c.nfields; ++i) c.f[i].src = mgx::out_field(d, sf.index[i]);
+    c.row0 = c0;
+    c.rows = cnt;
+    c.slot0 = a_lo / B + s_lo + (std::max(c0, a_lo) - a_lo) / B;
+    c.nslots = a_hi / B + s_hi + (last - a_hi) / B - c.slot0 + 1;
+    const hipError_t ke = mgx::launch_summary_partial(c, p->s_comp);
+    return ke == hipSuccess ? (int)MGX_OK : hip_fail(ke, "summary kernel launch");
+  };
+  if ((rc = gather_host_chunked(p, samples, starts, nframes, &x, &hook))) return rc;
+  // the signals' partials into the summaries, and those alone back to the caller
+  double* const result = reinterpret_cast<double*>(p->s_sum + l.result);
+  std::vector<double*> host_dst(a.nfields);
+  for (uint32_t i = 0; i < a.nfields; ++i) {
+    host_dst[i] = a.f[i].dst;
+    a.f[i].dst = result + nsignals * MGX_NUM_STATS * a.f[i].col0;
+  }
+  e = mgx::launch_summary_final(a, p->s_comp);
+  for (uint32_t i = 0; i < a.nfields && e == hipSuccess; ++i)
+    e = hipMemcpyAsync(host_dst[i], a.f[i].dst, nsignals * MGX_NUM_STATS * a.f[i].width * sizeof(double), hipMemcpyDeviceToHost,
+                       p->s_comp);
+  const hipError_t es = hipStreamSynchronize(p->s_comp);
+  if (e == hipSuccess) e = es;
+  return e == hipSuccess ? MGX_OK : hip_fail(e, "summary kernels and copies");
 }
 
 int mgx_wav_parse(const void* bytes, uint64_t len, mgx_wav_info* info) {

@@ -28,6 +28,9 @@
 //                                   signals: an array of Float32Arrays (a corpus); every signal's buffers
 //                                   in one launch, none across two signals; getBatch's result plus
 //                                   frameOffsets (signal s: rows frameOffsets[s] .. frameOffsets[s + 1])
+//   getSignalSummaries(features, signals, hopSize) / getSignalSummariesAsync(...)
+//                                   getBatchSignals' signals pooled per signal on the device: per feature
+//                                   {mean, variance, min, max}, Float64Arrays of signals x width, plus frameOffsets
 //   Meyda.signalsFrameStarts(lengths, bufferSize, hopSize)
 //                                   {starts, frameOffsets} of signals stored one after another
 //   Meyda.readWav(wavBytes)         the header: {pcmFormat, channels, sampleRate, sampleFrames, ...}
@@ -441,6 +444,24 @@ class Meyda {
     });
   }
 
+  // The signals of getBatchSignals pooled per signal on the device: for every feature {mean, variance, min,
+  // max}, Float64Arrays of signals.length x width (width: the feature's values per buffer, 1 for a number;
+  // signal s at [s width, (s + 1) width)); 'loudness' gives {specific, total}, each such an object. Population
+  // variance; a signal without buffers gives NaN. frameOffsets as getBatchSignals returns it. Only the
+  // summaries cross back from the device. 'complexSpectrum' and 'buffer' have no summary (TypeError).
+  getSignalSummaries(features, signals, hopSize) {
+    const names = this._checkNames(checkSummaryNames(features));
+    const c = this._concatSignals(signals, hopSize);
+    return summaryResult(names, addon.summarizeGather(this._plan(), c.samples, c.starts, c.frameOffsets, names), c.frameOffsets);
+  }
+
+  getSignalSummariesAsync(features, signals, hopSize) {
+    const names = this._checkNames(checkSummaryNames(features));
+    const c = this._concatSignals(signals, hopSize);
+    return this._runAsync((plan) => addon.summarizeGatherAsync(plan, c.samples, c.starts, c.frameOffsets, names))
+      .then((r) => summaryResult(names, r, c.frameOffsets));
+  }
+
   _concatSignals(signals, hopSize) {
     const hop = this._checkHop(hopSize);
     if (!Array.isArray(signals)) throw new TypeError('signals must be an array of Float32Arrays');
@@ -638,6 +659,36 @@ function checkBatchNames(features) {
     if (!GPU_FEATURES.has(n)) throw new TypeError("unknown batch feature '" + n + "'");
   }
   return names;
+}
+
+// The features a summary pools: every batch feature but the complex spectrum and the buffer itself
+function checkSummaryNames(features) {
+  const names = typeof features === 'string' ? [features] : Array.prototype.slice.call(features);
+  for (const n of names) {
+    if (n === 'complexSpectrum' || n === 'buffer') throw new TypeError("'" + n + "' has no summary");
+  }
+  return checkBatchNames(names);
+}
+
+// The addon's summaries (per field a Float64Array, signal s's statistic k at [(4 s + k) width, ...)) in the
+// facade's shape: per feature {mean, variance, min, max}, each signals x width
+const STATS = ['mean', 'variance', 'min', 'max'];
+function summaryResult(names, raw, frameOffsets) {
+  const S = frameOffsets.length - 1;
+  const split = (a) => {
+    const w = S > 0 ? a.length / (STATS.length * S) : 0;
+    const o = {};
+    STATS.forEach((k, j) => {
+      o[k] = new Float64Array(S * w);
+      for (let s = 0; s < S; ++s) o[k].set(a.subarray((s * STATS.length + j) * w, (s * STATS.length + j + 1) * w), s * w);
+    });
+    return o;
+  };
+  const r = { frameOffsets };
+  for (const n of names) {
+    r[n] = n === 'loudness' ? { specific: split(raw['loudness.specific']), total: split(raw['loudness.total']) } : split(raw[n]);
+  }
+  return r;
 }
 
 // Slice frame `i` of a SoA batch result into the reference's return shapes

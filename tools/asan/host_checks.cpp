@@ -217,6 +217,20 @@ static void frame_starts() {
   const uint64_t one = 0;
   CHECK(mgx_extract_gather_host(nullptr, nullptr, 0, &one, 1, nullptr, nullptr) == MGX_E_INVALID_ARGUMENT);
   CHECK(mgx_extract_gather_device(nullptr, nullptr, 0, &one, 1, nullptr, nullptr, nullptr) == MGX_E_INVALID_ARGUMENT);
+  // the summary calls: the struct is checked ahead of the plan, then the plan (nothing is read through either)
+  const uint64_t fo[2] = {0, 1};
+  uint64_t bytes = 77;
+  mgx_summary_outputs so;
+  memset(&so, 0, sizeof so);
+  for (uint32_t size : {0u, (uint32_t)sizeof so - 8, (uint32_t)sizeof so + 8, (uint32_t)sizeof so}) {
+    so.struct_size = size;
+    CHECK(mgx_summarize_host(nullptr, nullptr, 0, &one, 1, fo, 1, nullptr, nullptr, &so) == MGX_E_INVALID_ARGUMENT);
+    CHECK(strstr(mgx_last_error(), size == sizeof so ? "NULL plan" : "struct_size") != nullptr);
+    CHECK(mgx_summarize_device(nullptr, nullptr, 0, &one, 1, fo, 1, nullptr, nullptr, &so, nullptr, 0, nullptr) == MGX_E_INVALID_ARGUMENT);
+    CHECK(mgx_summary_workspace_bytes(nullptr, nullptr, nullptr, &so, 1, 1, &bytes) == MGX_E_INVALID_ARGUMENT);
+  }
+  CHECK(mgx_summarize_host(nullptr, nullptr, 0, &one, 1, fo, 1, nullptr, nullptr, nullptr) == MGX_E_INVALID_ARGUMENT);
+  CHECK(mgx_summary_workspace_bytes(nullptr, nullptr, nullptr, &so, 1, 1, nullptr) == MGX_E_INVALID_ARGUMENT && bytes == 77);
   printf("frame starts: %ld tables\n", n);
 }
 
