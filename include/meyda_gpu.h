@@ -32,6 +32,8 @@
  *   mgx_summarize_*      the gather calls with every clip's rows     no counterpart, as with the groups:
  *                        pooled on the device: mean, variance, min   the per-clip pooling loop of a host
  *                        and max of each output over a clip          application over Meyda.get's results
+ *   mgx_delta_device,    the rows' time derivatives (delta, delta-  no counterpart: the regression
+ *   mgx_summarize_deltas_*  delta) per frame, and pooled per clip    stencil of a host application
  *   mgx_group_*          several devices, RCCL gather of the        src/meyda.js:17-97 (one plan
  *                        per-frame records to the root device       per device), :69-91 (buffers
  *                                                                   are independent: shardable)
@@ -482,6 +484,87 @@ int mgx_summarize_device(mgx_plan* plan, const float* samples, uint64_t num_samp
 int mgx_summarize_host(mgx_plan* plan, const float* samples, uint64_t num_samples, const uint64_t* starts,
                        uint64_t num_frames, const uint64_t* frame_offsets, uint64_t num_signals,
                        const mgx_outputs* outputs, const mgx_aux_outputs* aux, const mgx_summary_outputs* summary);
+
+/* ---- Deltas: the time derivatives of a clip's rows, per frame and pooled ---------------------
+ * Replaces, in a host application, the stencil that turns a clip's per-buffer rows into their regression
+ * deltas (MFCC + delta + delta-delta, the per-frame vector of HTK, Kaldi and librosa.feature.delta) and the
+ * pooling of those into the clip descriptor. The reference has no counterpart. Deltas, like the statistics,
+ * are not features: MGX_NUM_FEATURES, the name table and every struct above are as they were.
+ *
+ * A signal owns rows [a, b) of an array of num_frames rows x cols columns (row-major, rows cols elements
+ * apart). For a half-width W (1 .. MGX_DELTA_MAX_WIDTH), a row t of [a, b) and a column c:
+ *
+ *   x~(u)     = x(min(max(u, a), b - 1), c)          rows outside the signal repeat its first / last row
+ *   delta(t,c) = (sum_{n = 1..W} n (x~(t + n) - x~(t - n))) / D,   D = 2 sum n^2 = W (W + 1) (2 W + 1) / 3
+ *
+ * The values are taken as float64 (a float32 converts exactly); the sum runs in ascending n in float64 (a
+ * difference, a product and an addition per term, each rounded), is divided by D and rounded once to the
+ * array's element type. The second order is the same operator over the delta rows as stored, clamped again at
+ * the signal's own ends: bit for bit what a second call on the first call's output gives. Non-finite values
+ * follow IEEE (Inf - Inf = NaN) and reach the rows within W (2 W for the second order) of them, in their own
+ * signal and column. A signal of one row has delta 0 wherever x is finite; an empty signal writes nothing;
+ * rows that belong to no signal (before frame_offsets[0], from frame_offsets[num_signals] on) are not written.
+ * A value is a function of its own signal's rows alone: no atomics, and the same bits from every call below,
+ * from a repeated call and from any grid. */
+#define MGX_DELTA_MAX_WIDTH 8
+
+/* The operator on device arrays; no plan (as mgx_pcm_decode_device takes none): asynchronous on `stream`, no
+ * allocation, no host-side state, capturable. rows_f64: 0 float32 rows, 1 float64 rows (the scalars of a
+ * scalar_f64 plan); the outputs have the rows' element type and shape. delta: the first order, delta2: the
+ * second; either may be NULL (with delta2 alone the first order is recomputed where the second needs it, from
+ * the same arithmetic: the same bits). frame_offsets: num_signals + 1 entries in device memory, or NULL with
+ * num_signals = 0 for one signal [0, num_frames) -- the output of a mgx_extract_signal_* call. The table is
+ * read as given, every entry limited to num_frames: a non-decreasing one gives the definition above, any other
+ * gives unspecified values in the outputs and no access outside the arrays.
+ * MGX_E_INVALID_ARGUMENT before any launch: cols = 0, width outside 1 .. MGX_DELTA_MAX_WIDTH, rows_f64 > 1,
+ * both outputs NULL, an output equal to rows or to the other output, num_signals > 0 with NULL frame_offsets,
+ * NULL rows with num_frames > 0. num_frames = 0 returns MGX_OK and writes nothing. */
+int mgx_delta_device(const void* rows, uint64_t num_frames, uint32_t cols, uint32_t rows_f64,
+                     const uint64_t* frame_offsets, uint64_t num_signals, uint32_t width,
+                     void* delta, void* delta2, void* stream);
+
+/* The summaries of the delta rows beside the summaries of the rows: mgx_summarize_* with this struct behind
+ * their arguments. delta / delta2 are mgx_summary_outputs themselves (same layout, float64 values and four
+ * statistics) and name the fields whose first / second order rows are pooled -- by the summary kernels, so
+ * every rule of the summaries holds for them (the bounds, NaN for an empty signal, NaN in all four for a
+ * column with a NaN, blocks of 256 rows from the signal's first row); a one-buffer signal gives mean = min =
+ * max = 0 and variance exactly 0. Fields: the 13 scalars (float64 rows on a scalar_f64 plan), loudness_specific,
+ * mfcc and mel_bands; a spectrum is MGX_E_UNSUPPORTED (the operator itself takes any cols). delta2 may name
+ * fields delta does not. */
+typedef struct mgx_delta_summaries {
+  uint32_t struct_size;                  /* = sizeof(mgx_delta_summaries); anything else: MGX_E_INVALID_ARGUMENT */
+  uint32_t width;                        /* W */
+  const mgx_summary_outputs* delta;      /* summaries of the delta rows of the fields it names, or NULL */
+  const mgx_summary_outputs* delta2;     /* of the second-order rows, or NULL */
+} mgx_delta_summaries;
+
+/* The three summary calls with deltas. deltas = NULL is exactly the mgx_summarize_* call (and the bytes of
+ * mgx_summary_workspace_bytes); `summary` must be a valid struct, but all of its fields may be NULL. Every
+ * per-frame field and every base summary the call names is written bit for bit as mgx_summarize_device /
+ * _host writes it.
+ * Device call: the workspace also holds the rows of a delta'd field that is neither requested per frame nor
+ * pooled, the delta and second-order rows of the named fields and their partials; its bytes keep the contract
+ * of mgx_summary_workspace_bytes (a multiple of 256, non-decreasing in num_frames, 0 when there is nothing to
+ * keep). After the gather launch the operator runs over those rows (two passes per field, keyed by the table
+ * as the summary kernels read it), then the summary kernels.
+ * Host call: the base summaries are reduced chunk by chunk as in mgx_summarize_host; the rows of the delta'd
+ * fields alone are copied, device to device, into plan-owned arrays as long as the call (at most 3 x
+ * num_frames x their columns x 4 bytes, 8 for float64 scalars; grown on demand, freed at mgx_plan_destroy;
+ * MGX_E_OUT_OF_MEMORY when the device has no room), and after the last chunk the operator and the pooling run
+ * over them as in the device call: the device call's bits, wherever the chunks end. Only summaries and the
+ * per-frame fields named cross back. */
+int mgx_summarize_deltas_workspace_bytes(const mgx_plan* plan, const mgx_outputs* outputs, const mgx_aux_outputs* aux,
+                                         const mgx_summary_outputs* summary, const mgx_delta_summaries* deltas,
+                                         uint64_t num_frames, uint64_t num_signals, uint64_t* bytes);
+int mgx_summarize_deltas_device(mgx_plan* plan, const float* samples, uint64_t num_samples, const uint64_t* starts,
+                                uint64_t num_frames, const uint64_t* frame_offsets, uint64_t num_signals,
+                                const mgx_outputs* outputs, const mgx_aux_outputs* aux,
+                                const mgx_summary_outputs* summary, const mgx_delta_summaries* deltas,
+                                void* workspace, uint64_t workspace_bytes, void* stream);
+int mgx_summarize_deltas_host(mgx_plan* plan, const float* samples, uint64_t num_samples, const uint64_t* starts,
+                              uint64_t num_frames, const uint64_t* frame_offsets, uint64_t num_signals,
+                              const mgx_outputs* outputs, const mgx_aux_outputs* aux,
+                              const mgx_summary_outputs* summary, const mgx_delta_summaries* deltas);
 
 /* ---- Multi-device groups -------------------------------
  * Replaces nothing in the reference (single-threaded browser code); it exists because

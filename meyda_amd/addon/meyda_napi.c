@@ -15,7 +15,7 @@
  *   extractWav(plan, wavBytes, features[, channel]) / extractWavAsync(...)
  *                                        -> the features of every full buffer of a .wav file;
  *                                           the raw PCM is decoded on the device
- *   summarizeGather(plan, samples, starts, frameOffsets, features) / summarizeGatherAsync(...)
+ *   summarizeGather(plan, samples, starts, frameOffsets, features[, {deltaWidth, deltaOrder}]) / summarizeGatherAsync(...)
  *                                        -> { name: Float64Array(S x 4 x width) }: mean, variance, min, max
  *                                           of each field over every signal's buffers (mgx_summarize_host)
  *   wavParse(wavBytes)                   -> { pcmFormat, channels, sampleRate, bitsPerSample, ... }
@@ -276,6 +276,12 @@ typedef struct {
   uint64_t* frame_offsets;
   uint64_t nsignals;
   mgx_summary_outputs sum;
+  /* ... with the options {deltaWidth, deltaOrder}: the summaries of the rows' deltas (order 1) and of the deltas'
+   * deltas (order 2) of the same fields beside them (mgx_summarize_deltas_host); delta_order 0: none asked for */
+  uint32_t delta_width, delta_order;
+  mgx_summary_outputs dsum[2];
+  mgx_delta_summaries deltas;
+  napi_ref drefs[2][NSLOTS];
   mgx_outputs out;
   mgx_aux_outputs aux;  /* melBands (SLOT_MEL): the job then makes the mgx_extract_*_ex call */
   /* The outputs are written straight into JS ArrayBuffers (napi_create_arraybuffer), held by
@@ -305,6 +311,12 @@ static void job_free_buffers(napi_env env, job* j) {
       j->refs[i] = NULL;
       j->bufs[i] = NULL;
     }
+  for (int k = 0; k < 2; ++k)
+    for (int i = 0; i < NSLOTS; ++i)
+      if (j->drefs[k][i]) {
+        napi_delete_reference(env, j->drefs[k][i]);
+        j->drefs[k][i] = NULL;
+      }
 }
 
 /* Parse the features argument (string or array of strings) into wanted output slots. */
@@ -493,11 +505,45 @@ static int job_prepare_gather(napi_env env, job* j, napi_value samples_v, napi_v
 
 /* summarizeGather(plan, samples, starts, frameOffsets, features): extractGather's inputs and the table of the
  * signals' buffers (a Float64Array of nsignals + 1 offsets, as signalsFrameStarts returns it). */
+/* A property of the options object as an integer in [lo, hi]; absent or undefined: dflt. 0 with a RangeError pending. */
+static int option_u32(napi_env env, napi_value obj, const char* name, uint32_t lo, uint32_t hi, uint32_t dflt, uint32_t* out) {
+  napi_value v;
+  napi_valuetype t = napi_undefined;
+  double d = 0;
+  *out = dflt;
+  if (napi_get_named_property(env, obj, name, &v) != napi_ok) return 0;
+  napi_typeof(env, v, &t);
+  if (t == napi_undefined) return 1;
+  if (t == napi_number) napi_get_value_double(env, v, &d);
+  if (t != napi_number || !(d >= lo) || d > hi || d != (double)(uint32_t)d) {
+    char msg[96];
+    snprintf(msg, sizeof msg, "%s must be an integer from %u to %u", name, lo, hi);
+    napi_throw_range_error(env, NULL, msg);
+    return 0;
+  }
+  *out = (uint32_t)d;
+  return 1;
+}
+
 static int job_prepare_summary(napi_env env, job* j, napi_value samples_v, napi_value starts_v, napi_value offsets_v,
-                               napi_value feats) {
+                               napi_value feats, napi_value options_v) {
   size_t count = 0;
   j->summary = 1;
   j->sum.struct_size = sizeof j->sum;
+  napi_valuetype ot = napi_undefined;
+  if (options_v) napi_typeof(env, options_v, &ot);
+  if (ot == napi_object) {  /* the trailing options: {deltaWidth = 2, deltaOrder = 2} */
+    if (!option_u32(env, options_v, "deltaWidth", 1, MGX_DELTA_MAX_WIDTH, 2, &j->delta_width)) return 0;
+    if (!option_u32(env, options_v, "deltaOrder", 1, 2, 2, &j->delta_order)) return 0;
+    j->deltas.struct_size = sizeof j->deltas;
+    j->deltas.width = j->delta_width;
+    for (uint32_t k = 0; k < j->delta_order; ++k) j->dsum[k].struct_size = sizeof j->dsum[k];
+    j->deltas.delta = &j->dsum[0];
+    j->deltas.delta2 = j->delta_order > 1 ? &j->dsum[1] : NULL;
+  } else if (ot != napi_undefined && ot != napi_null) {
+    napi_throw_type_error(env, NULL, "options must be an object: {deltaWidth, deltaOrder}");
+    return 0;
+  }
   j->frame_offsets = u64_of_f64(env, offsets_v, "frameOffsets", &count);
   if (!j->frame_offsets) return 0;
   if (count < 1) {
@@ -535,6 +581,14 @@ static int job_alloc(napi_env env, job* j, napi_value feats) {
     j->bufs[i] = data;
     if (j->summary) set_summary_field(&j->sum, i, (double*)data);
     else set_field(&j->out, &j->aux, i, data);
+    /* the delta summaries of the same field: arrays of the same size (a spectrum's too: the library refuses it) */
+    for (uint32_t k = 0; j->summary && k < j->delta_order; ++k) {
+      if (napi_create_arraybuffer(env, b, &data, &abv) != napi_ok || napi_create_reference(env, abv, 1, &j->drefs[k][i]) != napi_ok) {
+        napi_throw_error(env, NULL, "out of host memory");
+        return 0;
+      }
+      set_summary_field(&j->dsum[k], i, (double*)data);
+    }
   }
   return 1;
 }
@@ -620,7 +674,10 @@ static void job_run(job* j) {
     return;
   }
   const uint32_t n = j->box->desc.buffer_size;
-  if (j->summary)
+  if (j->summary && j->delta_order)
+    j->rc = mgx_summarize_deltas_host(j->box->plan, j->frames, j->nsamples, j->starts, j->nframes, j->frame_offsets, j->nsignals,
+                                      NULL, NULL, &j->sum, &j->deltas);
+  else if (j->summary)
     j->rc = mgx_summarize_host(j->box->plan, j->frames, j->nsamples, j->starts, j->nframes, j->frame_offsets, j->nsignals, NULL,
                                NULL, &j->sum);
   else if (j->gather)
@@ -647,11 +704,15 @@ static void job_run(job* j) {
   if (j->rc) snprintf(j->err, sizeof j->err, "%s", mgx_last_error());
 }
 
-static napi_value typed(napi_env env, job* j, int slot, napi_typedarray_type t, size_t elem) {
+static napi_value typed_of(napi_env env, napi_ref ref, size_t bytes, napi_typedarray_type t, size_t elem) {
   napi_value ab, ta;
-  if (napi_get_reference_value(env, j->refs[slot], &ab) != napi_ok) return NULL;
-  if (napi_create_typedarray(env, t, j->bytes[slot] / elem, ab, 0, &ta) != napi_ok) return NULL;
+  if (napi_get_reference_value(env, ref, &ab) != napi_ok) return NULL;
+  if (napi_create_typedarray(env, t, bytes / elem, ab, 0, &ta) != napi_ok) return NULL;
   return ta;
+}
+
+static napi_value typed(napi_env env, job* j, int slot, napi_typedarray_type t, size_t elem) {
+  return typed_of(env, j->refs[slot], j->bytes[slot], t, elem);
 }
 
 static napi_value job_result(napi_env env, job* j) {
@@ -666,6 +727,16 @@ static napi_value job_result(napi_env env, job* j) {
     for (int i = 0; i < NSLOTS; ++i) {
       const char* nm = i < MGX_NUM_SCALARS ? names[i] : arrays[i - SLOT_LOUD];
       if (j->want[i] && nm) napi_set_named_property(env, obj, nm, typed(env, j, i, napi_float64_array, 8));
+    }
+    /* the delta summaries: objects of the same names under "delta" and (order 2) "delta2" */
+    for (uint32_t k = 0; k < j->delta_order; ++k) {
+      napi_value sub;
+      if (napi_create_object(env, &sub) != napi_ok) return NULL;
+      for (int i = 0; i < NSLOTS; ++i) {
+        const char* nm = i < MGX_NUM_SCALARS ? names[i] : arrays[i - SLOT_LOUD];
+        if (j->want[i] && nm) napi_set_named_property(env, sub, nm, typed_of(env, j->drefs[k][i], j->bytes[i], napi_float64_array, 8));
+      }
+      napi_set_named_property(env, obj, k ? "delta2" : "delta", sub);
     }
     return obj;
   }
@@ -689,17 +760,17 @@ static int job_prepare_kind(napi_env env, job* j, int kind, size_t argc, napi_va
   if (kind == IN_WAV) return job_prepare_wav(env, j, argv[1], argv[2], argc > 3 ? argv[3] : NULL, argc > 4 ? argv[4] : NULL);
   if (kind == IN_SIGNAL) return job_prepare_signal(env, j, argv[1], argv[2], argv[3]);
   if (kind == IN_GATHER) return job_prepare_gather(env, j, argv[1], argv[2], argv[3]);
-  if (kind == IN_SUMMARY) return job_prepare_summary(env, j, argv[1], argv[2], argv[3], argv[4]);
+  if (kind == IN_SUMMARY) return job_prepare_summary(env, j, argv[1], argv[2], argv[3], argv[4], argc > 5 ? argv[5] : NULL);
   return job_prepare(env, j, argv[1], argv[2]);
 }
 
 static napi_value extract_common(napi_env env, napi_callback_info info, int kind) {
-  size_t argc = 5;
-  napi_value argv[5];
+  size_t argc = 6;
+  napi_value argv[6];
   CHECK(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
   if (argc < (kind == IN_SUMMARY ? 5u : kind == IN_SIGNAL || kind == IN_GATHER ? 4u : 3u)) {
     napi_throw_type_error(env, NULL, kind == IN_WAV ? "extractWav(plan, wavBytes, features[, channel[, hop]])"
-                                   : kind == IN_SUMMARY ? "summarizeGather(plan, samples, starts, frameOffsets, features)"
+                                   : kind == IN_SUMMARY ? "summarizeGather(plan, samples, starts, frameOffsets, features[, {deltaWidth, deltaOrder}])"
                                    : kind == IN_GATHER ? "extractGather(plan, samples, starts, features)"
                                    : kind == IN_SIGNAL ? "extractSignal(plan, samples, hop, features)"
                                                        : "extract(plan, frames, features)");
@@ -848,12 +919,12 @@ static void async_complete(napi_env env, napi_status status, void* data) {
 }
 
 static napi_value extract_async_common(napi_env env, napi_callback_info info, int kind) {
-  size_t argc = 5;
-  napi_value argv[5];
+  size_t argc = 6;
+  napi_value argv[6];
   CHECK(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
   if (argc < (kind == IN_SUMMARY ? 5u : kind == IN_SIGNAL || kind == IN_GATHER ? 4u : 3u)) {
     napi_throw_type_error(env, NULL, kind == IN_WAV ? "extractWavAsync(plan, wavBytes, features[, channel[, hop]])"
-                                   : kind == IN_SUMMARY ? "summarizeGatherAsync(plan, samples, starts, frameOffsets, features)"
+                                   : kind == IN_SUMMARY ? "summarizeGatherAsync(plan, samples, starts, frameOffsets, features[, {deltaWidth, deltaOrder}])"
                                    : kind == IN_GATHER ? "extractGatherAsync(plan, samples, starts, features)"
                                    : kind == IN_SIGNAL ? "extractSignalAsync(plan, samples, hop, features)"
                                                        : "extractAsync(plan, frames, features)");

@@ -39,6 +39,8 @@ EXPORTS = ["mgx_plan_desc_init", "mgx_plan_create", "mgx_plan_destroy", "mgx_pla
            "mgx_extract_device_ex", "mgx_extract_host_ex", "mgx_extract_host_pcm_ex",
            "mgx_signals_frame_starts", "mgx_extract_gather_device", "mgx_extract_gather_host",
            "mgx_summary_workspace_bytes", "mgx_summarize_device", "mgx_summarize_host",
+           "mgx_delta_device", "mgx_summarize_deltas_workspace_bytes", "mgx_summarize_deltas_device",
+           "mgx_summarize_deltas_host",
            "mgx_shard_range", "mgx_packed_layout", "mgx_comm_unique_id", "mgx_group_create",
            "mgx_group_create_rank", "mgx_group_create_loopback", "mgx_group_create_loopback_rccl", "mgx_group_destroy",
            "mgx_group_info", "mgx_group_comm_info", "mgx_group_extract_device", "mgx_group_extract_host"]
@@ -111,6 +113,17 @@ class SummaryOutputs(ctypes.Structure):
                 ("loudness_specific", ctypes.c_void_p), ("mfcc", ctypes.c_void_p),
                 ("amplitude_spectrum", ctypes.c_void_p), ("power_spectrum", ctypes.c_void_p),
                 ("mel_bands", ctypes.c_void_p)]
+
+
+DELTA_MAX_WIDTH = 8  # MGX_DELTA_MAX_WIDTH
+# the fields whose delta rows a summary call pools (mgx_delta_summaries): SUMMARY_FEATURES less the spectra
+DELTA_FEATURES = SCALAR_NAMES + ["loudness", "mfcc", "melBands"]
+
+
+class DeltaSummaries(ctypes.Structure):
+    """mgx_delta_summaries: the summaries of the delta and second-order rows (the mgx_summarize_deltas_* calls)."""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("width", ctypes.c_uint32),
+                ("delta", ctypes.POINTER(SummaryOutputs)), ("delta2", ctypes.POINTER(SummaryOutputs))]
 
 
 class HostTables(ctypes.Structure):
@@ -205,6 +218,17 @@ def lib():
                                            ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p]
         L.mgx_summarize_host.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64,
                                          ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(Outputs), aux, summ]
+        dsum = ctypes.POINTER(DeltaSummaries)
+        L.mgx_delta_device.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p,
+                                       ctypes.c_uint64, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+        L.mgx_summarize_deltas_workspace_bytes.argtypes = [ctypes.c_void_p, ctypes.POINTER(Outputs), aux, summ, dsum,
+                                                           ctypes.c_uint64, ctypes.c_uint64, u64p]
+        L.mgx_summarize_deltas_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p,
+                                                  ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(Outputs), aux,
+                                                  summ, dsum, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p]
+        L.mgx_summarize_deltas_host.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p,
+                                                ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(Outputs), aux,
+                                                summ, dsum]
         L.mgx_shard_range.argtypes = [ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, u64p, u64p]
         L.mgx_packed_layout.argtypes = [ctypes.POINTER(PlanDesc), ctypes.c_uint32, ctypes.c_uint64, u64p]
         L.mgx_packed_layout.restype = ctypes.c_uint64
@@ -482,13 +506,51 @@ class Plan:
                                          _aux_ref(outputs), ctypes.byref(summary), ctypes.c_void_p(workspace_ptr),
                                          workspace_bytes, ctypes.c_void_p(stream or 0)))
 
-    def summarize_gather_torch(self, samples, starts, frame_offsets, features, per_frame=(), stream=None):
+    def _delta_summaries(self, S, features, deltas, alloc):
+        """deltas = (width, order): a DeltaSummaries over arrays alloc(shape) for the delta (and at order 2 the
+        second-order) rows of `features`, and the arrays by name as _summary_outputs gives them (None at order 1
+        for the second). Spectrum features pass through: the library refuses them with its own message."""
+        width, order = deltas
+        if order not in (1, 2):
+            raise ValueError("delta order %r: 1 or 2" % (order,))
+        d1, so1 = self._summary_outputs(S, features, alloc)
+        d2, so2 = self._summary_outputs(S, features, alloc) if order == 2 else (None, None)
+        ds = DeltaSummaries()
+        ds.struct_size = ctypes.sizeof(DeltaSummaries)
+        ds.width = width
+        ds.delta = ctypes.pointer(so1)
+        if so2 is not None:
+            ds.delta2 = ctypes.pointer(so2)
+        ds.keep = (so1, so2)  # (the structs the pointers name live as long as this one)
+        return d1, d2, ds
+
+    def summarize_deltas_workspace_bytes(self, outputs, summary, deltas, num_frames, num_signals):
+        """mgx_summarize_deltas_workspace_bytes (host only); deltas: a DeltaSummaries or None."""
+        b = ctypes.c_uint64()
+        check(lib().mgx_summarize_deltas_workspace_bytes(self._h, ctypes.byref(outputs), _aux_ref(outputs), ctypes.byref(summary),
+                                                         None if deltas is None else ctypes.byref(deltas), num_frames,
+                                                         num_signals, ctypes.byref(b)))
+        return b.value
+
+    def summarize_deltas_device(self, samples_ptr, num_samples, starts_ptr, num_frames, offsets_ptr, num_signals, outputs,
+                                summary, deltas, workspace_ptr, workspace_bytes, stream=None):
+        """mgx_summarize_deltas_device on device pointers (async on `stream`); deltas: a DeltaSummaries or None."""
+        check(lib().mgx_summarize_deltas_device(self._h, ctypes.c_void_p(samples_ptr), num_samples, ctypes.c_void_p(starts_ptr),
+                                                num_frames, ctypes.c_void_p(offsets_ptr), num_signals, ctypes.byref(outputs),
+                                                _aux_ref(outputs), ctypes.byref(summary),
+                                                None if deltas is None else ctypes.byref(deltas),
+                                                ctypes.c_void_p(workspace_ptr), workspace_bytes, ctypes.c_void_p(stream or 0)))
+
+    def summarize_gather_torch(self, samples, starts, frame_offsets, features, per_frame=(), stream=None, deltas=None):
         """extract_gather_torch with every signal's rows pooled on the device: signal s owns rows
         [frame_offsets[s], frame_offsets[s + 1]) (int64 CUDA tensors, or anything numpy turns into one). Returns
         (summaries, rows): per pooled field a float64 CUDA tensor (S, 4, width) of mean, variance, min, max, and
         the per-frame tensors of the features named in `per_frame`. The workspace is allocated here and handed to
         torch's allocator again when this returns, which orders its reuse after the launch on torch's current
-        stream: a caller who passes another stream synchronises it before allocating again."""
+        stream: a caller who passes another stream synchronises it before allocating again.
+        deltas = (width, order): the rows' regression deltas of that half-width are pooled too
+        (mgx_summarize_deltas_device), and the result is (summaries, rows, delta_summaries, delta2_summaries), the
+        last None at order 1."""
         import torch
         assert samples.is_cuda and samples.dtype == torch.float32 and samples.is_contiguous() and samples.dim() == 1
         dev = samples.device
@@ -502,16 +564,25 @@ class Plan:
         F, S = starts.shape[0], frame_offsets.shape[0] - 1
         rows, o = self.alloc_outputs(F, per_frame, device=dev)
         summ, so = self._summary_outputs(S, features, lambda shape: torch.empty(shape, dtype=torch.float64, device=dev))
-        nbytes = self.summary_workspace_bytes(o, so, F, S)
-        ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
         if stream is None:
             stream = torch.cuda.current_stream(dev).cuda_stream
+        if deltas is not None:
+            d1, d2, ds = self._delta_summaries(S, features, deltas,
+                                               lambda shape: torch.empty(shape, dtype=torch.float64, device=dev))
+            nbytes = self.summarize_deltas_workspace_bytes(o, so, ds, F, S)
+            ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+            self.summarize_deltas_device(samples.data_ptr(), samples.shape[0], starts.data_ptr(), F, frame_offsets.data_ptr(), S,
+                                         o, so, ds, ws.data_ptr(), nbytes, stream)
+            return summ, rows, d1, d2
+        nbytes = self.summary_workspace_bytes(o, so, F, S)
+        ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
         self.summarize_device(samples.data_ptr(), samples.shape[0], starts.data_ptr(), F, frame_offsets.data_ptr(), S, o, so,
                               ws.data_ptr(), nbytes, stream)
         return summ, rows
 
-    def summarize_gather(self, samples, starts, frame_offsets, features, per_frame=()):
-        """Host numpy in / numpy out (mgx_summarize_host): (summaries, rows) as summarize_gather_torch gives them."""
+    def summarize_gather(self, samples, starts, frame_offsets, features, per_frame=(), deltas=None):
+        """Host numpy in / numpy out (mgx_summarize_host): (summaries, rows) as summarize_gather_torch gives them;
+        with deltas = (width, order) (mgx_summarize_deltas_host), (summaries, rows, delta_summaries, delta2_summaries)."""
         samples = np.ascontiguousarray(samples, dtype=np.float32)
         starts = np.ascontiguousarray(starts, dtype=np.uint64)
         frame_offsets = np.ascontiguousarray(frame_offsets, dtype=np.uint64)
@@ -519,17 +590,27 @@ class Plan:
         S = frame_offsets.size - 1
         rows, o = self._host_outputs(starts.size, per_frame)
         summ, so = self._summary_outputs(S, features, lambda shape: np.empty(shape, np.float64))
+        if deltas is not None:
+            d1, d2, ds = self._delta_summaries(S, features, deltas, lambda shape: np.empty(shape, np.float64))
+            check(lib().mgx_summarize_deltas_host(self._h, samples.ctypes.data, samples.size, starts.ctypes.data, starts.size,
+                                                  frame_offsets.ctypes.data, S, ctypes.byref(o), _aux_ref(o), ctypes.byref(so),
+                                                  ctypes.byref(ds)))
+            return summ, rows, d1, d2
         check(lib().mgx_summarize_host(self._h, samples.ctypes.data, samples.size, starts.ctypes.data, starts.size,
                                        frame_offsets.ctypes.data, S, ctypes.byref(o), _aux_ref(o), ctypes.byref(so)))
         return summ, rows
 
-    def summarize_signals(self, signals, hop, features, per_frame=()):
+    def summarize_signals(self, signals, hop, features, per_frame=(), deltas=None):
         """A list of 1-D host signals in one call, pooled per signal: returns (summaries, frame_offsets), summaries
         being {name: ndarray (S, 4, width)} of mean, variance, min, max (STATS) over each signal's buffers; with
-        `per_frame`, (summaries, frame_offsets, rows), rows as extract_signals gives them for those features."""
+        `per_frame`, (summaries, frame_offsets, rows), rows as extract_signals gives them for those features.
+        With deltas = (width, order): (summaries, rows, delta_summaries, delta2_summaries) as summarize_gather gives
+        them (frame_offsets: signals_frame_starts of the signals' lengths)."""
         signals = [np.ascontiguousarray(x, dtype=np.float32).ravel() for x in signals]
         starts, frame_offsets = signals_frame_starts([x.size for x in signals], self.n, hop)
         samples = np.concatenate(signals) if signals else np.empty(0, np.float32)
+        if deltas is not None:
+            return self.summarize_gather(samples, starts, frame_offsets, features, per_frame, deltas=deltas)
         summ, rows = self.summarize_gather(samples, starts, frame_offsets, features, per_frame)
         return (summ, frame_offsets, rows) if per_frame else (summ, frame_offsets)
 
@@ -758,3 +839,36 @@ def pcm_decode_device(pcm_u8, sample_frames, fmt, channels, channel, out, stream
         stream = torch.cuda.current_stream(out.device).cuda_stream
     check(lib().mgx_pcm_decode_device(ctypes.c_void_p(pcm_u8.data_ptr()), sample_frames, fmt, channels, channel,
                                       ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(stream)))
+
+
+def delta_device(rows_ptr, num_frames, cols, rows_f64, offsets_ptr, num_signals, width, delta_ptr, delta2_ptr, stream=None):
+    """mgx_delta_device on device pointers (async on `stream`); a pointer may be None."""
+    check(lib().mgx_delta_device(ctypes.c_void_p(rows_ptr or 0), num_frames, cols, 1 if rows_f64 else 0,
+                                 ctypes.c_void_p(offsets_ptr or 0), num_signals, width, ctypes.c_void_p(delta_ptr or 0),
+                                 ctypes.c_void_p(delta2_ptr or 0), ctypes.c_void_p(stream or 0)))
+
+
+def delta_torch(rows, frame_offsets=None, width=2, order=2, stream=None):
+    """The regression deltas of `rows`, a (F,) or (F, cols) float32 or float64 CUDA tensor, within each signal:
+    signal s owns rows [frame_offsets[s], frame_offsets[s + 1]) (an int64 CUDA tensor, or anything numpy turns
+    into one; None: one signal, every row). Returns the tuple of tensors of rows' shape, (delta,) at order 1 and
+    (delta, delta2) at order 2; rows that belong to no signal are 0."""
+    import torch
+    assert rows.is_cuda and rows.is_contiguous() and rows.dim() in (1, 2) and rows.dtype in (torch.float32, torch.float64)
+    if order not in (1, 2):
+        raise ValueError("delta order %r: 1 or 2" % (order,))
+    F = rows.shape[0]
+    cols = rows.shape[1] if rows.dim() == 2 else 1
+    S = 0
+    if frame_offsets is not None:
+        if not torch.is_tensor(frame_offsets):
+            frame_offsets = torch.from_numpy(np.ascontiguousarray(frame_offsets, dtype=np.uint64).view(np.int64)).to(rows.device)
+        assert frame_offsets.is_cuda and frame_offsets.dtype == torch.int64 and frame_offsets.is_contiguous()
+        assert frame_offsets.dim() == 1 and frame_offsets.shape[0] >= 1
+        S = frame_offsets.shape[0] - 1
+    out = tuple(torch.zeros_like(rows) for _ in range(order))
+    if stream is None:
+        stream = torch.cuda.current_stream(rows.device).cuda_stream
+    delta_device(rows.data_ptr(), F, cols, rows.dtype == torch.float64, None if frame_offsets is None else frame_offsets.data_ptr(),
+                 S, width, out[0].data_ptr(), out[1].data_ptr() if order == 2 else None, stream)
+    return out

@@ -3133,6 +3133,134 @@ hipError_t launch_summary_final(const SummaryArgs& a, hipStream_t stream) {
   return hipGetLastError();
 }
 
+// ---- Deltas (mgx_delta_device, mgx_summarize_deltas_*): the regression delta of every row within its signal ----
+// A stencil along the row axis, memory-bound. A workgroup owns a tile of whole rows (tile_rows of them, about
+// 4096 elements) and its threads walk the tile's flattened elements, so loads and stores are coalesced whatever
+// cols is (1, 13, 64, a spectrum's N/2), and the 2 W neighbour rows an element reads are the ones its
+// neighbouring threads and tiles read: they come from L1 / L2. The row's signal -- the clamp bounds -- is looked
+// up once per row of the tile (a binary search of the table by the tile's first threads, kept in LDS), and an
+// element finds its row by a multiplication with the reciprocal of cols, exact for the tile's few thousand
+// elements: no 64-bit division and no search per element. No atomics; one writer per element; a value depends
+// on its signal's rows alone, so on no grid.
+namespace {
+
+constexpr uint32_t kDeltaTileRows = 256;     // at most: one thread of the workgroup resolves one row
+constexpr uint32_t kDeltaTileElems = 4096;   // a tile's elements, about (a whole row at least)
+
+struct DeltaArgs {
+  const void* rows;
+  void* out;
+  const uint64_t* table;  // null: one signal, rows [0, num_frames)
+  uint64_t num_signals, num_frames, ntiles;
+  uint64_t rcp;           // floor(2^32 / cols) + 1: element j of a tile is in its row (j * rcp) >> 32 (tile_rows > 1)
+  uint32_t cols, width, tile_rows;
+};
+
+// The delta of column c at row t of the signal [a, last]: the sum in ascending n, each term a difference, a
+// product and an addition in float64 (-ffp-contract=off: none fused), one division, one rounding to T.
+// x: the array at column c of row 0.
+template <typename T>
+__device__ __forceinline__ T delta_value(const T* __restrict__ x, uint64_t cols, uint64_t t, uint64_t a, uint64_t last, uint32_t W,
+                                         double D) {
+  double acc = 0.0;
+  for (uint32_t n = 1; n <= W; ++n) {
+    const uint64_t up = t + n < last ? t + n : last, um = t >= a + n ? t - n : a;
+    acc += (double)n * ((double)x[up * cols] - (double)x[um * cols]);
+  }
+  return (T)(acc / D);
+}
+
+// kSecond: the delta of the delta rows, each of those computed here as delta_value gives (and rounds) it
+template <typename T, bool kSecond>
+__global__ __launch_bounds__(256) void delta_kernel(DeltaArgs g) {
+  __shared__ uint64_t sig_a[kDeltaTileRows], sig_b[kDeltaTileRows];
+  const T* __restrict__ const rows = static_cast<const T*>(g.rows);
+  T* __restrict__ const out = static_cast<T*>(g.out);
+  const uint32_t W = g.width;
+  const double D = (double)(W * (W + 1) * (2 * W + 1) / 3);
+  const uint64_t cols = g.cols, T_ = g.num_frames;
+  for (uint64_t tile = blockIdx.x; tile < g.ntiles; tile += gridDim.x) {
+    const uint64_t r0 = tile * g.tile_rows;
+    const uint32_t nr = T_ - r0 < g.tile_rows ? (uint32_t)(T_ - r0) : g.tile_rows;
+    if (threadIdx.x < nr) {
+      // the row's signal: the last s with table[s] <= t; [a, b) empty when the row belongs to none
+      const uint64_t t = r0 + threadIdx.x;
+      uint64_t a = 0, b = T_;
+      if (g.table) {
+        uint64_t lo = 0, hi = g.num_signals + 1;  // the first entry above t
+        while (lo < hi) {
+          const uint64_t mid = lo + (hi - lo) / 2;
+          if (g.table[mid] <= t) lo = mid + 1;
+          else hi = mid;
+        }
+        a = b = 0;
+        if (lo > 0 && lo <= g.num_signals) {
+          a = g.table[lo - 1];
+          b = g.table[lo];
+          a = a < T_ ? a : T_;
+          b = b < T_ ? b : T_;
+        }
+      }
+      sig_a[threadIdx.x] = a;
+      sig_b[threadIdx.x] = b;
+    }
+    __syncthreads();
+    // (nr cols: at most kDeltaTileElems, or one row of cols < 2^32 elements)
+    const uint64_t ne = (uint64_t)nr * g.cols;
+    for (uint64_t j = threadIdx.x; j < ne; j += 256) {
+      const uint32_t row = g.tile_rows > 1 ? (uint32_t)((j * g.rcp) >> 32) : 0u;
+      const uint32_t c = (uint32_t)j - row * g.cols;
+      const uint64_t t = r0 + row, a = sig_a[row], b = sig_b[row];
+      if (!(t >= a && t < b)) continue;  // (whatever the table holds: a <= t <= b - 1 < num_frames from here on)
+      const uint64_t last = b - 1;
+      const T* const x = rows + c;
+      T v;
+      if (!kSecond) {
+        v = delta_value(x, cols, t, a, last, W, D);
+      } else {
+        double acc = 0.0;
+        for (uint32_t n = 1; n <= W; ++n) {
+          const uint64_t up = t + n < last ? t + n : last, um = t >= a + n ? t - n : a;
+          acc += (double)n * ((double)delta_value(x, cols, up, a, last, W, D) - (double)delta_value(x, cols, um, a, last, W, D));
+        }
+        v = (T)(acc / D);
+      }
+      out[t * cols + c] = v;
+    }
+    __syncthreads();
+  }
+}
+
+}  // namespace
+
+hipError_t launch_delta(const void* rows, void* out, uint64_t num_frames, uint32_t cols, bool f64, const uint64_t* table,
+                        uint64_t num_signals, uint32_t width, bool second, hipStream_t stream) {
+  if (num_frames == 0) return hipSuccess;
+  if (cols == 0 || width == 0 || width > MGX_DELTA_MAX_WIDTH) return hipErrorInvalidValue;
+  DeltaArgs g{};
+  g.rows = rows;
+  g.out = out;
+  g.table = table;
+  g.num_signals = num_signals;
+  g.num_frames = num_frames;
+  g.cols = cols;
+  g.width = width;
+  g.tile_rows = kDeltaTileElems / cols;
+  if (g.tile_rows < 1) g.tile_rows = 1;
+  if (g.tile_rows > kDeltaTileRows) g.tile_rows = kDeltaTileRows;
+  g.rcp = (1ull << 32) / cols + 1;
+  g.ntiles = (num_frames + g.tile_rows - 1) / g.tile_rows;
+  const unsigned grid = (unsigned)(g.ntiles < 16384 ? g.ntiles : 16384);
+  if (f64) {
+    if (second) hipLaunchKernelGGL((delta_kernel<double, true>), dim3(grid), dim3(256), 0, stream, g);
+    else hipLaunchKernelGGL((delta_kernel<double, false>), dim3(grid), dim3(256), 0, stream, g);
+  } else {
+    if (second) hipLaunchKernelGGL((delta_kernel<float, true>), dim3(grid), dim3(256), 0, stream, g);
+    else hipLaunchKernelGGL((delta_kernel<float, false>), dim3(grid), dim3(256), 0, stream, g);
+  }
+  return hipGetLastError();
+}
+
 }  // namespace mgx
 
 #if MGX_WAVE_TIMES

@@ -225,6 +225,13 @@ struct SummaryArgs {
 hipError_t launch_summary_table(const uint64_t* raw, uint64_t* table, uint64_t num_signals, uint64_t num_frames, hipStream_t stream);
 hipError_t launch_summary_partial(const SummaryArgs& a, hipStream_t stream);
 hipError_t launch_summary_final(const SummaryArgs& a, hipStream_t stream);
+// Deltas (mgx_delta_device, mgx_summarize_deltas_*; kernels.hip delta_kernel): out(t, c) = the regression delta
+// of half-width `width` of rows (num_frames x cols, float32 or float64 as f64 says) within the row's signal,
+// signal s being rows [min(table[s], num_frames), min(table[s + 1], num_frames)) (table null: one signal, every
+// row). second: out is the delta of the delta rows, those recomputed (and rounded as stored) where they are read
+// instead of read from memory. Rows that belong to no signal are not written. One launch, asynchronous.
+hipError_t launch_delta(const void* rows, void* out, uint64_t num_frames, uint32_t cols, bool f64, const uint64_t* table,
+                        uint64_t num_signals, uint32_t width, bool second, hipStream_t stream);
 size_t extract_lds_bytes(int n, int ncoef, int nfilt, bool chain);
 size_t lds_image_bytes(int n, int ncoef, int nfilt);  // DevTables::lds_image, a multiple of 16
 hipError_t launch_lds_image(int n, int precision, int mode, const KernelArgs& a, void* image, hipStream_t stream);

@@ -492,6 +492,10 @@ struct mgx_plan {
   // allocation, grown when a call needs more)
   unsigned char* s_sum = nullptr;
   size_t s_sum_bytes = 0;
+  // mgx_summarize_deltas_host: the delta'd fields' rows of the whole call, their delta and second-order rows, a
+  // table, shifts, partials and summaries of their own (one allocation beside s_sum, grown when a call needs more)
+  unsigned char* s_delta = nullptr;
+  size_t s_delta_bytes = 0;
   hipStream_t s_copy = nullptr, s_comp = nullptr;
   hipEvent_t ev_loaded[2] = {nullptr, nullptr}, ev_done[2] = {nullptr, nullptr}, ev_back[2] = {nullptr, nullptr};
   // small host batches (kSmallBatchFrames): pinned, device-mapped, coherent host buffers
@@ -842,6 +846,7 @@ int mgx_plan_destroy(mgx_plan* p) {
       if (ev) (void)hipEventDestroy(ev);
   }
   if (p->s_sum) (void)hipFree(p->s_sum);
+  if (p->s_delta) (void)hipFree(p->s_delta);
   if (p->s_copy) (void)hipStreamDestroy(p->s_copy);
   if (p->s_comp) (void)hipStreamDestroy(p->s_comp);
   if (p->s_res) (void)hipStreamDestroy(p->s_res);
@@ -1748,14 +1753,16 @@ struct SummaryLayout {
   uint64_t table, shift, part, result, total;
 };
 
-SummaryLayout summary_layout(const mgx_plan_desc& d, uint32_t extra, uint32_t cols, uint64_t nframes, uint64_t nsignals, bool result) {
+// deltas (mgx_summarize_deltas_device): the arrays and the table are kept for the delta rows even when no field is pooled.
+SummaryLayout summary_layout(const mgx_plan_desc& d, uint32_t extra, uint32_t cols, uint64_t nframes, uint64_t nsignals, bool result,
+                             bool deltas = false) {
   SummaryLayout l{};
   auto take = [&l](uint64_t bytes) {
     const uint64_t at = l.total;
     l.total += (bytes + 255) / 256 * 256;
     return at;
   };
-  if (cols == 0 || nsignals == 0 || nframes == 0) return l;
+  if ((cols == 0 && !deltas) || nsignals == 0 || nframes == 0) return l;
   take(mgx::out_layout(d, extra, nframes, l.frames));
   l.table = take((nsignals + 1) * sizeof(uint64_t));
   l.shift = take(nsignals * cols * sizeof(double));
@@ -1776,9 +1783,235 @@ int summary_inputs(const mgx_plan* p, const float* samples, uint64_t num_samples
   return MGX_OK;
 }
 
+// mgx_summarize_deltas_*: the caller's mgx_delta_summaries as two lists of summary fields (k = 0: the delta
+// rows', 1: the second-order rows'; destinations the caller's arrays), and the fields whose rows of each order
+// the call has to hold: the second order is the delta of the first, so rows[0] has every field either names.
+struct DeltaReq {
+  uint32_t width = 0;
+  SummaryFields sf[2];
+  uint32_t rows[2] = {0, 0};
+  bool any() const { return rows[0] != 0; }
+};
+
+int delta_request(const mgx_plan* p, const mgx_delta_summaries* ds, DeltaReq* q) {
+  if (!ds) return MGX_OK;
+  if (ds->struct_size != sizeof(mgx_delta_summaries))
+    return fail(MGX_E_INVALID_ARGUMENT, "mgx_delta_summaries.struct_size is %u, expected %zu", ds->struct_size,
+                sizeof(mgx_delta_summaries));
+  if (ds->width < 1 || ds->width > MGX_DELTA_MAX_WIDTH)
+    return fail(MGX_E_INVALID_ARGUMENT, "mgx_delta_summaries.width is %u, expected 1..%d", ds->width, MGX_DELTA_MAX_WIDTH);
+  q->width = ds->width;
+  const mgx_summary_outputs* const so[2] = {ds->delta, ds->delta2};
+  for (int k = 0; k < 2; ++k) {
+    if (!so[k]) continue;
+    const int rc = check_summary(so[k]);
+    if (rc) return rc;
+    if (so[k]->amplitude_spectrum || so[k]->power_spectrum)
+      return fail(MGX_E_UNSUPPORTED, "deltas of a spectrum are not pooled (mgx_delta_summaries.%s): mgx_delta_device takes its rows",
+                  k ? "delta2" : "delta");
+    if (p) summary_fields(p, so[k], &q->sf[k]);  // (the checks above come ahead of the plan's own, as check_summary does)
+  }
+  q->rows[1] = q->sf[1].pooled;
+  q->rows[0] = q->sf[0].pooled | q->sf[1].pooled;
+  return MGX_OK;
+}
+
+// What the deltas add to the buffer a summary call works in, from `base` bytes on: the delta rows of the fields
+// q.rows[0] and the second-order rows of q.rows[1] (each laid out as mgx::out_layout lays per-frame arrays out),
+// a table of their own when the buffer holds none (the host call's), and per order the shifts, the partials and
+// (host call) the summaries. Everything 256-byte aligned; total: base when there is nothing to keep.
+struct DeltaLayout {
+  uint64_t rows[2][mgx::kOutFields];
+  uint64_t table, shift[2], part[2], result[2], total;
+};
+
+DeltaLayout delta_layout(const mgx_plan_desc& d, const DeltaReq& q, uint64_t nframes, uint64_t nsignals, bool host, uint64_t base) {
+  DeltaLayout l{};
+  l.total = base;
+  auto take = [&l](uint64_t bytes) {
+    const uint64_t at = l.total;
+    l.total += (bytes + 255) / 256 * 256;
+    return at;
+  };
+  if (!q.any() || nsignals == 0 || nframes == 0) return l;
+  for (int k = 0; k < 2; ++k) {
+    const uint64_t at = l.total;
+    take(mgx::out_layout(d, q.rows[k], nframes, l.rows[k]));
+    for (int i = 0; i < mgx::kOutFields; ++i)
+      if (l.rows[k][i] != UINT64_MAX) l.rows[k][i] += at;
+  }
+  if (host) l.table = take((nsignals + 1) * sizeof(uint64_t));
+  for (int k = 0; k < 2; ++k) {
+    const uint64_t cols = q.sf[k].a.cols;
+    l.shift[k] = take(nsignals * cols * sizeof(double));
+    l.part[k] = take((nframes / mgx::kSummaryBlock + nsignals + 1) * mgx::kSummaryWords * cols * sizeof(double));
+    if (host) l.result[k] = take(nsignals * MGX_NUM_STATS * cols * sizeof(double));
+  }
+  return l;
+}
+
+// The operator and the pooling of a deltas call, on `st`: x holds the rows of every field of q.rows[0] (nframes
+// of them), buf the arrays of `l`, table the num_signals + 1 offsets as the summary kernels read them (device
+// memory). Per field the delta rows, then (q.rows[1]) their delta: two passes, the second over the stored rows;
+// then the summary kernels over each order's rows into the destinations of q.sf[k] (device pointers here).
+int delta_pool(const mgx_plan_desc& d, DeltaReq& q, const mgx::Outputs& x, unsigned char* buf, const DeltaLayout& l,
+               const uint64_t* table, uint64_t nframes, uint64_t nsignals, hipStream_t st) {
+  hipError_t e = hipSuccess;
+  for (int i = 0; i < mgx::kOutFields && e == hipSuccess; ++i) {
+    if (!((q.rows[0] >> i) & 1u)) continue;
+    const bool f64 = i < MGX_NUM_SCALARS && d.scalar_f64;
+    const uint32_t cols = (uint32_t)(mgx::out_field_bytes(d, i) / (f64 ? 8 : 4));
+    e = mgx::launch_delta(mgx::out_field(x, i), buf + l.rows[0][i], nframes, cols, f64, table, nsignals, q.width, false, st);
+    if (e == hipSuccess && ((q.rows[1] >> i) & 1u))
+      e = mgx::launch_delta(buf + l.rows[0][i], buf + l.rows[1][i], nframes, cols, f64, table, nsignals, q.width, false, st);
+  }
+  for (int k = 0; k < 2 && e == hipSuccess; ++k) {
+    mgx::SummaryArgs& a = q.sf[k].a;
+    if (a.cols == 0) continue;
+    for (uint32_t i = 0; i < a.nfields; ++i) a.f[i].src = buf + l.rows[k][q.sf[k].index[i]];
+    a.num_signals = nsignals;
+    a.num_frames = nframes;
+    a.table = table;
+    a.shift = reinterpret_cast<double*>(buf + l.shift[k]);
+    a.part = reinterpret_cast<double*>(buf + l.part[k]);
+    a.row0 = 0;
+    a.rows = nframes;
+    a.slot0 = 0;
+    a.nslots = nframes / mgx::kSummaryBlock + nsignals;
+    e = mgx::launch_summary_partial(a, st);
+    if (e == hipSuccess) e = mgx::launch_summary_final(a, st);
+  }
+  return e == hipSuccess ? (int)MGX_OK : hip_fail(e, "delta and summary kernel launch");
+}
+
+int summarize_host_impl(mgx_plan* p, const float* samples, uint64_t num_samples, const uint64_t* starts, uint64_t nframes,
+                        const uint64_t* frame_offsets, uint64_t nsignals, const mgx_outputs* outputs, const mgx_aux_outputs* aux,
+                        const mgx_summary_outputs* summary, const mgx_delta_summaries* deltas);
+
 }  // namespace
 
 extern "C" {
+
+int mgx_delta_device(const void* rows, uint64_t num_frames, uint32_t cols, uint32_t rows_f64, const uint64_t* frame_offsets,
+                     uint64_t num_signals, uint32_t width, void* delta, void* delta2, void* stream) {
+  if (cols == 0) return fail(MGX_E_INVALID_ARGUMENT, "cols is 0");
+  if (width < 1 || width > MGX_DELTA_MAX_WIDTH)
+    return fail(MGX_E_INVALID_ARGUMENT, "width is %u, expected 1..%d", width, MGX_DELTA_MAX_WIDTH);
+  if (rows_f64 > 1) return fail(MGX_E_INVALID_ARGUMENT, "rows_f64 is %u, expected 0 or 1", rows_f64);
+  if (!delta && !delta2) return fail(MGX_E_INVALID_ARGUMENT, "delta and delta2 are both NULL");
+  if (delta == delta2) return fail(MGX_E_INVALID_ARGUMENT, "delta and delta2 are the same array");
+  if (rows && (delta == rows || delta2 == rows)) return fail(MGX_E_INVALID_ARGUMENT, "an output is the rows' own array");
+  if (num_signals > 0 && !frame_offsets) return fail(MGX_E_INVALID_ARGUMENT, "frame_offsets is NULL");
+  if (num_frames == 0) return MGX_OK;
+  if (!rows) return fail(MGX_E_INVALID_ARGUMENT, "rows is NULL");
+  // (frame_offsets with num_signals = 0: a table of one entry, no signal, nothing written)
+  hipError_t e = hipSuccess;
+  if (delta) {
+    e = mgx::launch_delta(rows, delta, num_frames, cols, rows_f64 != 0, frame_offsets, num_signals, width, false, (hipStream_t)stream);
+    if (e == hipSuccess && delta2)
+      e = mgx::launch_delta(delta, delta2, num_frames, cols, rows_f64 != 0, frame_offsets, num_signals, width, false, (hipStream_t)stream);
+  } else {
+    // no array for the delta rows: each one is recomputed where the second order reads it
+    e = mgx::launch_delta(rows, delta2, num_frames, cols, rows_f64 != 0, frame_offsets, num_signals, width, true, (hipStream_t)stream);
+  }
+  return e == hipSuccess ? MGX_OK : hip_fail(e, "delta kernel launch");
+}
+
+int mgx_summarize_deltas_workspace_bytes(const mgx_plan* p, const mgx_outputs* o, const mgx_aux_outputs* aux,
+                                         const mgx_summary_outputs* summary, const mgx_delta_summaries* deltas, uint64_t nframes,
+                                         uint64_t nsignals, uint64_t* bytes) {
+  if (!deltas) return mgx_summary_workspace_bytes(p, o, aux, summary, nframes, nsignals, bytes);
+  if (!bytes) return fail(MGX_E_INVALID_ARGUMENT, "bytes is NULL");
+  const mgx_outputs none{};
+  mgx::Outputs x;
+  DeltaReq q;
+  int rc = check_summary(summary);
+  if (rc || (rc = delta_request(p, deltas, &q)) || (rc = make_outputs(p, o ? o : &none, aux, &x))) return rc;
+  SummaryFields sf;
+  summary_fields(p, summary, &sf);
+  const uint32_t extra = (sf.pooled | q.rows[0]) & ~mgx::out_requested(x);
+  const SummaryLayout l = summary_layout(p->d, extra, sf.a.cols, nframes, nsignals, false, q.any());
+  *bytes = delta_layout(p->d, q, nframes, nsignals, false, l.total).total;
+  return MGX_OK;
+}
+
+int mgx_summarize_deltas_device(mgx_plan* p, const float* samples, uint64_t num_samples, const uint64_t* starts, uint64_t nframes,
+                                const uint64_t* frame_offsets, uint64_t nsignals, const mgx_outputs* o, const mgx_aux_outputs* aux,
+                                const mgx_summary_outputs* summary, const mgx_delta_summaries* deltas, void* workspace,
+                                uint64_t workspace_bytes, void* stream) {
+  if (!deltas)
+    return mgx_summarize_device(p, samples, num_samples, starts, nframes, frame_offsets, nsignals, o, aux, summary, workspace,
+                                workspace_bytes, stream);
+  const mgx_outputs none{};
+  mgx::Outputs x;
+  DeltaReq q;
+  int rc = check_summary(summary);
+  if (rc || (rc = delta_request(p, deltas, &q)) || (rc = make_outputs(p, o ? o : &none, aux, &x))) return rc;
+  SummaryFields sf;
+  summary_fields(p, summary, &sf);
+  if (!q.any())  // (no field named in either: the summary call)
+    return mgx_summarize_device(p, samples, num_samples, starts, nframes, frame_offsets, nsignals, o, aux, summary, workspace,
+                                workspace_bytes, stream);
+  if ((rc = summary_inputs(p, samples, num_samples, starts, nframes, frame_offsets, nsignals))) return rc;
+  if ((rc = check_outputs(x))) return rc;
+  const uint32_t extra = (sf.pooled | q.rows[0]) & ~mgx::out_requested(x);
+  const SummaryLayout l = summary_layout(p->d, extra, sf.a.cols, nframes, nsignals, false, true);
+  const DeltaLayout dl = delta_layout(p->d, q, nframes, nsignals, false, l.total);
+  if (workspace_bytes < dl.total || (dl.total > 0 && !workspace))
+    return fail(MGX_E_INVALID_ARGUMENT, "the workspace holds %llu bytes, the call needs %llu (mgx_summarize_deltas_workspace_bytes)",
+                (unsigned long long)workspace_bytes, (unsigned long long)dl.total);
+  if (dl.total > 0 && reinterpret_cast<uintptr_t>(workspace) % 256 != 0)
+    return fail(MGX_E_INVALID_ARGUMENT, "the workspace is not 256-byte aligned");
+  unsigned char* const ws = static_cast<unsigned char*>(workspace);
+  // the launch's outputs: the caller's per-frame arrays, and for the other pooled or delta'd fields the workspace's
+  mgx::Outputs u = x;
+  if (l.total > 0)
+    for (int i = 0; i < mgx::kOutFields; ++i)
+      if (l.frames[i] != UINT64_MAX) mgx::out_field(u, i) = ws + l.frames[i];
+  if (nframes > 0) {
+    const GatherLaunch g{starts, num_samples};
+    LaunchOpts opt;
+    opt.gather = &g;
+    if ((rc = extract_device_impl(p, samples, nframes, (uint64_t)p->n, l.total > 0 ? &u : &x, stream, opt))) return rc;
+  }
+  if (nsignals == 0) return MGX_OK;
+  hipError_t e = hipSetDevice(p->d.device);
+  if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
+  mgx::SummaryArgs& a = sf.a;
+  a.num_signals = nsignals;
+  a.num_frames = nframes;
+  uint64_t* const table = nframes > 0 ? reinterpret_cast<uint64_t*>(ws + l.table) : nullptr;
+  if (nframes > 0) {
+    // the base summaries, exactly as mgx_summarize_device forms them; the table serves the deltas too
+    for (uint32_t i = 0; i < a.nfields; ++i) a.f[i].src = mgx::out_field(u, sf.index[i]);
+    a.table = table;
+    a.shift = reinterpret_cast<double*>(ws + l.shift);
+    a.part = reinterpret_cast<double*>(ws + l.part);
+    a.row0 = 0;
+    a.rows = nframes;
+    a.slot0 = 0;
+    a.nslots = nframes / mgx::kSummaryBlock + nsignals;
+    e = mgx::launch_summary_table(frame_offsets, table, nsignals, nframes, (hipStream_t)stream);
+    if (e == hipSuccess) e = mgx::launch_summary_partial(a, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, "summary kernel launch");
+  }
+  e = mgx::launch_summary_final(a, (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(e, "summary kernel launch");
+  if (nframes > 0) return delta_pool(p->d, q, u, ws, dl, table, nframes, nsignals, (hipStream_t)stream);
+  // no buffers: every signal is empty, NaN in all four (the final kernel reads neither rows nor table)
+  for (int k = 0; k < 2 && e == hipSuccess; ++k) {
+    q.sf[k].a.num_signals = nsignals;
+    q.sf[k].a.num_frames = 0;
+    e = mgx::launch_summary_final(q.sf[k].a, (hipStream_t)stream);
+  }
+  return e == hipSuccess ? MGX_OK : hip_fail(e, "summary kernel launch");
+}
+
+int mgx_summarize_deltas_host(mgx_plan* p, const float* samples, uint64_t num_samples, const uint64_t* starts, uint64_t nframes,
+                              const uint64_t* frame_offsets, uint64_t nsignals, const mgx_outputs* outputs,
+                              const mgx_aux_outputs* aux, const mgx_summary_outputs* summary, const mgx_delta_summaries* deltas) {
+  return summarize_host_impl(p, samples, num_samples, starts, nframes, frame_offsets, nsignals, outputs, aux, summary, deltas);
+}
 
 int mgx_summary_workspace_bytes(const mgx_plan* p, const mgx_outputs* o, const mgx_aux_outputs* aux, const mgx_summary_outputs* summary,
                                 uint64_t nframes, uint64_t nsignals, uint64_t* bytes) {
@@ -1850,10 +2083,22 @@ int mgx_summarize_device(mgx_plan* p, const float* samples, uint64_t num_samples
 int mgx_summarize_host(mgx_plan* p, const float* samples, uint64_t num_samples, const uint64_t* starts, uint64_t nframes,
                        const uint64_t* frame_offsets, uint64_t nsignals, const mgx_outputs* outputs, const mgx_aux_outputs* aux,
                        const mgx_summary_outputs* summary) {
+  return summarize_host_impl(p, samples, num_samples, starts, nframes, frame_offsets, nsignals, outputs, aux, summary, nullptr);
+}
+
+}  // extern "C"
+
+namespace {
+
+// mgx_summarize_host (deltas null: nothing here differs from what it was) and mgx_summarize_deltas_host
+int summarize_host_impl(mgx_plan* p, const float* samples, uint64_t num_samples, const uint64_t* starts, uint64_t nframes,
+                        const uint64_t* frame_offsets, uint64_t nsignals, const mgx_outputs* outputs, const mgx_aux_outputs* aux,
+                        const mgx_summary_outputs* summary, const mgx_delta_summaries* deltas) {
   const mgx_outputs none{};
   mgx::Outputs x;
+  DeltaReq q;
   int rc = check_summary(summary);
-  if (rc || (rc = make_outputs(p, outputs ? outputs : &none, aux, &x))) return rc;
+  if (rc || (rc = delta_request(p, deltas, &q)) || (rc = make_outputs(p, outputs ? outputs : &none, aux, &x))) return rc;
   SummaryFields sf;
   summary_fields(p, summary, &sf);
   if ((rc = summary_inputs(p, samples, num_samples, starts, nframes, frame_offsets, nsignals))) return rc;
@@ -1877,9 +2122,12 @@ int mgx_summarize_host(mgx_plan* p, const float* samples, uint64_t num_samples, 
     // no buffers: every signal is empty, NaN in all four (nothing for the device to do)
     for (uint32_t i = 0; i < a.nfields; ++i)
       std::fill_n(a.f[i].dst, nsignals * MGX_NUM_STATS * a.f[i].width, std::nan(""));
+    for (int k = 0; k < 2; ++k)
+      for (uint32_t i = 0; i < q.sf[k].a.nfields; ++i)
+        std::fill_n(q.sf[k].a.f[i].dst, nsignals * MGX_NUM_STATS * q.sf[k].a.f[i].width, std::nan(""));
     return MGX_OK;
   }
-  if (nsignals == 0 || a.cols == 0) return gather_host_chunked(p, samples, starts, nframes, &x, nullptr);
+  if (nsignals == 0 || (a.cols == 0 && !q.any())) return gather_host_chunked(p, samples, starts, nframes, &x, nullptr);
   const SummaryLayout l = summary_layout(p->d, 0, a.cols, nframes, nsignals, true);
   hipError_t e = hipSetDevice(p->d.device);
   if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
@@ -1893,16 +2141,34 @@ int mgx_summarize_host(mgx_plan* p, const float* samples, uint64_t num_samples, 
     if (e != hipSuccess) { p->s_sum = nullptr; return hip_fail(e, "hipMalloc(summary buffers)"); }
     p->s_sum_bytes = l.total;
   }
+  // the deltas' own buffer: the delta'd fields' rows of the whole call (each chunk's copied in behind its
+  // extraction), then what delta_layout adds
+  uint64_t xoff[mgx::kOutFields];
+  const DeltaLayout dl = delta_layout(p->d, q, nframes, nsignals, true, mgx::out_layout(p->d, q.rows[0], nframes, xoff));
+  if (q.any() && p->s_delta_bytes < dl.total) {
+    if (p->s_delta) (void)hipFree(p->s_delta);
+    p->s_delta = nullptr;
+    p->s_delta_bytes = 0;
+    e = hipMalloc(reinterpret_cast<void**>(&p->s_delta), dl.total);
+    if (e != hipSuccess) { p->s_delta = nullptr; return hip_fail(e, "hipMalloc(delta rows)"); }
+    p->s_delta_bytes = dl.total;
+  }
   a.num_signals = nsignals;
   a.num_frames = nframes;
-  a.table = reinterpret_cast<const uint64_t*>(p->s_sum + l.table);
-  a.shift = reinterpret_cast<double*>(p->s_sum + l.shift);
-  a.part = reinterpret_cast<double*>(p->s_sum + l.part);
-  e = hipMemcpyAsync(p->s_sum + l.table, frame_offsets, (nsignals + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, p->s_comp);
-  if (e != hipSuccess) return hip_fail(e, "hipMemcpyAsync(frame_offsets)");
+  if (a.cols > 0) {
+    a.table = reinterpret_cast<const uint64_t*>(p->s_sum + l.table);
+    a.shift = reinterpret_cast<double*>(p->s_sum + l.shift);
+    a.part = reinterpret_cast<double*>(p->s_sum + l.part);
+    e = hipMemcpyAsync(p->s_sum + l.table, frame_offsets, (nsignals + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, p->s_comp);
+    if (e != hipSuccess) return hip_fail(e, "hipMemcpyAsync(frame_offsets)");
+  }
+  if (q.any()) {
+    e = hipMemcpyAsync(p->s_delta + dl.table, frame_offsets, (nsignals + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, p->s_comp);
+    if (e != hipSuccess) return hip_fail(e, "hipMemcpyAsync(frame_offsets)");
+  }
   ChunkHook hook;
-  hook.pooled = sf.pooled;
-  hook.after = [&](uint64_t f0, uint64_t cnt, const mgx::Outputs& d) {
+  hook.pooled = sf.pooled | q.rows[0];
+  auto reduce_chunk = [&](uint64_t f0, uint64_t cnt, const mgx::Outputs& d) {
     // the chunk's rows [f0, f0 + cnt) and the slots they can belong to: from the block that holds the first of
     // them that a signal owns to the block that holds the last (the kernel passes over a slot without rows here)
     const uint64_t* const tb = frame_offsets;
@@ -1922,6 +2188,20 @@ int mgx_summarize_host(mgx_plan* p, const float* samples, uint64_t num_samples, 
     const hipError_t ke = mgx::launch_summary_partial(c, p->s_comp);
     return ke == hipSuccess ? (int)MGX_OK : hip_fail(ke, "summary kernel launch");
   };
+  hook.after = [&](uint64_t f0, uint64_t cnt, const mgx::Outputs& d) {
+    if (a.cols > 0) {
+      const int hr = reduce_chunk(f0, cnt, d);
+      if (hr) return hr;
+    }
+    // the delta'd fields' rows of the chunk to their place in the call's arrays, before the slot is reused
+    hipError_t ce = hipSuccess;
+    for (int i = 0; i < mgx::kOutFields && ce == hipSuccess; ++i) {
+      if (!((q.rows[0] >> i) & 1u)) continue;
+      const uint64_t fb = mgx::out_field_bytes(p->d, i);
+      ce = hipMemcpyAsync(p->s_delta + xoff[i] + f0 * fb, mgx::out_field(d, i), cnt * fb, hipMemcpyDeviceToDevice, p->s_comp);
+    }
+    return ce == hipSuccess ? (int)MGX_OK : hip_fail(ce, "hipMemcpyAsync(delta rows)");
+  };
   if ((rc = gather_host_chunked(p, samples, starts, nframes, &x, &hook))) return rc;
   // the signals' partials into the summaries, and those alone back to the caller
   double* const result = reinterpret_cast<double*>(p->s_sum + l.result);
@@ -1934,10 +2214,36 @@ int mgx_summarize_host(mgx_plan* p, const float* samples, uint64_t num_samples, 
   for (uint32_t i = 0; i < a.nfields && e == hipSuccess; ++i)
     e = hipMemcpyAsync(host_dst[i], a.f[i].dst, nsignals * MGX_NUM_STATS * a.f[i].width * sizeof(double), hipMemcpyDeviceToHost,
                        p->s_comp);
+  if (q.any() && e == hipSuccess) {
+    // the operator and the pooling over the whole call's rows, as the device call runs them
+    std::vector<double*> delta_dst[2];
+    for (int k = 0; k < 2; ++k) {
+      mgx::SummaryArgs& da = q.sf[k].a;
+      double* const dres = reinterpret_cast<double*>(p->s_delta + dl.result[k]);
+      for (uint32_t i = 0; i < da.nfields; ++i) {
+        delta_dst[k].push_back(da.f[i].dst);
+        da.f[i].dst = dres + nsignals * MGX_NUM_STATS * da.f[i].col0;
+      }
+    }
+    const mgx::Outputs xr = mgx::out_at(p->s_delta, xoff);
+    rc = delta_pool(p->d, q, xr, p->s_delta, dl, reinterpret_cast<const uint64_t*>(p->s_delta + dl.table), nframes, nsignals, p->s_comp);
+    for (int k = 0; k < 2 && rc == MGX_OK && e == hipSuccess; ++k) {
+      const mgx::SummaryArgs& da = q.sf[k].a;
+      for (uint32_t i = 0; i < da.nfields && e == hipSuccess; ++i)
+        e = hipMemcpyAsync(delta_dst[k][i], da.f[i].dst, nsignals * MGX_NUM_STATS * da.f[i].width * sizeof(double),
+                           hipMemcpyDeviceToHost, p->s_comp);
+    }
+  }
   const hipError_t es = hipStreamSynchronize(p->s_comp);
+  if (rc) return rc;
   if (e == hipSuccess) e = es;
   return e == hipSuccess ? MGX_OK : hip_fail(e, "summary kernels and copies");
 }
+
+}  // namespace
+
+extern "C" {
+
 
 int mgx_wav_parse(const void* bytes, uint64_t len, mgx_wav_info* info) {
   if (!bytes || !info) return fail(MGX_E_INVALID_ARGUMENT, "NULL argument");

@@ -28,7 +28,7 @@
 //                                   signals: an array of Float32Arrays (a corpus); every signal's buffers
 //                                   in one launch, none across two signals; getBatch's result plus
 //                                   frameOffsets (signal s: rows frameOffsets[s] .. frameOffsets[s + 1])
-//   getSignalSummaries(features, signals, hopSize) / getSignalSummariesAsync(...)
+//   getSignalSummaries(features, signals, hopSize[, {deltaWidth, deltaOrder}]) / getSignalSummariesAsync(...)
 //                                   getBatchSignals' signals pooled per signal on the device: per feature
 //                                   {mean, variance, min, max}, Float64Arrays of signals x width, plus frameOffsets
 //   Meyda.signalsFrameStarts(lengths, bufferSize, hopSize)
@@ -449,16 +449,25 @@ class Meyda {
   // signal s at [s width, (s + 1) width)); 'loudness' gives {specific, total}, each such an object. Population
   // variance; a signal without buffers gives NaN. frameOffsets as getBatchSignals returns it. Only the
   // summaries cross back from the device. 'complexSpectrum' and 'buffer' have no summary (TypeError).
-  getSignalSummaries(features, signals, hopSize) {
+  // options {deltaWidth: 2, deltaOrder: 2}: the same statistics of the rows' regression deltas of half-width
+  // deltaWidth (1..8) within each signal, and at order 2 of the deltas' deltas (MFCC + delta + delta-delta pooled
+  // per clip): the result gains `delta` (and `delta2`), objects of the result's own shape. The deltas of a
+  // spectrum are not pooled (the library's error). Without the option the result is as it was.
+  getSignalSummaries(features, signals, hopSize, options) {
     const names = this._checkNames(checkSummaryNames(features));
     const c = this._concatSignals(signals, hopSize);
-    return summaryResult(names, addon.summarizeGather(this._plan(), c.samples, c.starts, c.frameOffsets, names), c.frameOffsets);
+    const d = deltaOptions(options);
+    const raw = d ? addon.summarizeGather(this._plan(), c.samples, c.starts, c.frameOffsets, names, d)
+      : addon.summarizeGather(this._plan(), c.samples, c.starts, c.frameOffsets, names);
+    return summaryResult(names, raw, c.frameOffsets);
   }
 
-  getSignalSummariesAsync(features, signals, hopSize) {
+  getSignalSummariesAsync(features, signals, hopSize, options) {
     const names = this._checkNames(checkSummaryNames(features));
     const c = this._concatSignals(signals, hopSize);
-    return this._runAsync((plan) => addon.summarizeGatherAsync(plan, c.samples, c.starts, c.frameOffsets, names))
+    const d = deltaOptions(options);
+    return this._runAsync((plan) => (d ? addon.summarizeGatherAsync(plan, c.samples, c.starts, c.frameOffsets, names, d)
+      : addon.summarizeGatherAsync(plan, c.samples, c.starts, c.frameOffsets, names)))
       .then((r) => summaryResult(names, r, c.frameOffsets));
   }
 
@@ -688,7 +697,21 @@ function summaryResult(names, raw, frameOffsets) {
   for (const n of names) {
     r[n] = n === 'loudness' ? { specific: split(raw['loudness.specific']), total: split(raw['loudness.total']) } : split(raw[n]);
   }
+  // (the delta summaries the addon hangs on its result: the same fields, the same shape)
+  for (const k of ['delta', 'delta2']) if (raw[k]) r[k] = summaryResult(names, raw[k], frameOffsets);
   return r;
+}
+
+// getSignalSummaries' options as the addon takes them, or null when no deltas are asked for
+function deltaOptions(options) {
+  if (options === undefined || options === null) return null;
+  if (typeof options !== 'object') throw new TypeError('options must be an object: {deltaWidth, deltaOrder}');
+  if (options.deltaWidth === undefined && options.deltaOrder === undefined) return null;
+  const d = { deltaWidth: options.deltaWidth === undefined ? 2 : options.deltaWidth,
+    deltaOrder: options.deltaOrder === undefined ? 2 : options.deltaOrder };
+  if (!Number.isInteger(d.deltaWidth) || d.deltaWidth < 1 || d.deltaWidth > 8) throw new RangeError('deltaWidth must be an integer from 1 to 8');
+  if (d.deltaOrder !== 1 && d.deltaOrder !== 2) throw new RangeError('deltaOrder must be 1 or 2');
+  return d;
 }
 
 // Slice frame `i` of a SoA batch result into the reference's return shapes

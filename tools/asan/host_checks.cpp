@@ -231,6 +231,42 @@ static void frame_starts() {
   }
   CHECK(mgx_summarize_host(nullptr, nullptr, 0, &one, 1, fo, 1, nullptr, nullptr, nullptr) == MGX_E_INVALID_ARGUMENT);
   CHECK(mgx_summary_workspace_bytes(nullptr, nullptr, nullptr, &so, 1, 1, nullptr) == MGX_E_INVALID_ARGUMENT && bytes == 77);
+  // the delta calls: the delta struct and the summaries it names are checked ahead of the plan too; the operator
+  // refuses its arguments before any launch (no pointer is read)
+  so.struct_size = sizeof so;
+  mgx_summary_outputs named = so;
+  double stats[4 * 13];
+  named.mfcc = stats;
+  mgx_delta_summaries ds{(uint32_t)sizeof(mgx_delta_summaries), 2, &named, &named};
+  auto delta_calls = [&](int want, const char* why) {
+    CHECK(mgx_summarize_deltas_host(nullptr, nullptr, 0, &one, 1, fo, 1, nullptr, nullptr, &so, &ds) == want);
+    CHECK(strstr(mgx_last_error(), why) != nullptr);
+    CHECK(mgx_summarize_deltas_device(nullptr, nullptr, 0, &one, 1, fo, 1, nullptr, nullptr, &so, &ds, nullptr, 0, nullptr) == want);
+    CHECK(mgx_summarize_deltas_workspace_bytes(nullptr, nullptr, nullptr, &so, &ds, 1, 1, &bytes) == want && bytes == 77);
+  };
+  delta_calls(MGX_E_INVALID_ARGUMENT, "NULL plan");
+  ds.width = MGX_DELTA_MAX_WIDTH + 1;
+  delta_calls(MGX_E_INVALID_ARGUMENT, "width");
+  ds.width = 2;
+  ds.struct_size -= 8;
+  delta_calls(MGX_E_INVALID_ARGUMENT, "mgx_delta_summaries.struct_size");
+  ds.struct_size += 8;
+  named.power_spectrum = stats;
+  delta_calls(MGX_E_UNSUPPORTED, "spectrum");
+  named.power_spectrum = nullptr;
+  named.reserved = 1;
+  delta_calls(MGX_E_INVALID_ARGUMENT, "reserved");
+  float rows[4], d1[4], d2[4];
+  CHECK(mgx_delta_device(rows, 4, 0, 0, nullptr, 0, 2, d1, d2, nullptr) == MGX_E_INVALID_ARGUMENT);
+  CHECK(mgx_delta_device(rows, 4, 1, 0, nullptr, 0, 0, d1, d2, nullptr) == MGX_E_INVALID_ARGUMENT);
+  CHECK(mgx_delta_device(rows, 4, 1, 0, nullptr, 0, 9, d1, d2, nullptr) == MGX_E_INVALID_ARGUMENT);
+  CHECK(mgx_delta_device(rows, 4, 1, 2, nullptr, 0, 2, d1, d2, nullptr) == MGX_E_INVALID_ARGUMENT);
+  CHECK(mgx_delta_device(rows, 4, 1, 0, nullptr, 0, 2, nullptr, nullptr, nullptr) == MGX_E_INVALID_ARGUMENT);
+  CHECK(mgx_delta_device(rows, 4, 1, 0, nullptr, 0, 2, d1, d1, nullptr) == MGX_E_INVALID_ARGUMENT);
+  CHECK(mgx_delta_device(rows, 4, 1, 0, nullptr, 0, 2, rows, d2, nullptr) == MGX_E_INVALID_ARGUMENT);
+  CHECK(mgx_delta_device(rows, 4, 1, 0, nullptr, 1, 2, d1, d2, nullptr) == MGX_E_INVALID_ARGUMENT);
+  CHECK(mgx_delta_device(nullptr, 4, 1, 0, nullptr, 0, 2, d1, d2, nullptr) == MGX_E_INVALID_ARGUMENT);
+  CHECK(mgx_delta_device(nullptr, 0, 1, 0, nullptr, 0, 2, d1, d2, nullptr) == MGX_OK);
   printf("frame starts: %ld tables\n", n);
 }
 
