@@ -914,6 +914,16 @@ __device__ __forceinline__ T* uniform_ptr(T* p) {
   return (T*)(((uint64_t)hi << 32) | lo);
 }
 
+// a < b for two wave-uniform frame or batch counts, from their 32-bit halves: scalar compares. The scalar unit
+// has no ordered 64-bit compare, so `a < b` itself is a v_mov_b64 of one side and a v_cmp_lt_u64 -- twice per
+// frame in the frame loop. (The high words through an empty asm: the compiler otherwise puts the 64-bit
+// compare back together.)
+__device__ __forceinline__ bool ult_uniform(uint64_t a, uint64_t b) {
+  uint32_t ah = (uint32_t)(a >> 32), bh = (uint32_t)(b >> 32);
+  asm volatile("" : "+s"(ah), "+s"(bh));
+  return ah < bh || (ah == bh && (uint32_t)a < (uint32_t)b);
+}
+
 __device__ __forceinline__ int opaque(int v) {
   asm volatile("" : "+v"(v));
   return v;
@@ -1013,7 +1023,7 @@ struct MelTab {
 // Each lane stores its running sums before bins 1..R-1 at fixed entries of the slot buffer
 // (immediate offsets: no per-bin address), then the scan's carry into it; band j sums
 // carry-or-zero + entry for U_j and D_{j+1}. No selects: per bin a packed multiply and a packed
-// FMA, per scan step two DPP moves and a packed FMA. No cross-segment sums are formed, so there
+// FMA, per scan step two DPP-fused FMAs. No cross-segment sums are formed, so there
 // is no cancellation; the sums are float32 like the reference's Float32Array accumulation, in a
 // different order (and the falling weight is 1 - rising in float32, within an ulp of the f64 ratio).
 template <int N>
@@ -1032,23 +1042,35 @@ __device__ __forceinline__ void mel_energies(KArgs* ap, const float (&av)[Geo<N>
     const f32x2 w = mt.weights(jj), pp = {p, p}, kk = {kp, kp};
     acc = __builtin_elementwise_fma(w, pp, acc * kk);
   }
-  f32x2 sc = acc;
-  auto step = [&](float u, float d, int s) {
-    const f32x2 src = {u, d}, ks = {mt.scan_keep(s), mt.scan_keep(s)};
-    sc = __builtin_elementwise_fma(src, ks, sc);
-  };
-  step(dpp_f<0x111>(sc.x), dpp_f<0x111>(sc.y), 0);  // row_shr:1
-  step(dpp_f<0x112>(sc.x), dpp_f<0x112>(sc.y), 1);  // row_shr:2
-  step(dpp_f<0x114>(sc.x), dpp_f<0x114>(sc.y), 2);  // row_shr:4
-  step(dpp_f<0x118>(sc.x), dpp_f<0x118>(sc.y), 3);  // row_shr:8
+  // (each half a scalar FMA whose first operand is the DPP move itself -- one v_fmac_f32_dpp -- where a packed
+  // FMA took two separate moves ahead of it: 2 VALU per step instead of 3, the same float32 FMA)
+  // (written as assembly: the compiler fuses a DPP move into an add but not into an FMA, whose accumulator is
+  // tied to its destination. The leading s_nop is the two wait states between a VALU write of a register and a
+  // DPP read of it, which the compiler cannot see inside the statement.)
+  float su = acc.x, sd = acc.y;
+#define MGX_MEL_STEP(ctrl, s)                                                                               \
+  asm volatile("s_nop 1\n\tv_fmac_f32_dpp %0, %0, %2 " ctrl " row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t" \
+               "v_fmac_f32_dpp %1, %1, %2 " ctrl " row_mask:0xf bank_mask:0xf bound_ctrl:1"                \
+               : "+v"(su), "+v"(sd)                                                                         \
+               : "v"(mt.scan_keep(s)))
+  MGX_MEL_STEP("row_shr:1", 0);
+  MGX_MEL_STEP("row_shr:2", 1);
+  MGX_MEL_STEP("row_shr:4", 2);
+  MGX_MEL_STEP("row_shr:8", 3);
   // (the row broadcasts write every row: the rows a step must not add to have keep 0 in the plan,
   // so no zero has to be written ahead of a row-masked move)
-  step(dpp_f<0x142>(sc.x), dpp_f<0x142>(sc.y), 4);  // row_bcast:15 (rows 1, 3)
-  step(dpp_f<0x143>(sc.x), dpp_f<0x143>(sc.y), 5);  // row_bcast:31 (rows 2, 3)
-  const float xu = dpp_f<0x138>(sc.x), xd = dpp_f<0x138>(sc.y);  // exclusive: carry into this lane
-  mine[(R - 1) * 64] = make_float2(xu, xd);
-  if (lane == 63) buf[R * 64] = make_float2(sc.x, sc.y);
-  if (lane == 0) buf[R * 64 + 1] = make_float2(0.0f, 0.0f);
+  MGX_MEL_STEP("row_bcast:15", 4);  // rows 1, 3
+  MGX_MEL_STEP("row_bcast:31", 5);  // rows 2, 3
+#undef MGX_MEL_STEP
+  // The carry into lane l -- the inclusive sums of lane l - 1, 0 for lane 0 -- is entry (R - 1) 64 + l, and the
+  // wave's totals are entry R 64: the inclusive sums of lane l - 1 at entry (R - 1) 64 + (l - 1) + 1 for every
+  // l up to 64. So each lane stores its own inclusive sums one entry up (no move across the lanes), and lane 0
+  // the two zero entries.
+  mine[(R - 1) * 64 + 1] = make_float2(su, sd);
+  if (lane == 0) {
+    buf[(R - 1) * 64] = make_float2(0.0f, 0.0f);
+    buf[R * 64 + 1] = make_float2(0.0f, 0.0f);
+  }
   wave_sync();
   if (lane < nf) {  // nf <= kMaxMel = 64
     const unsigned char* b = reinterpret_cast<const unsigned char*>(buf);
@@ -1249,28 +1271,41 @@ __device__ __forceinline__ void frame_phase1(KArgs* ap, float (&x)[Geo<N>::CH], 
   // energy; the lane partials e32 stay: the FFT's range test reads them)
   // (NOTIME: the all-feature kernel's schedule without rms / energy / zcr, compiled out)
   const bool want_zcr = SUB ? (bool)ap->need_zcr : !NOTIME, want_energy = SUB ? (bool)ap->need_energy : !NOTIME;
-  if (!want_zcr) {
-  } else if (__ballot(e32 != e32)) {
-#pragma unroll
-    for (int c = 0; c < CH; ++c) {
-      const uint64_t g = __ballot(x[c] >= 0.0f), l = __ballot(x[c] < 0.0f);
-      z += __popcll(((g & (l >> 1)) | (l & (g >> 1))) & 0x7FFFFFFFFFFFFFFFull);
-      if (c > 0) z += (int)((((pge >> 63) & l) | ((plt >> 63) & g)) & 1ull);
-      pge = g;
-      plt = l;
-    }
-  } else {
-    // without NaN samples x >= 0 is the complement of x < 0, so a sign change between samples
-    // i and i + 1 is bit i of s ^ (s >> 1) over the frame's sign sequence s (sample 64 c + l is
-    // bit l of chunk c's ballot): the chunk's 63 inner pairs and, in bit 63, the pair it forms
-    // with the next chunk's first sample (the last chunk's bit 63 compares with itself: 0)
+  if (want_zcr) {
+    // The x < 0 ballots once, ahead of the NaN branch, for both of its sides: written in each side, the
+    // compiler hoisted the NaN side's compares above the branch and issued the other side's again, 32
+    // v_cmp per frame where 16 do. (N >= 2048 keeps them in each side: shared, its 32 ballots cost the
+    // N = 2048 kernel a VGPR more.)
+    constexpr bool kShared = CH <= 16;
     uint64_t l[CH];
+    if constexpr (kShared) {
 #pragma unroll
-    for (int c = 0; c < CH; ++c) l[c] = __ballot(x[c] < 0.0f);
+      for (int c = 0; c < CH; ++c) l[c] = __ballot(x[c] < 0.0f);
+    }
+    if (__ballot(e32 != e32)) {
 #pragma unroll
-    for (int c = 0; c < CH; ++c) {
-      const uint64_t nxt = c + 1 < CH ? l[c + 1] << 63 : l[c] & 0x8000000000000000ull;
-      z += __popcll(l[c] ^ ((l[c] >> 1) | nxt));
+      for (int c = 0; c < CH; ++c) {
+        if constexpr (!kShared) l[c] = __ballot(x[c] < 0.0f);
+        const uint64_t g = __ballot(x[c] >= 0.0f);
+        z += __popcll(((g & (l[c] >> 1)) | (l[c] & (g >> 1))) & 0x7FFFFFFFFFFFFFFFull);
+        if (c > 0) z += (int)((((pge >> 63) & l[c]) | ((plt >> 63) & g)) & 1ull);
+        pge = g;
+        plt = l[c];
+      }
+    } else {
+      // without NaN samples x >= 0 is the complement of x < 0, so a sign change between samples
+      // i and i + 1 is bit i of s ^ (s >> 1) over the frame's sign sequence s (sample 64 c + l is
+      // bit l of chunk c's ballot): the chunk's 63 inner pairs and, in bit 63, the pair it forms
+      // with the next chunk's first sample (the last chunk's bit 63 compares with itself: 0)
+      if constexpr (!kShared) {
+#pragma unroll
+        for (int c = 0; c < CH; ++c) l[c] = __ballot(x[c] < 0.0f);
+      }
+#pragma unroll
+      for (int c = 0; c < CH; ++c) {
+        const uint64_t nxt = c + 1 < CH ? l[c + 1] << 63 : l[c] & 0x8000000000000000ull;
+        z += __popcll(l[c] ^ ((l[c] >> 1) | nxt));
+      }
     }
   }
   // float32 partial sums are within 1e-6 relative of the double sum; a wave whose
@@ -1596,6 +1631,8 @@ __device__ __forceinline__ void frame_phase1(KArgs* ap, float (&x)[Geo<N>::CH], 
     const int row = lane < 40 ? lane >> 3 : 0;
     const double* src = momt + row * MS + (lane & 7);  // entries g, g+8, ..., g+56 of the row
     double t = ((src[0] + src[8]) + (src[16] + src[24])) + ((src[32] + src[40]) + (src[48] + src[56]));
+    // (the same three moves as ds_swizzle_b32 on the LDS port, lane ^ 1, ^ 2, ^ 7: 6 VALU fewer per frame and
+    // no faster, 0.5567 against 0.5561 ms -- profiles/nonarith_valu.txt)
     t += dpp_d<0xB1>(t);   // quad_perm [1,0,3,2]
     t += dpp_d<0x4E>(t);   // quad_perm [2,3,0,1]
     t += dpp_d<0x141>(t);  // row_half_mirror: each 8-lane group holds its row's total
@@ -1670,7 +1707,9 @@ __device__ __forceinline__ void frame_phase1(KArgs* ap, float (&x)[Geo<N>::CH], 
   // reference's own summation, right for any frame).
   MGX_MARK(bands_done);
   MGX_STAMP(7);
-  const bool nonfinite = light ? light_nonfinite : !(total < 0x1p64);
+  // (total is +0 or above, or a NaN of either sign: !(total < 2^64) is its high word at or above 2^64's as
+  // unsigned integers -- a scalar compare of the wave-uniform total, where the f64 compare takes the VALU)
+  const bool nonfinite = light ? light_nonfinite : (uint32_t)(__builtin_bit_cast(uint64_t, total) >> 32) >= 0x43F00000u;
   if (nonfinite) {
     // (CHAIN with paired batches: the pair's first batch keeps its mel sums in the upper half of lm)
     nonfinite_frame_sums<N>(ap, av, lane, buf, rec, CHAIN && ap->chain_pair && !(it & 1) ? 32 : 0);
@@ -2304,7 +2343,7 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(RES ? 
   [[maybe_unused]] GatherAhead<kStartAhead> ahead;
   auto frame_ptr = [&](uint64_t b, int j) {
     uint64_t f = b * FPW + j;
-    f = f < nf ? f : nf - 1;
+    f = ult_uniform(f, nf) ? f : nf - 1;
     if constexpr (GATHER) return gather_frame<FPW, kStartAhead>(f, b, j, nf, wstride, ahead);
     // (wave-uniform, uniform_ptr: the lane's offset is added at each load)
     // (the frame's start: a 64-bit scalar product with the launch's stride, KernelArgs::frame_stride -- the
@@ -2424,7 +2463,7 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(RES ? 
       // the last batch's frames past the end: nothing to compute (phase 2 stores nothing for them).
       // A launch of 1-3 frames would otherwise run 4 frames in its one wave (the real-time path's
       // one-frame launch: ~4x its serial time).
-      if (f >= nf) break;
+      if (!ult_uniform(f, nf)) break;
       float x[CH];
       GF next = nullptr;
       if constexpr (RES) {
@@ -2444,7 +2483,7 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(RES ? 
       } else {
         load(x, b, j);
       }
-      frame_phase1<N, FAITH, LITERAL, SUB, LIGHT, NOTIME, CHAIN, kWinReg>(args_ptr(), x, j, f, f < nf, lane, lp, kl, dc_lane, buf, mom, recs,
+      frame_phase1<N, FAITH, LITERAL, SUB, LIGHT, NOTIME, CHAIN, kWinReg>(args_ptr(), x, j, f, /*valid: f < nf, see the break above*/ true, lane, lp, kl, dc_lane, buf, mom, recs,
                                       reinterpret_cast<const int*>(smem + LY::kc_off + 16 * 8), xn, next,
                                       reinterpret_cast<const double2*>(smem + LY::twl_off), wreg, blim, rows, it, ntf);
     }

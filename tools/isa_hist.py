@@ -7,10 +7,10 @@ from collections import Counter
 
 
 def body(path, n=1024, faith=1, lit=0):
-    names = ["_ZN3mgx12_GLOBAL__N_114extract_kernelILi%dELb%dELb%dELb0ELb0ELb0ELb0EEEvNS_10KernelArgsE" % (n, faith, lit),
-             "_ZN3mgx12_GLOBAL__N_114extract_kernelILi%dELb%dELb%dELb0ELb0ELb0EEEvNS_10KernelArgsE" % (n, faith, lit)]
+    # extract_kernel<N, FAITH, LITERAL, ...>: every later template parameter false
+    name = re.compile(r"_ZN3mgx12_GLOBAL__N_114extract_kernelILi%dELb%dELb%d(ELb0)*EEEv[^:\s]*:" % (n, faith, lit))
     lines = open(path).read().split("\n")
-    start = [i for i, l in enumerate(lines) if any(l.startswith(nm + ":") for nm in names)][0]
+    start = [i for i, l in enumerate(lines) if name.match(l)][0]
     out = []
     for l in lines[start + 1:]:
         if l.startswith(".Lfunc_end"):
