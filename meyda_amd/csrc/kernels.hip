@@ -1528,6 +1528,7 @@ __device__ __forceinline__ void frame_phase1(KArgs* ap, float (&x)[Geo<N>::CH], 
   const bool need_mom = mom_level > 0, need_hi = mom_level > 1;
   double T0 = 0, T1 = 0, T2 = 0, T3 = 0, T4 = 0;
   float l2f = 0.0f;
+  double l2d = 0.0;
   // (the sums start from bins 0 and 1 instead of from 0.0: every amplitude is >= +0 or NaN,
   // so 0 + a and fma(1, a, 0) are a itself -- the same sums without the no-op adds)
   if (need_hi) {
@@ -1550,13 +1551,22 @@ __device__ __forceinline__ void frame_phase1(KArgs* ap, float (&x)[Geo<N>::CH], 
     // inputs; one hardware log per two bins, and the product's rounding is ~2^-24 relative,
     // finer than the log's own ulp). v_log_f32 flushes a denormal input to 0 (-inf): a wave
     // whose sum is not finite (a zero, tiny, infinite or NaN amplitude, or a pair product
-    // leaving the normal range; rare) recomputes bin by bin with log2f's scaling.
+    // leaving the normal range; rare) recomputes bin by bin, exponent and mantissa apart and
+    // summed in double: out there |log2 a| is 40 .. 149, where a float32 log2f is good to ~1e-5
+    // and a float32 sum of R of them to less, and on a flat spectrum (an impulse) every bin errs
+    // the same way, so the flatness missed the 1e-5 bar by that much. frexpf gives 0, Inf and
+    // NaN back as they are (log2f: -Inf, +Inf, NaN) and scales a denormal.
 #pragma unroll
     for (int jj = 0; jj < R; jj += 2) l2f += __builtin_amdgcn_logf(av[jj] * av[jj + 1]);
+    l2d = (double)l2f;
     if (__ballot(!(__builtin_fabsf(l2f) < __builtin_huge_valf()))) {
-      l2f = 0.0f;
+      l2d = 0.0;
 #pragma unroll
-      for (int jj = 0; jj < R; ++jj) l2f += log2f(av[jj]);
+      for (int jj = 0; jj < R; ++jj) {
+        int e;
+        const float m = frexpf(av[jj], &e);
+        l2d += (double)e + (double)log2f(m);
+      }
     }
   } else if (need_mom) {
     T0 = (double)av[0];
@@ -1581,6 +1591,19 @@ __device__ __forceinline__ void frame_phase1(KArgs* ap, float (&x)[Geo<N>::CH], 
 #pragma unroll
     for (int jj = 0; jj < R; ++jj) am = max(am, __builtin_bit_cast(uint32_t, av[jj]));
     light_nonfinite = __ballot(am >= kPowOverflowBits) != 0;
+    // The other kernels send a frame to the reference's own summation by its amplitude total (>= 2^64,
+    // below), which also takes frames whose largest amplitude is short of 2^64: the two summations agree
+    // within the bar, not bit for bit, and a subset has to give the full request's bits. With every
+    // amplitude below 2^64 / L the total is below 2^64 whatever the rounding; in the band between (rare,
+    // wave-uniform) the same total is formed here: the lane sums in the same order, the same scan.
+    constexpr uint32_t kTotalMayOverflowBits = kPowOverflowBits - ((uint32_t)ilog2c(N / 2) << 23);
+    if (!light_nonfinite && __ballot(am >= kTotalMayOverflowBits)) {
+      double t = (double)av[0];
+#pragma unroll
+      for (int jj = 1; jj < R; ++jj) t += (double)av[jj];
+      const double tot = readlane_d(wave_inclusive_scan(t), 63);
+      light_nonfinite = (uint32_t)(__builtin_bit_cast(uint64_t, tot) >> 32) >= 0x43F00000u;
+    }
   }
   MGX_MARK(moments_done);
   prio_hi<8>();
@@ -1616,7 +1639,7 @@ __device__ __forceinline__ void frame_phase1(KArgs* ap, float (&x)[Geo<N>::CH], 
       mcol[1 * MS] = P2;
       mcol[2 * MS] = P3;
       mcol[3 * MS] = P4;
-      mcol[4 * MS] = (double)l2f;
+      mcol[4 * MS] = l2d;
     }
   }
   // prefix P(k) = sum_{i<k} a_i: lane-exclusive offset + local prefix
@@ -1672,7 +1695,7 @@ __device__ __forceinline__ void frame_phase1(KArgs* ap, float (&x)[Geo<N>::CH], 
     double S2 = 0, S3 = 0, S4 = 0, l2 = 0;
     if (need_hi) {
       S2 = wave_sum(P2); S3 = wave_sum(P3); S4 = wave_sum(P4);
-      l2 = wave_sum((double)l2f);
+      l2 = wave_sum(l2d);
     }
     wave_sync();
     if (lane == 0) {

@@ -91,6 +91,33 @@ def test_literal_snapshot_mode(n, oracle_mod):
     assert np.array_equal(o["scalars"][:, 10], g["literal_loudness_total"])
 
 
+def test_magnitude_ladder(oracle_mod):
+    """The five base frames of tests/ladder.py at N = 512, scaled by 2^k for k = -149, -145, ..., 127: 350
+    frames from all-zero and denormal spectra to overflowing ones (tools/gen_golden.js --ladder). The bars of
+    the tests above: amplitude and vectors bit for bit (a NaN for a NaN), scalars by test_scalars' rule."""
+    import ladder
+    g = ladder.load_golden()
+    assert g["manifest"]["scales"] == ladder.GOLDEN_KS and g["F"] == 350
+    assert np.array_equal(g["bases"].view(np.uint32), ladder.bases(ladder.GOLDEN_N).view(np.uint32))
+    x = ladder.golden_frames()
+    assert x.shape == (350, ladder.GOLDEN_N)
+    o = oracle_mod.extract(x)
+    # the fixture crosses what it is there for
+    assert np.isnan(g["amp"]).any() and (g["amp"] == 0).all(1).any() and np.isinf(g["scalars"]).any()
+    for key in ("amp", "loudness_specific", "mfcc"):
+        a, r = o[key], g[key]
+        assert np.array_equal(tolerance._cls(a), tolerance._cls(r)), key
+        same = (a.view(np.uint32) == r.view(np.uint32)) | (np.isnan(a) & np.isnan(r))
+        assert same.all(), (key, int((~same).sum()), np.argwhere(~same)[:5].tolist())
+    got, ref = o["scalars"], g["scalars"]
+    assert np.array_equal(np.isnan(got), np.isnan(ref)), np.argwhere(np.isnan(got) != np.isnan(ref))[:5].tolist()
+    fin = np.isfinite(ref)
+    assert np.array_equal(got[~fin], ref[~fin], equal_nan=True)
+    rel = np.abs(got[fin] - ref[fin]) / np.maximum(np.abs(ref[fin]), 1e-300)
+    assert rel.max() <= 1e-12, (rel.max(), np.argwhere(fin)[np.argmax(rel)].tolist())
+    assert not tolerance.check_scalars(got, ref, g["amp"], ladder.GOLDEN_N)
+
+
 def test_config1_reference_numbers(oracle_mod):
     # BASELINE.md C1: frame 0 of sound1.wav at N=512 -> rms 0.0050815644, centroid 32.0121595
     g = golden_io.load(512)

@@ -27,6 +27,9 @@
 //        gen_golden.js --n4096    N = 4096 alone, into tests/golden/N4096/ with a manifest of its own
 //                                 (tests/golden/N4096/manifest.json): the same families with fewer frames,
 //                                 every file within the committed-file limit; nothing else is touched
+//        gen_golden.js --ladder   the magnitude ladder (tests/ladder.py) at N = 512, into tests/golden/ladder/
+//                                 with a manifest of its own; reads tests/golden/ladder/bases.f32, written by
+//                                 `python tests/ladder.py`; nothing else is touched
 'use strict';
 const fs = require('fs');
 const path = require('path');
@@ -239,7 +242,53 @@ function concat(Type, arrs) {
   return out;
 }
 
+// --ladder: the five base frames of tests/ladder.py (tests/golden/ladder/bases.f32, N = 512) at the scales
+// 2^k, k = -149, -145, ..., 127: 350 frames through the intended path, from zero and denormal spectra to
+// overflowing ones. Pins the oracle where the other fixtures (all of moderate magnitude) say nothing.
+function ladderMain() {
+  const N = 512, NB = 5, dir = path.join(OUT, 'ladder');
+  const buf = fs.readFileSync(path.join(dir, 'bases.f32'));
+  if (buf.length !== NB * N * 4) throw new Error('bases.f32: expected ' + NB + ' x ' + N + ' float32 (python tests/ladder.py)');
+  const bases = new Float32Array(buf.buffer.slice(buf.byteOffset, buf.byteOffset + buf.length));
+  const ks = [];
+  for (let k = -149; k <= 127; k += 4) ks.push(k);
+  const M = makeMeyda(N);
+  const recs = [];
+  for (const k of ks) {
+    const s = Math.pow(2, k);
+    for (let b = 0; b < NB; b++) {
+      const x = new Float32Array(N);
+      for (let n = 0; n < N; n++) x[n] = Math.fround(bases[b * N + n] * s);
+      recs.push(runIntended(M, N, x, 'hanning'));
+    }
+  }
+  const F = recs.length;
+  const scal = new Float64Array(F * SCALARS.length);
+  recs.forEach((r, f) => SCALARS.forEach((name, j) => { scal[f * SCALARS.length + j] = r[name]; }));
+  const w = (rel, typed) => { writeBin('ladder/' + rel, typed); return rel; };
+  const manifest = {
+    generator: 'tools/gen_golden.js --ladder',
+    reference: 'kirbysayshi/meyda snapshot (src/, lib/jsfft/) evaluated under node ' + process.version,
+    sampleRate: SR,
+    bufferSize: N,
+    frames: F,
+    order: 'frame 5 * i + b = Math.fround(bases[b] * 2^scales[i])',
+    scales: ks,
+    scalars: SCALARS,
+    files: {
+      bases: 'bases.f32',
+      amp: w('amp.f32', concat(Float32Array, recs.map((r) => r.amp))),
+      scalars: w('scalars.f64', scal),
+      loudness_specific: w('loudness_specific.f32', concat(Float32Array, recs.map((r) => r.loudnessSpecific))),
+      mfcc: w('mfcc.f32', concat(Float32Array, recs.map((r) => r.mfcc))),
+    },
+  };
+  fs.writeFileSync(path.join(dir, 'manifest.json'), JSON.stringify(manifest, null, 1) + '\n');
+  console.log('ladder: ' + F + ' frames at N=' + N);
+}
+
 function main() {
+  if (process.argv.includes('--ladder')) return ladderMain();
   const only4096 = process.argv.includes('--n4096');
   fs.mkdirSync(OUT, { recursive: true });
   const wavs = {};
