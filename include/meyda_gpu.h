@@ -34,6 +34,9 @@
  *                        and max of each output over a clip          application over Meyda.get's results
  *   mgx_delta_device,    the rows' time derivatives (delta, delta-  no counterpart: the regression
  *   mgx_summarize_deltas_*  delta) per frame, and pooled per clip    stencil of a host application
+ *   mgx_flux_device,     spectral flux: the distance of a row from   no counterpart in this snapshot (one
+ *   mgx_summarize_flux_*  an earlier row of its clip, per frame     buffer per call); later Meyda's
+ *                        (the onset envelope) and pooled per clip    spectralFlux, Dixon's rectified flux
  *   mgx_group_*          several devices, RCCL gather of the        src/meyda.js:17-97 (one plan
  *                        per-frame records to the root device       per device), :69-91 (buffers
  *                                                                   are independent: shardable)
@@ -565,6 +568,98 @@ int mgx_summarize_deltas_host(mgx_plan* plan, const float* samples, uint64_t num
                               uint64_t num_frames, const uint64_t* frame_offsets, uint64_t num_signals,
                               const mgx_outputs* outputs, const mgx_aux_outputs* aux,
                               const mgx_summary_outputs* summary, const mgx_delta_summaries* deltas);
+
+/* ---- Spectral flux: the change between a clip's rows, per frame and pooled --------------------
+ * Replaces, in a host application, the loop that compares every buffer's row (its amplitude spectrum, its
+ * log-mel bands, its MFCCs) with an earlier buffer's row of the same clip: the onset-strength envelope of onset
+ * and beat detection (Dixon's half-wave rectified flux, the L2 flux of Marsyas, librosa.onset.onset_strength
+ * over log-mel rows). The reference delivers one buffer per call and has no counterpart. Flux, like the
+ * statistics and the deltas, is not a feature: MGX_NUM_FEATURES, the name table and every struct above are as
+ * they were.
+ *
+ * A signal owns rows [a, b) of an array of num_frames rows x cols columns (row-major). For a lag L
+ * (1 .. MGX_FLUX_MAX_LAG), a row t of [a, b) and p = max(t - L, a) -- the earlier row, clamped at the signal's
+ * first row as the deltas clamp:
+ *
+ *   d(c) = +0 if x(t,c) == x(p,c), else x(t,c) - x(p,c)      values taken as float64 (a float32 converts
+ *                                                            exactly), the difference rounded once
+ *   e(c) = d if d > 0 or d is NaN, else +0    MGX_FLUX_RECTIFIED
+ *          |d|                                MGX_FLUX_L1
+ *          d d, rounded before it is added    MGX_FLUX_L2
+ *
+ * The equality rule keeps a column that is -Infinity in both rows (a mel band that spans no bin) at 0 instead
+ * of Inf - Inf; a NaN compares unequal and stays NaN. The terms are added in a fixed order: 64 partials P[l]
+ * start at +0; for k = 0, 64, 128, ... ascending, P[l] += e(k + l) for the columns that exist; then P[l] +=
+ * P[l + h] for l < h, with h = 32, 16, 8, 4, 2, 1; S = P[0]. Every term is >= +0 or NaN, so a partial that
+ * stayed +0 changes nothing, and no mapping of rows to lanes changes a bit. The result is S (RECTIFIED, L1) or
+ * sqrt(S) in float64 as the device's sqrt gives it (L2), rounded once to the rows' element type. A signal's first row,
+ * and every row of a one-row signal, is 0 wherever the row is finite; an empty signal writes nothing; rows that
+ * belong to no signal are not written. A value is a function of its own signal's rows alone: no atomics, and
+ * the same bits from every call below, from a repeated call and from any grid. */
+typedef enum mgx_flux_mode {
+  MGX_FLUX_RECTIFIED = 0,
+  MGX_FLUX_L1 = 1,
+  MGX_FLUX_L2 = 2,
+  MGX_NUM_FLUX_MODES = 3
+} mgx_flux_mode;
+#define MGX_FLUX_MAX_LAG 8
+
+/* The operator on device arrays; no plan: asynchronous on `stream`, no allocation, no host-side state,
+ * capturable. rows_f64: 0 float32 rows, 1 float64 rows; flux: num_frames values of the rows' element type.
+ * frame_offsets: num_signals + 1 entries in device memory, or NULL with num_signals = 0 for one signal
+ * [0, num_frames). The table is read as mgx_delta_device reads it, every entry limited to num_frames: a
+ * non-decreasing one gives the definition above, any other gives unspecified values and no access outside the
+ * arrays.
+ * MGX_E_INVALID_ARGUMENT before any launch: cols = 0, mode >= MGX_NUM_FLUX_MODES, lag outside 1 ..
+ * MGX_FLUX_MAX_LAG, rows_f64 > 1, NULL flux, flux equal to rows, num_signals > 0 with NULL frame_offsets, NULL
+ * rows with num_frames > 0. num_frames = 0 returns MGX_OK and writes nothing. */
+int mgx_flux_device(const void* rows, uint64_t num_frames, uint32_t cols, uint32_t rows_f64,
+                    const uint64_t* frame_offsets, uint64_t num_signals, uint32_t mode, uint32_t lag,
+                    void* flux, void* stream);
+
+/* One flux of one field through the summary calls: its column per frame, its pooling per clip, or both. */
+typedef struct mgx_flux_request {
+  uint32_t struct_size;  /* = sizeof(mgx_flux_request), 32; anything else: MGX_E_INVALID_ARGUMENT */
+  uint32_t field;        /* MGX_LOUDNESS (the loudness_specific rows), MGX_MFCC, MGX_AMPLITUDE_SPECTRUM,
+                            MGX_POWER_SPECTRUM or MGX_MEL_BANDS; anything else: MGX_E_UNSUPPORTED */
+  uint32_t mode, lag;
+  float* per_frame;      /* num_frames floats (the onset envelope), or NULL */
+  double* summary;       /* num_signals x MGX_NUM_STATS: mean, variance, min, max of the flux per clip, or NULL */
+} mgx_flux_request;
+#define MGX_FLUX_MAX_REQUESTS 4
+
+/* The three mgx_summarize_deltas_* calls with num_flux requests behind `deltas` (which may be NULL). num_flux =
+ * 0 is exactly the deltas call, its workspace bytes included. MGX_E_INVALID_ARGUMENT: more than
+ * MGX_FLUX_MAX_REQUESTS requests, a bad struct_size, mode or lag, a request with both pointers NULL, summary set
+ * with num_signals = 0. Everything the deltas call writes is written bit for bit as before. num_signals = 0 is
+ * the gather call, as in every summary call: no signal owns a row, and no per_frame column is written.
+ * Device call: the workspace also holds the rows of a flux'd field that nothing else keeps (a field requested
+ * per frame, pooled or delta'd is shared), the flux column of a request without per_frame, and the pooling's
+ * shifts and partials; its bytes keep the contract of mgx_summary_workspace_bytes. After the gather launch the
+ * operator runs per request, keyed by the table as the summary kernels read it, then the summary kernels over
+ * the one-column flux array: every rule of the summaries holds for it.
+ * Host call: the device call's bits wherever the chunks end. No spectrum is kept for the call: the last lag
+ * rows of each flux'd field go from a chunk to a small plan-owned carry buffer before the slot is reused, the
+ * operator runs per chunk over the slot's rows and that carry, and the flux columns alone (4 bytes per buffer
+ * and request; grown on demand, freed at mgx_plan_destroy) last as long as the call and are pooled after the
+ * last chunk. Only summaries, per_frame columns and the per-frame fields named cross back; of a per_frame column
+ * the rows of the signals alone, [frame_offsets[0], frame_offsets[num_signals]): a row that belongs to no signal
+ * is not written, as in the device call. */
+int mgx_summarize_flux_workspace_bytes(const mgx_plan* plan, const mgx_outputs* outputs, const mgx_aux_outputs* aux,
+                                       const mgx_summary_outputs* summary, const mgx_delta_summaries* deltas,
+                                       const mgx_flux_request* flux, uint32_t num_flux, uint64_t num_frames,
+                                       uint64_t num_signals, uint64_t* bytes);
+int mgx_summarize_flux_device(mgx_plan* plan, const float* samples, uint64_t num_samples, const uint64_t* starts,
+                              uint64_t num_frames, const uint64_t* frame_offsets, uint64_t num_signals,
+                              const mgx_outputs* outputs, const mgx_aux_outputs* aux,
+                              const mgx_summary_outputs* summary, const mgx_delta_summaries* deltas,
+                              const mgx_flux_request* flux, uint32_t num_flux,
+                              void* workspace, uint64_t workspace_bytes, void* stream);
+int mgx_summarize_flux_host(mgx_plan* plan, const float* samples, uint64_t num_samples, const uint64_t* starts,
+                            uint64_t num_frames, const uint64_t* frame_offsets, uint64_t num_signals,
+                            const mgx_outputs* outputs, const mgx_aux_outputs* aux,
+                            const mgx_summary_outputs* summary, const mgx_delta_summaries* deltas,
+                            const mgx_flux_request* flux, uint32_t num_flux);
 
 /* ---- Multi-device groups -------------------------------
  * Replaces nothing in the reference (single-threaded browser code); it exists because

@@ -15,7 +15,9 @@
  *   extractWav(plan, wavBytes, features[, channel]) / extractWavAsync(...)
  *                                        -> the features of every full buffer of a .wav file;
  *                                           the raw PCM is decoded on the device
- *   summarizeGather(plan, samples, starts, frameOffsets, features[, {deltaWidth, deltaOrder}]) / summarizeGatherAsync(...)
+ *   summarizeGather(plan, samples, starts, frameOffsets, features[, {deltaWidth, deltaOrder, flux}]) / summarizeGatherAsync(...)
+ *     flux: [{field, mode, lag, perFrame}] (numbers as in mgx_flux_request); the result gains `flux`, one
+ *     {summary: Float64Array(nsignals x 4), perFrame: Float32Array(nframes)} per request
  *                                        -> { name: Float64Array(S x 4 x width) }: mean, variance, min, max
  *                                           of each field over every signal's buffers (mgx_summarize_host)
  *   wavParse(wavBytes)                   -> { pcmFormat, channels, sampleRate, bitsPerSample, ... }
@@ -282,6 +284,12 @@ typedef struct {
   mgx_summary_outputs dsum[2];
   mgx_delta_summaries deltas;
   napi_ref drefs[2][NSLOTS];
+  /* ... and with the option flux: the flux of the named fields pooled per signal, and per frame where asked
+   * (mgx_summarize_flux_host); with flux and neither delta option no deltas are asked for */
+  uint32_t num_flux;
+  mgx_flux_request flux[MGX_FLUX_MAX_REQUESTS];
+  int flux_per_frame[MGX_FLUX_MAX_REQUESTS];
+  napi_ref frefs[2][MGX_FLUX_MAX_REQUESTS];  /* [0] the summaries, [1] the per-frame columns */
   mgx_outputs out;
   mgx_aux_outputs aux;  /* melBands (SLOT_MEL): the job then makes the mgx_extract_*_ex call */
   /* The outputs are written straight into JS ArrayBuffers (napi_create_arraybuffer), held by
@@ -316,6 +324,12 @@ static void job_free_buffers(napi_env env, job* j) {
       if (j->drefs[k][i]) {
         napi_delete_reference(env, j->drefs[k][i]);
         j->drefs[k][i] = NULL;
+      }
+  for (int k = 0; k < 2; ++k)
+    for (int i = 0; i < MGX_FLUX_MAX_REQUESTS; ++i)
+      if (j->frefs[k][i]) {
+        napi_delete_reference(env, j->frefs[k][i]);
+        j->frefs[k][i] = NULL;
       }
 }
 
@@ -525,6 +539,76 @@ static int option_u32(napi_env env, napi_value obj, const char* name, uint32_t l
   return 1;
 }
 
+/* Is the named property of obj there (neither absent nor undefined)? */
+static int option_given(napi_env env, napi_value obj, const char* name, napi_value* v) {
+  napi_valuetype t = napi_undefined;
+  if (napi_get_named_property(env, obj, name, v) != napi_ok) return 0;
+  napi_typeof(env, *v, &t);
+  return t != napi_undefined;
+}
+
+/* The option flux: an array of 1 .. MGX_FLUX_MAX_REQUESTS objects {field, mode = 0, lag = 1, perFrame = false}.
+ * The arrays are made once the numbers of buffers and signals are known (job_alloc_flux). */
+static int parse_flux(napi_env env, job* j, napi_value arr) {
+  bool is_arr = false;
+  uint32_t n = 0;
+  napi_is_array(env, arr, &is_arr);
+  if (is_arr) napi_get_array_length(env, arr, &n);
+  if (!is_arr || n < 1 || n > MGX_FLUX_MAX_REQUESTS) {
+    napi_throw_range_error(env, NULL, "flux must be an array of 1 to 4 requests");
+    return 0;
+  }
+  for (uint32_t i = 0; i < n; ++i) {
+    napi_value e, pf;
+    napi_valuetype t = napi_undefined;
+    if (napi_get_element(env, arr, i, &e) == napi_ok) napi_typeof(env, e, &t);
+    if (t != napi_object) {
+      napi_throw_type_error(env, NULL, "a flux request must be an object: {field, mode, lag, perFrame}");
+      return 0;
+    }
+    mgx_flux_request* r = &j->flux[i];
+    r->struct_size = sizeof *r;
+    if (!option_u32(env, e, "field", 0, MGX_NUM_FEATURES - 1, MGX_NUM_FEATURES, &r->field)) return 0;
+    if (r->field == MGX_NUM_FEATURES) {
+      napi_throw_type_error(env, NULL, "a flux request names its field");
+      return 0;
+    }
+    if (!option_u32(env, e, "mode", 0, MGX_NUM_FLUX_MODES - 1, MGX_FLUX_RECTIFIED, &r->mode)) return 0;
+    if (!option_u32(env, e, "lag", 1, MGX_FLUX_MAX_LAG, 1, &r->lag)) return 0;
+    bool b = false;
+    if (option_given(env, e, "perFrame", &pf)) napi_coerce_to_bool(env, pf, &pf), napi_get_value_bool(env, pf, &b);
+    j->flux_per_frame[i] = b ? 1 : 0;
+  }
+  j->num_flux = n;
+  return 1;
+}
+
+static int job_alloc_flux(napi_env env, job* j) {
+  for (uint32_t i = 0; i < j->num_flux; ++i) {
+    napi_value abv;
+    void* data = NULL;
+    /* (without signals there is nothing to pool: the library takes the per-frame column alone) */
+    if (j->nsignals > 0) {
+      if (napi_create_arraybuffer(env, (size_t)j->nsignals * MGX_NUM_STATS * sizeof(double), &data, &abv) != napi_ok ||
+          napi_create_reference(env, abv, 1, &j->frefs[0][i]) != napi_ok) {
+        napi_throw_error(env, NULL, "out of host memory");
+        return 0;
+      }
+      j->flux[i].summary = (double*)data;
+    }
+    if (j->flux_per_frame[i]) {
+      if (napi_create_arraybuffer(env, (size_t)j->nframes * sizeof(float), &data, &abv) != napi_ok ||
+          napi_create_reference(env, abv, 1, &j->frefs[1][i]) != napi_ok) {
+        napi_throw_error(env, NULL, "out of host memory");
+        return 0;
+      }
+      memset(data, 0, (size_t)j->nframes * sizeof(float));
+      j->flux[i].per_frame = (float*)data;
+    }
+  }
+  return 1;
+}
+
 static int job_prepare_summary(napi_env env, job* j, napi_value samples_v, napi_value starts_v, napi_value offsets_v,
                                napi_value feats, napi_value options_v) {
   size_t count = 0;
@@ -532,7 +616,12 @@ static int job_prepare_summary(napi_env env, job* j, napi_value samples_v, napi_
   j->sum.struct_size = sizeof j->sum;
   napi_valuetype ot = napi_undefined;
   if (options_v) napi_typeof(env, options_v, &ot);
-  if (ot == napi_object) {  /* the trailing options: {deltaWidth = 2, deltaOrder = 2} */
+  napi_value fv, dv;
+  const int has_flux = ot == napi_object && option_given(env, options_v, "flux", &fv);
+  if (has_flux && !parse_flux(env, j, fv)) return 0;
+  if (has_flux && !option_given(env, options_v, "deltaWidth", &dv) && !option_given(env, options_v, "deltaOrder", &dv)) {
+    /* flux and no delta key: no deltas */
+  } else if (ot == napi_object) {  /* the trailing options: {deltaWidth = 2, deltaOrder = 2} */
     if (!option_u32(env, options_v, "deltaWidth", 1, MGX_DELTA_MAX_WIDTH, 2, &j->delta_width)) return 0;
     if (!option_u32(env, options_v, "deltaOrder", 1, 2, 2, &j->delta_order)) return 0;
     j->deltas.struct_size = sizeof j->deltas;
@@ -551,7 +640,7 @@ static int job_prepare_summary(napi_env env, job* j, napi_value samples_v, napi_
     return 0;
   }
   j->nsignals = count - 1;
-  return job_prepare_gather(env, j, samples_v, starts_v, feats);
+  return job_prepare_gather(env, j, samples_v, starts_v, feats) && job_alloc_flux(env, j);
 }
 
 /* Field i of a summary (the complex spectrum has none) */
@@ -674,7 +763,10 @@ static void job_run(job* j) {
     return;
   }
   const uint32_t n = j->box->desc.buffer_size;
-  if (j->summary && j->delta_order)
+  if (j->summary && j->num_flux)
+    j->rc = mgx_summarize_flux_host(j->box->plan, j->frames, j->nsamples, j->starts, j->nframes, j->frame_offsets, j->nsignals,
+                                    NULL, NULL, &j->sum, j->delta_order ? &j->deltas : NULL, j->flux, j->num_flux);
+  else if (j->summary && j->delta_order)
     j->rc = mgx_summarize_deltas_host(j->box->plan, j->frames, j->nsamples, j->starts, j->nframes, j->frame_offsets, j->nsignals,
                                       NULL, NULL, &j->sum, &j->deltas);
   else if (j->summary)
@@ -737,6 +829,22 @@ static napi_value job_result(napi_env env, job* j) {
         if (j->want[i] && nm) napi_set_named_property(env, sub, nm, typed_of(env, j->drefs[k][i], j->bytes[i], napi_float64_array, 8));
       }
       napi_set_named_property(env, obj, k ? "delta2" : "delta", sub);
+    }
+    /* the flux: an array, one {summary, perFrame} per request */
+    if (j->num_flux) {
+      napi_value arr;
+      if (napi_create_array_with_length(env, j->num_flux, &arr) != napi_ok) return NULL;
+      for (uint32_t i = 0; i < j->num_flux; ++i) {
+        napi_value one;
+        if (napi_create_object(env, &one) != napi_ok) return NULL;
+        if (j->frefs[0][i])
+          napi_set_named_property(env, one, "summary",
+                                  typed_of(env, j->frefs[0][i], (size_t)j->nsignals * MGX_NUM_STATS * sizeof(double), napi_float64_array, 8));
+        if (j->frefs[1][i])
+          napi_set_named_property(env, one, "perFrame", typed_of(env, j->frefs[1][i], (size_t)j->nframes * sizeof(float), napi_float32_array, 4));
+        napi_set_element(env, arr, i, one);
+      }
+      napi_set_named_property(env, obj, "flux", arr);
     }
     return obj;
   }

@@ -41,6 +41,7 @@ EXPORTS = ["mgx_plan_desc_init", "mgx_plan_create", "mgx_plan_destroy", "mgx_pla
            "mgx_summary_workspace_bytes", "mgx_summarize_device", "mgx_summarize_host",
            "mgx_delta_device", "mgx_summarize_deltas_workspace_bytes", "mgx_summarize_deltas_device",
            "mgx_summarize_deltas_host",
+           "mgx_flux_device", "mgx_summarize_flux_workspace_bytes", "mgx_summarize_flux_device", "mgx_summarize_flux_host",
            "mgx_shard_range", "mgx_packed_layout", "mgx_comm_unique_id", "mgx_group_create",
            "mgx_group_create_rank", "mgx_group_create_loopback", "mgx_group_create_loopback_rccl", "mgx_group_destroy",
            "mgx_group_info", "mgx_group_comm_info", "mgx_group_extract_device", "mgx_group_extract_host"]
@@ -124,6 +125,19 @@ class DeltaSummaries(ctypes.Structure):
     """mgx_delta_summaries: the summaries of the delta and second-order rows (the mgx_summarize_deltas_* calls)."""
     _fields_ = [("struct_size", ctypes.c_uint32), ("width", ctypes.c_uint32),
                 ("delta", ctypes.POINTER(SummaryOutputs)), ("delta2", ctypes.POINTER(SummaryOutputs))]
+
+
+FLUX_MODES = {"rectified": 0, "l1": 1, "l2": 2}  # mgx_flux_mode
+FLUX_MAX_LAG = 8  # MGX_FLUX_MAX_LAG
+FLUX_MAX_REQUESTS = 4  # MGX_FLUX_MAX_REQUESTS
+# the fields a summary call takes the flux of (mgx_flux_request.field), by feature name; "loudness": its specific rows
+FLUX_FEATURES = {"loudness": 13, "mfcc": 14, "amplitudeSpectrum": 15, "powerSpectrum": 16, "melBands": 19}
+
+
+class FluxRequest(ctypes.Structure):
+    """mgx_flux_request: one flux of one field through the mgx_summarize_flux_* calls."""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("field", ctypes.c_uint32), ("mode", ctypes.c_uint32), ("lag", ctypes.c_uint32),
+                ("per_frame", ctypes.c_void_p), ("summary", ctypes.c_void_p)]
 
 
 class HostTables(ctypes.Structure):
@@ -229,6 +243,17 @@ def lib():
         L.mgx_summarize_deltas_host.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p,
                                                 ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(Outputs), aux,
                                                 summ, dsum]
+        freq = ctypes.POINTER(FluxRequest)
+        L.mgx_flux_device.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p,
+                                      ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p]
+        L.mgx_summarize_flux_workspace_bytes.argtypes = [ctypes.c_void_p, ctypes.POINTER(Outputs), aux, summ, dsum, freq,
+                                                         ctypes.c_uint32, ctypes.c_uint64, ctypes.c_uint64, u64p]
+        L.mgx_summarize_flux_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p,
+                                                ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(Outputs), aux,
+                                                summ, dsum, freq, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p]
+        L.mgx_summarize_flux_host.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p,
+                                              ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(Outputs), aux,
+                                              summ, dsum, freq, ctypes.c_uint32]
         L.mgx_shard_range.argtypes = [ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, u64p, u64p]
         L.mgx_packed_layout.argtypes = [ctypes.POINTER(PlanDesc), ctypes.c_uint32, ctypes.c_uint64, u64p]
         L.mgx_packed_layout.restype = ctypes.c_uint64
@@ -541,7 +566,55 @@ class Plan:
                                                 None if deltas is None else ctypes.byref(deltas),
                                                 ctypes.c_void_p(workspace_ptr), workspace_bytes, ctypes.c_void_p(stream or 0)))
 
-    def summarize_gather_torch(self, samples, starts, frame_offsets, features, per_frame=(), stream=None, deltas=None):
+    def _flux_requests(self, F, S, flux, alloc, alloc32):
+        """flux: a list of dicts {feature, mode ("rectified", "l1", "l2" or its number; default "rectified"), lag
+        (default 1), per_frame (default False), summary (default True)}. Returns the array of FluxRequest over
+        arrays alloc((S, 4)) (float64) and alloc32((F,)) (float32), and the results: one dict per request with
+        "feature", "mode", "lag", "summary" ((S, 4): mean, variance, min, max of the flux per signal, or None) and
+        "per_frame" ((F,), or None). Numbers out of range pass through: the library refuses them with its message."""
+        reqs = (FluxRequest * max(len(flux), 1))()
+        ptr = lambda a: a.data_ptr() if hasattr(a, "data_ptr") else a.ctypes.data
+        out = []
+        for i, f in enumerate(flux):
+            name = f["feature"]
+            if name not in FLUX_FEATURES:
+                raise ValueError("%r has no flux" % (name,))
+            mode = f.get("mode", "rectified")
+            if isinstance(mode, str):
+                if mode not in FLUX_MODES:
+                    raise ValueError("flux mode %r: one of %s" % (mode, sorted(FLUX_MODES)))
+                mode = FLUX_MODES[mode]
+            res = {"feature": name, "mode": mode, "lag": f.get("lag", 1), "summary": None, "per_frame": None}
+            r = reqs[i]
+            r.struct_size = ctypes.sizeof(FluxRequest)
+            r.field, r.mode, r.lag = FLUX_FEATURES[name], mode, res["lag"]
+            if f.get("summary", True):
+                res["summary"] = alloc((S, len(STATS)))
+                r.summary = ptr(res["summary"])
+            if f.get("per_frame", False):
+                res["per_frame"] = alloc32((F,))
+                r.per_frame = ptr(res["per_frame"])
+            out.append(res)
+        return reqs, out
+
+    def summarize_flux_workspace_bytes(self, outputs, summary, deltas, flux, num_flux, num_frames, num_signals):
+        """mgx_summarize_flux_workspace_bytes (host only); deltas: a DeltaSummaries or None; flux: a FluxRequest array."""
+        b = ctypes.c_uint64()
+        check(lib().mgx_summarize_flux_workspace_bytes(self._h, ctypes.byref(outputs), _aux_ref(outputs), ctypes.byref(summary),
+                                                       None if deltas is None else ctypes.byref(deltas), flux, num_flux,
+                                                       num_frames, num_signals, ctypes.byref(b)))
+        return b.value
+
+    def summarize_flux_device(self, samples_ptr, num_samples, starts_ptr, num_frames, offsets_ptr, num_signals, outputs,
+                              summary, deltas, flux, num_flux, workspace_ptr, workspace_bytes, stream=None):
+        """mgx_summarize_flux_device on device pointers (async on `stream`)."""
+        check(lib().mgx_summarize_flux_device(self._h, ctypes.c_void_p(samples_ptr), num_samples, ctypes.c_void_p(starts_ptr),
+                                              num_frames, ctypes.c_void_p(offsets_ptr), num_signals, ctypes.byref(outputs),
+                                              _aux_ref(outputs), ctypes.byref(summary),
+                                              None if deltas is None else ctypes.byref(deltas), flux, num_flux,
+                                              ctypes.c_void_p(workspace_ptr), workspace_bytes, ctypes.c_void_p(stream or 0)))
+
+    def summarize_gather_torch(self, samples, starts, frame_offsets, features, per_frame=(), stream=None, deltas=None, flux=None):
         """extract_gather_torch with every signal's rows pooled on the device: signal s owns rows
         [frame_offsets[s], frame_offsets[s + 1]) (int64 CUDA tensors, or anything numpy turns into one). Returns
         (summaries, rows): per pooled field a float64 CUDA tensor (S, 4, width) of mean, variance, min, max, and
@@ -550,7 +623,10 @@ class Plan:
         stream: a caller who passes another stream synchronises it before allocating again.
         deltas = (width, order): the rows' regression deltas of that half-width are pooled too
         (mgx_summarize_deltas_device), and the result is (summaries, rows, delta_summaries, delta2_summaries), the
-        last None at order 1."""
+        last None at order 1.
+        flux = a list of requests (_flux_requests): the flux of those fields per frame and pooled
+        (mgx_summarize_flux_device); the result then has one more element, the list of the requests' results
+        (a per_frame column is zero in rows that belong to no signal)."""
         import torch
         assert samples.is_cuda and samples.dtype == torch.float32 and samples.is_contiguous() and samples.dim() == 1
         dev = samples.device
@@ -566,6 +642,18 @@ class Plan:
         summ, so = self._summary_outputs(S, features, lambda shape: torch.empty(shape, dtype=torch.float64, device=dev))
         if stream is None:
             stream = torch.cuda.current_stream(dev).cuda_stream
+        if flux is not None:
+            d1 = d2 = ds = None
+            if deltas is not None:
+                d1, d2, ds = self._delta_summaries(S, features, deltas,
+                                                   lambda shape: torch.empty(shape, dtype=torch.float64, device=dev))
+            reqs, fres = self._flux_requests(F, S, flux, lambda shape: torch.empty(shape, dtype=torch.float64, device=dev),
+                                             lambda shape: torch.zeros(shape, dtype=torch.float32, device=dev))
+            nbytes = self.summarize_flux_workspace_bytes(o, so, ds, reqs, len(flux), F, S)
+            ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+            self.summarize_flux_device(samples.data_ptr(), samples.shape[0], starts.data_ptr(), F, frame_offsets.data_ptr(), S,
+                                       o, so, ds, reqs, len(flux), ws.data_ptr(), nbytes, stream)
+            return (summ, rows, d1, d2, fres) if deltas is not None else (summ, rows, fres)
         if deltas is not None:
             d1, d2, ds = self._delta_summaries(S, features, deltas,
                                                lambda shape: torch.empty(shape, dtype=torch.float64, device=dev))
@@ -580,9 +668,10 @@ class Plan:
                               ws.data_ptr(), nbytes, stream)
         return summ, rows
 
-    def summarize_gather(self, samples, starts, frame_offsets, features, per_frame=(), deltas=None):
+    def summarize_gather(self, samples, starts, frame_offsets, features, per_frame=(), deltas=None, flux=None):
         """Host numpy in / numpy out (mgx_summarize_host): (summaries, rows) as summarize_gather_torch gives them;
-        with deltas = (width, order) (mgx_summarize_deltas_host), (summaries, rows, delta_summaries, delta2_summaries)."""
+        with deltas = (width, order) (mgx_summarize_deltas_host), (summaries, rows, delta_summaries, delta2_summaries);
+        with flux = a list of requests (mgx_summarize_flux_host), one more element: the requests' results."""
         samples = np.ascontiguousarray(samples, dtype=np.float32)
         starts = np.ascontiguousarray(starts, dtype=np.uint64)
         frame_offsets = np.ascontiguousarray(frame_offsets, dtype=np.uint64)
@@ -590,6 +679,16 @@ class Plan:
         S = frame_offsets.size - 1
         rows, o = self._host_outputs(starts.size, per_frame)
         summ, so = self._summary_outputs(S, features, lambda shape: np.empty(shape, np.float64))
+        if flux is not None:
+            d1 = d2 = ds = None
+            if deltas is not None:
+                d1, d2, ds = self._delta_summaries(S, features, deltas, lambda shape: np.empty(shape, np.float64))
+            reqs, fres = self._flux_requests(starts.size, S, flux, lambda shape: np.empty(shape, np.float64),
+                                             lambda shape: np.zeros(shape, np.float32))
+            check(lib().mgx_summarize_flux_host(self._h, samples.ctypes.data, samples.size, starts.ctypes.data, starts.size,
+                                                frame_offsets.ctypes.data, S, ctypes.byref(o), _aux_ref(o), ctypes.byref(so),
+                                                None if ds is None else ctypes.byref(ds), reqs, len(flux)))
+            return (summ, rows, d1, d2, fres) if deltas is not None else (summ, rows, fres)
         if deltas is not None:
             d1, d2, ds = self._delta_summaries(S, features, deltas, lambda shape: np.empty(shape, np.float64))
             check(lib().mgx_summarize_deltas_host(self._h, samples.ctypes.data, samples.size, starts.ctypes.data, starts.size,
@@ -600,15 +699,22 @@ class Plan:
                                        frame_offsets.ctypes.data, S, ctypes.byref(o), _aux_ref(o), ctypes.byref(so)))
         return summ, rows
 
-    def summarize_signals(self, signals, hop, features, per_frame=(), deltas=None):
+    def summarize_signals(self, signals, hop, features, per_frame=(), deltas=None, flux=None):
         """A list of 1-D host signals in one call, pooled per signal: returns (summaries, frame_offsets), summaries
         being {name: ndarray (S, 4, width)} of mean, variance, min, max (STATS) over each signal's buffers; with
         `per_frame`, (summaries, frame_offsets, rows), rows as extract_signals gives them for those features.
         With deltas = (width, order): (summaries, rows, delta_summaries, delta2_summaries) as summarize_gather gives
-        them (frame_offsets: signals_frame_starts of the signals' lengths)."""
+        them (frame_offsets: signals_frame_starts of the signals' lengths).
+        With flux = a list of requests: one more element behind what the call returns without it, the requests' results."""
         signals = [np.ascontiguousarray(x, dtype=np.float32).ravel() for x in signals]
         starts, frame_offsets = signals_frame_starts([x.size for x in signals], self.n, hop)
         samples = np.concatenate(signals) if signals else np.empty(0, np.float32)
+        if flux is not None:
+            r = self.summarize_gather(samples, starts, frame_offsets, features, per_frame, deltas=deltas, flux=flux)
+            if deltas is not None:
+                return r
+            summ, rows, fres = r
+            return (summ, frame_offsets, rows, fres) if per_frame else (summ, frame_offsets, fres)
         if deltas is not None:
             return self.summarize_gather(samples, starts, frame_offsets, features, per_frame, deltas=deltas)
         summ, rows = self.summarize_gather(samples, starts, frame_offsets, features, per_frame)
@@ -871,4 +977,42 @@ def delta_torch(rows, frame_offsets=None, width=2, order=2, stream=None):
         stream = torch.cuda.current_stream(rows.device).cuda_stream
     delta_device(rows.data_ptr(), F, cols, rows.dtype == torch.float64, None if frame_offsets is None else frame_offsets.data_ptr(),
                  S, width, out[0].data_ptr(), out[1].data_ptr() if order == 2 else None, stream)
+    return out
+
+
+def flux_device(rows_ptr, num_frames, cols, rows_f64, offsets_ptr, num_signals, mode, lag, flux_ptr, stream=None):
+    """mgx_flux_device on device pointers (async on `stream`); a pointer may be None."""
+    check(lib().mgx_flux_device(ctypes.c_void_p(rows_ptr or 0), num_frames, cols, 1 if rows_f64 else 0,
+                                ctypes.c_void_p(offsets_ptr or 0), num_signals, mode, lag, ctypes.c_void_p(flux_ptr or 0),
+                                ctypes.c_void_p(stream or 0)))
+
+
+def flux_torch(rows, frame_offsets=None, mode="rectified", lag=1, stream=None, out=None):
+    """The spectral flux of `rows`, a (F,) or (F, cols) float32 or float64 CUDA tensor, within each signal: the
+    distance of every row from the row `lag` before it, clamped at the signal's first row (include/meyda_gpu.h).
+    mode: "rectified", "l1" or "l2". Signal s owns rows [frame_offsets[s], frame_offsets[s + 1]) (an int64 CUDA
+    tensor, or anything numpy turns into one; None: one signal, every row). Returns a (F,) tensor of rows' type
+    (`out` when given, written where a row belongs to a signal); rows that belong to no signal are 0."""
+    import torch
+    assert rows.is_cuda and rows.is_contiguous() and rows.dim() in (1, 2) and rows.dtype in (torch.float32, torch.float64)
+    if isinstance(mode, str):
+        if mode not in FLUX_MODES:
+            raise ValueError("flux mode %r: one of %s" % (mode, sorted(FLUX_MODES)))
+        mode = FLUX_MODES[mode]
+    F = rows.shape[0]
+    cols = rows.shape[1] if rows.dim() == 2 else 1
+    S = 0
+    if frame_offsets is not None:
+        if not torch.is_tensor(frame_offsets):
+            frame_offsets = torch.from_numpy(np.ascontiguousarray(frame_offsets, dtype=np.uint64).view(np.int64)).to(rows.device)
+        assert frame_offsets.is_cuda and frame_offsets.dtype == torch.int64 and frame_offsets.is_contiguous()
+        assert frame_offsets.dim() == 1 and frame_offsets.shape[0] >= 1
+        S = frame_offsets.shape[0] - 1
+    if out is None:
+        out = torch.zeros(F, dtype=rows.dtype, device=rows.device)
+    assert out.is_cuda and out.is_contiguous() and out.dtype == rows.dtype and out.shape == (F,)
+    if stream is None:
+        stream = torch.cuda.current_stream(rows.device).cuda_stream
+    flux_device(rows.data_ptr(), F, cols, rows.dtype == torch.float64, None if frame_offsets is None else frame_offsets.data_ptr(),
+                S, mode, lag, out.data_ptr(), stream)
     return out

@@ -3323,6 +3323,147 @@ hipError_t launch_delta(const void* rows, void* out, uint64_t num_frames, uint32
   return hipGetLastError();
 }
 
+// ---- Spectral flux (mgx_flux_device, mgx_summarize_flux_*): the distance of every row from an earlier row of its signal ----
+// A reduction over two rows, memory-bound. A row belongs to a group of G consecutive lanes, G the power of two
+// that holds its columns up to a wave's 64: lane l of the group owns the partial P[l] of the definition
+// (include/meyda_gpu.h) and adds the terms of columns l, l + 64, ... in ascending order, then the groups fold
+// with __shfl_xor at distances G/2 .. 1 -- the definition's halvings from the first that can hold a term on
+// (the earlier ones add a +0 to a value that is >= +0 or NaN: no bit changes), so a 13-column row on 16 lanes
+// and one on a wave give the same bits. A wave's loads are consecutive addresses whatever cols is: 64 columns of
+// one row, or the whole rows of 64 / G consecutive rows. A workgroup owns a tile of consecutive rows and its
+// groups take them in ascending order, 256 / G at a time, so the earlier row t - lag is one a neighbouring group
+// reads in the same pass or read a pass before: it comes from L1 / L2, and only a tile's first lag rows are
+// another workgroup's. The row's signal is looked up once per row of the tile (a binary search by the tile's
+// first threads, kept in LDS). No atomics; one writer per output; nothing depends on the grid.
+// A launch may cover rows [row0, row0 + nrows) of a longer array (a chunk of mgx_summarize_flux_host): the
+// table counts rows of the whole array, and the lag rows before row0 are read from `carry`.
+namespace {
+
+constexpr uint32_t kFluxTileRows = 1024;     // at most: every thread of the workgroup resolves four rows
+constexpr uint32_t kFluxTileElems = 32768;   // a tile's elements, about
+constexpr uint32_t kFluxTiles = 4096;        // tiles a launch is cut into, where its rows allow (16 a CU)
+constexpr uint64_t kFluxNoSignal = ~0ull;
+
+struct FluxArgs {
+  const void* rows;       // row row0 of the array
+  const void* carry;      // rows row0 - lag .. row0 - 1 (null when row0 is 0: no row before the array's first)
+  void* out;              // the flux of row row0
+  const uint64_t* table;  // null: one signal, rows [0, num_frames)
+  uint64_t num_signals, num_frames, row0, nrows, ntiles;
+  uint32_t cols, mode, lag, tile_rows, group, group_log2;
+};
+
+template <typename T>
+__global__ __launch_bounds__(256) void flux_kernel(FluxArgs g) {
+  __shared__ uint64_t sig_a[kFluxTileRows];
+  const T* __restrict__ const rows = static_cast<const T*>(g.rows);
+  const T* __restrict__ const carry = static_cast<const T*>(g.carry);
+  T* __restrict__ const out = static_cast<T*>(g.out);
+  const uint32_t G = g.group, lane = threadIdx.x & (G - 1), grp = threadIdx.x >> g.group_log2, ngrp = 256u >> g.group_log2;
+  const uint32_t mode = g.mode, cols = g.cols;
+  const uint64_t L = g.lag, T_ = g.num_frames;
+  for (uint64_t tile = blockIdx.x; tile < g.ntiles; tile += gridDim.x) {
+    const uint64_t r0 = tile * g.tile_rows;
+    const uint32_t nr = g.nrows - r0 < g.tile_rows ? (uint32_t)(g.nrows - r0) : g.tile_rows;
+    for (uint32_t i = threadIdx.x; i < nr; i += 256) {
+      // the row's signal: the last s with table[s] <= t; its first row, or none when the row belongs to no signal
+      const uint64_t t = g.row0 + r0 + i;
+      uint64_t a = 0, b = T_;
+      if (g.table) {
+        uint64_t lo = 0, hi = g.num_signals + 1;  // the first entry above t
+        while (lo < hi) {
+          const uint64_t mid = lo + (hi - lo) / 2;
+          if (g.table[mid] <= t) lo = mid + 1;
+          else hi = mid;
+        }
+        a = b = 0;
+        if (lo > 0 && lo <= g.num_signals) {
+          a = g.table[lo - 1];
+          b = g.table[lo];
+          a = a < T_ ? a : T_;
+          b = b < T_ ? b : T_;
+        }
+      }
+      sig_a[i] = t >= a && t < b ? a : kFluxNoSignal;
+    }
+    __syncthreads();
+    for (uint32_t i = grp; i < nr; i += ngrp) {
+      const uint64_t a = sig_a[i];
+      if (a == kFluxNoSignal) continue;  // (whatever the table holds: a <= t < num_frames from here on)
+      const uint64_t tl = r0 + i, t = g.row0 + tl;
+      const uint64_t p = t >= a + L ? t - L : a;  // row0 - lag <= p <= t
+      const T* __restrict__ const xt = rows + tl * cols;
+      const T* __restrict__ const xp = p >= g.row0 ? rows + (p - g.row0) * cols : carry + (p + L - g.row0) * cols;
+      double P = 0.0;
+      auto term = [&](T vt, T vp) {
+        const double x = (double)vt, y = (double)vp;
+        const double d = x == y ? 0.0 : x - y;
+        const double e = mode == MGX_FLUX_L2 ? d * d : mode == MGX_FLUX_L1 ? fabs(d) : (d > 0.0 || d != d) ? d : 0.0;
+        P += e;
+      };
+      uint64_t c = lane;
+      // (a wave per row: eight loads in flight per lane ahead of the additions, whose order is the columns')
+      if (G == 64)
+        for (; c + 192 < cols; c += 256) {
+          T vt[4], vp[4];
+#pragma unroll
+          for (int k = 0; k < 4; ++k) vt[k] = xt[c + 64 * k];
+#pragma unroll
+          for (int k = 0; k < 4; ++k) vp[k] = xp[c + 64 * k];
+#pragma unroll
+          for (int k = 0; k < 4; ++k) term(vt[k], vp[k]);
+        }
+      for (; c < cols; c += 64) term(xt[c], xp[c]);  // (G < 64: cols <= G, one term at the most)
+#pragma unroll
+      for (uint32_t h = 32; h >= 1; h >>= 1)
+        if (h < G) P += __shfl_xor(P, (int)h);
+      if (lane == 0) out[tl] = (T)(mode == MGX_FLUX_L2 ? sqrt(P) : P);
+    }
+    __syncthreads();
+  }
+}
+
+}  // namespace
+
+hipError_t launch_flux(const void* rows, const void* carry, void* out, uint64_t row0, uint64_t nrows, uint64_t num_frames,
+                       uint32_t cols, bool f64, const uint64_t* table, uint64_t num_signals, uint32_t mode, uint32_t lag,
+                       hipStream_t stream) {
+  if (nrows == 0) return hipSuccess;
+  if (cols == 0 || mode >= MGX_NUM_FLUX_MODES || lag == 0 || lag > MGX_FLUX_MAX_LAG || row0 + nrows > num_frames ||
+      (row0 > 0 && !carry))
+    return hipErrorInvalidValue;
+  FluxArgs g{};
+  g.rows = rows;
+  g.carry = carry;
+  g.out = out;
+  g.table = table;
+  g.num_signals = num_signals;
+  g.num_frames = num_frames;
+  g.row0 = row0;
+  g.nrows = nrows;
+  g.cols = cols;
+  g.mode = mode;
+  g.lag = lag;
+  g.group = 1;
+  while (g.group < cols && g.group < 64) {
+    g.group <<= 1;
+    ++g.group_log2;
+  }
+  // a tile: about kFluxTileElems elements, at least one pass of the workgroup's groups and 64 rows (so the lag rows
+  // another workgroup owns are few beside it); smaller, down to that, while the launch has fewer than
+  // kFluxTiles tiles to spread over the device (no bit depends on it)
+  const uint32_t least = 256u >> g.group_log2 > 64u ? 256u >> g.group_log2 : 64u;
+  g.tile_rows = kFluxTileElems / cols;
+  if (g.tile_rows > kFluxTileRows) g.tile_rows = kFluxTileRows;
+  if ((uint64_t)g.tile_rows * kFluxTiles > nrows) g.tile_rows = (uint32_t)(nrows / kFluxTiles);
+  if (g.tile_rows < least) g.tile_rows = least;
+  g.ntiles = (nrows + g.tile_rows - 1) / g.tile_rows;
+  const unsigned grid = (unsigned)(g.ntiles < 16384 ? g.ntiles : 16384);
+  if (f64) hipLaunchKernelGGL((flux_kernel<double>), dim3(grid), dim3(256), 0, stream, g);
+  else hipLaunchKernelGGL((flux_kernel<float>), dim3(grid), dim3(256), 0, stream, g);
+  return hipGetLastError();
+}
+
 }  // namespace mgx
 
 #if MGX_WAVE_TIMES

@@ -232,6 +232,13 @@ hipError_t launch_summary_final(const SummaryArgs& a, hipStream_t stream);
 // instead of read from memory. Rows that belong to no signal are not written. One launch, asynchronous.
 hipError_t launch_delta(const void* rows, void* out, uint64_t num_frames, uint32_t cols, bool f64, const uint64_t* table,
                         uint64_t num_signals, uint32_t width, bool second, hipStream_t stream);
+// Spectral flux (mgx_flux_device, mgx_summarize_flux_*; kernels.hip flux_kernel): out[i] = the flux of row row0 + i
+// of an array of num_frames rows x cols (float32 or float64 as f64 says) within the row's signal, for the nrows
+// rows from row0 on (row0 + nrows <= num_frames). rows, out: at row row0; carry: the lag rows before row0 (a host
+// chunk's; may be null when row0 is 0). The table as launch_delta reads it. One launch, asynchronous.
+hipError_t launch_flux(const void* rows, const void* carry, void* out, uint64_t row0, uint64_t nrows, uint64_t num_frames,
+                       uint32_t cols, bool f64, const uint64_t* table, uint64_t num_signals, uint32_t mode, uint32_t lag,
+                       hipStream_t stream);
 size_t extract_lds_bytes(int n, int ncoef, int nfilt, bool chain);
 size_t lds_image_bytes(int n, int ncoef, int nfilt);  // DevTables::lds_image, a multiple of 16
 hipError_t launch_lds_image(int n, int precision, int mode, const KernelArgs& a, void* image, hipStream_t stream);

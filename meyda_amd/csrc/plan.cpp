@@ -496,6 +496,10 @@ struct mgx_plan {
   // table, shifts, partials and summaries of their own (one allocation beside s_sum, grown when a call needs more)
   unsigned char* s_delta = nullptr;
   size_t s_delta_bytes = 0;
+  // mgx_summarize_flux_host: a table, per request the two carries of lag rows and the flux column of the whole
+  // call, then shifts, partials and summaries (one allocation, grown when a call needs more)
+  unsigned char* s_flux = nullptr;
+  size_t s_flux_bytes = 0;
   hipStream_t s_copy = nullptr, s_comp = nullptr;
   hipEvent_t ev_loaded[2] = {nullptr, nullptr}, ev_done[2] = {nullptr, nullptr}, ev_back[2] = {nullptr, nullptr};
   // small host batches (kSmallBatchFrames): pinned, device-mapped, coherent host buffers
@@ -847,6 +851,7 @@ int mgx_plan_destroy(mgx_plan* p) {
   }
   if (p->s_sum) (void)hipFree(p->s_sum);
   if (p->s_delta) (void)hipFree(p->s_delta);
+  if (p->s_flux) (void)hipFree(p->s_flux);
   if (p->s_copy) (void)hipStreamDestroy(p->s_copy);
   if (p->s_comp) (void)hipStreamDestroy(p->s_comp);
   if (p->s_res) (void)hipStreamDestroy(p->s_res);
@@ -1884,9 +1889,224 @@ int delta_pool(const mgx_plan_desc& d, DeltaReq& q, const mgx::Outputs& x, unsig
   return e == hipSuccess ? (int)MGX_OK : hip_fail(e, "delta and summary kernel launch");
 }
 
+// mgx_summarize_flux_*: the caller's requests, the fields whose rows the call has to hold, and the requests that
+// are pooled as the columns of one summary launch (each of width 1; destinations the caller's arrays).
+struct FluxReq {
+  uint32_t n = 0;
+  mgx_flux_request r[MGX_FLUX_MAX_REQUESTS];
+  uint32_t cols[MGX_FLUX_MAX_REQUESTS] = {};
+  uint32_t rows = 0;
+  SummaryFields sf;
+  int pooled[MGX_FLUX_MAX_REQUESTS] = {};  // column k of sf is request pooled[k]
+  bool any() const { return n != 0; }
+};
+
+int flux_request(const mgx_plan* p, const mgx_flux_request* fr, uint32_t num, uint64_t nsignals, FluxReq* q) {
+  if (num == 0) return MGX_OK;
+  if (!fr) return fail(MGX_E_INVALID_ARGUMENT, "flux is NULL with num_flux = %u", num);
+  if (num > MGX_FLUX_MAX_REQUESTS) return fail(MGX_E_INVALID_ARGUMENT, "num_flux is %u, at most %d", num, MGX_FLUX_MAX_REQUESTS);
+  for (uint32_t i = 0; i < num; ++i) {
+    const mgx_flux_request& r = fr[i];
+    if (r.struct_size != sizeof(mgx_flux_request))
+      return fail(MGX_E_INVALID_ARGUMENT, "mgx_flux_request.struct_size is %u, expected %zu (flux[%u])", r.struct_size,
+                  sizeof(mgx_flux_request), i);
+    if (r.mode >= MGX_NUM_FLUX_MODES)
+      return fail(MGX_E_INVALID_ARGUMENT, "mgx_flux_request.mode is %u, expected 0..%d (flux[%u])", r.mode, MGX_NUM_FLUX_MODES - 1, i);
+    if (r.lag < 1 || r.lag > MGX_FLUX_MAX_LAG)
+      return fail(MGX_E_INVALID_ARGUMENT, "mgx_flux_request.lag is %u, expected 1..%d (flux[%u])", r.lag, MGX_FLUX_MAX_LAG, i);
+    if (!r.per_frame && !r.summary)
+      return fail(MGX_E_INVALID_ARGUMENT, "mgx_flux_request.per_frame and .summary are both NULL (flux[%u])", i);
+    if (r.summary && nsignals == 0)
+      return fail(MGX_E_INVALID_ARGUMENT, "mgx_flux_request.summary is set with num_signals = 0 (flux[%u])", i);
+    if (r.field != MGX_LOUDNESS && r.field != MGX_MFCC && r.field != MGX_AMPLITUDE_SPECTRUM && r.field != MGX_POWER_SPECTRUM &&
+        r.field != MGX_MEL_BANDS)
+      return fail(MGX_E_UNSUPPORTED, "mgx_flux_request.field is %u: flux is taken of the loudness, mfcc, spectrum and mel_bands rows (flux[%u])",
+                  r.field, i);
+  }
+  q->n = num;
+  for (uint32_t i = 0; i < num; ++i) {
+    q->r[i] = fr[i];
+    q->rows |= 1u << fr[i].field;
+    if (p) q->cols[i] = (uint32_t)(mgx::out_field_bytes(p->d, (int)fr[i].field) / 4);
+    if (!fr[i].summary) continue;
+    mgx::SummaryField& f = q->sf.a.f[q->sf.a.nfields];
+    f.dst = fr[i].summary;
+    f.width = 1;
+    f.col0 = q->sf.a.nfields;
+    f.f64 = 0;
+    q->pooled[q->sf.a.nfields++] = (int)i;
+  }
+  q->sf.a.cols = q->sf.a.nfields;
+  return MGX_OK;
+}
+
+// What the flux requests add to the buffer a summary call works in, from `base` bytes on. Host call: a table and
+// per request two carries of lag rows. Both: the flux column of a request the buffer has to hold (device call:
+// one without per_frame; host call: every one), the pooling's shifts and partials and (host call) the summaries.
+struct FluxLayout {
+  uint64_t table, carry[MGX_FLUX_MAX_REQUESTS][2], col[MGX_FLUX_MAX_REQUESTS], shift, part, result, total;
+};
+
+FluxLayout flux_layout(const FluxReq& q, uint64_t nframes, uint64_t nsignals, bool host, uint64_t base) {
+  FluxLayout l{};
+  l.total = base;
+  auto take = [&l](uint64_t bytes) {
+    const uint64_t at = l.total;
+    l.total += (bytes + 255) / 256 * 256;
+    return at;
+  };
+  if (!q.any() || nsignals == 0 || nframes == 0) return l;
+  if (host) l.table = take((nsignals + 1) * sizeof(uint64_t));
+  for (uint32_t i = 0; i < q.n; ++i) {
+    if (host)
+      for (int k = 0; k < 2; ++k) l.carry[i][k] = take((uint64_t)q.r[i].lag * q.cols[i] * sizeof(float));
+    l.col[i] = host || !q.r[i].per_frame ? take(nframes * sizeof(float)) : UINT64_MAX;
+  }
+  const uint64_t cols = q.sf.a.cols;
+  l.shift = take(nsignals * cols * sizeof(double));
+  l.part = take((nframes / mgx::kSummaryBlock + nsignals + 1) * mgx::kSummaryWords * cols * sizeof(double));
+  if (host) l.result = take(nsignals * MGX_NUM_STATS * cols * sizeof(double));
+  return l;
+}
+
+// The pooling of the flux columns col[i] (nframes floats each, device memory) into the destinations of q.sf
+int flux_pool(FluxReq& q, float* const* col, unsigned char* buf, const FluxLayout& l, const uint64_t* table, uint64_t nframes,
+              uint64_t nsignals, hipStream_t st) {
+  mgx::SummaryArgs& a = q.sf.a;
+  if (a.cols == 0) return MGX_OK;
+  for (uint32_t k = 0; k < a.nfields; ++k) a.f[k].src = col[q.pooled[k]];
+  a.num_signals = nsignals;
+  a.num_frames = nframes;
+  a.table = table;
+  a.shift = reinterpret_cast<double*>(buf + l.shift);
+  a.part = reinterpret_cast<double*>(buf + l.part);
+  a.row0 = 0;
+  a.rows = nframes;
+  a.slot0 = 0;
+  a.nslots = nframes / mgx::kSummaryBlock + nsignals;
+  hipError_t e = mgx::launch_summary_partial(a, st);
+  if (e == hipSuccess) e = mgx::launch_summary_final(a, st);
+  return e == hipSuccess ? (int)MGX_OK : hip_fail(e, "summary kernel launch");
+}
+
 int summarize_host_impl(mgx_plan* p, const float* samples, uint64_t num_samples, const uint64_t* starts, uint64_t nframes,
                         const uint64_t* frame_offsets, uint64_t nsignals, const mgx_outputs* outputs, const mgx_aux_outputs* aux,
-                        const mgx_summary_outputs* summary, const mgx_delta_summaries* deltas);
+                        const mgx_summary_outputs* summary, const mgx_delta_summaries* deltas,
+                        const mgx_flux_request* flux = nullptr, uint32_t nflux = 0);
+
+// mgx_summarize_deltas_workspace_bytes (deltas there, no request) and mgx_summarize_flux_workspace_bytes (deltas or
+// not, requests): the summary call's buffer with the rows of every delta'd or flux'd field kept, then what the
+// deltas and the flux add.
+int summarize_more_workspace_bytes(const mgx_plan* p, const mgx_outputs* o, const mgx_aux_outputs* aux, const mgx_summary_outputs* summary,
+                                   const mgx_delta_summaries* deltas, const mgx_flux_request* flux, uint32_t nflux, uint64_t nframes,
+                                   uint64_t nsignals, uint64_t* bytes) {
+  if (!bytes) return fail(MGX_E_INVALID_ARGUMENT, "bytes is NULL");
+  const mgx_outputs none{};
+  mgx::Outputs x;
+  DeltaReq q;
+  FluxReq fq;
+  int rc = check_summary(summary);
+  if (rc || (rc = delta_request(p, deltas, &q)) || (rc = flux_request(p, flux, nflux, nsignals, &fq)) ||
+      (rc = make_outputs(p, o ? o : &none, aux, &x)))
+    return rc;
+  SummaryFields sf;
+  summary_fields(p, summary, &sf);
+  const uint32_t extra = (sf.pooled | q.rows[0] | fq.rows) & ~mgx::out_requested(x);
+  const SummaryLayout l = summary_layout(p->d, extra, sf.a.cols, nframes, nsignals, false, q.any() || fq.any());
+  const DeltaLayout dl = delta_layout(p->d, q, nframes, nsignals, false, l.total);
+  *bytes = flux_layout(fq, nframes, nsignals, false, dl.total).total;
+  return MGX_OK;
+}
+
+// The device call of the same two: the gather launch and the base pooling as mgx_summarize_device makes them, then
+// the deltas (delta_pool), then the flux operator per request and the pooling of its columns.
+int summarize_more_device(mgx_plan* p, const float* samples, uint64_t num_samples, const uint64_t* starts, uint64_t nframes,
+                          const uint64_t* frame_offsets, uint64_t nsignals, const mgx_outputs* o, const mgx_aux_outputs* aux,
+                          const mgx_summary_outputs* summary, const mgx_delta_summaries* deltas, const mgx_flux_request* flux,
+                          uint32_t nflux, void* workspace, uint64_t workspace_bytes, void* stream) {
+  const mgx_outputs none{};
+  mgx::Outputs x;
+  DeltaReq q;
+  FluxReq fq;
+  int rc = check_summary(summary);
+  if (rc || (rc = delta_request(p, deltas, &q)) || (rc = flux_request(p, flux, nflux, nsignals, &fq)) ||
+      (rc = make_outputs(p, o ? o : &none, aux, &x)))
+    return rc;
+  if (!q.any() && !fq.any())  // (no field named in either struct, no request: the summary call)
+    return mgx_summarize_device(p, samples, num_samples, starts, nframes, frame_offsets, nsignals, o, aux, summary, workspace,
+                                workspace_bytes, stream);
+  SummaryFields sf;
+  summary_fields(p, summary, &sf);
+  if ((rc = summary_inputs(p, samples, num_samples, starts, nframes, frame_offsets, nsignals))) return rc;
+  if ((rc = check_outputs(x))) return rc;
+  const uint32_t extra = (sf.pooled | q.rows[0] | fq.rows) & ~mgx::out_requested(x);
+  const SummaryLayout l = summary_layout(p->d, extra, sf.a.cols, nframes, nsignals, false, true);
+  const DeltaLayout dl = delta_layout(p->d, q, nframes, nsignals, false, l.total);
+  const FluxLayout fl = flux_layout(fq, nframes, nsignals, false, dl.total);
+  if (workspace_bytes < fl.total || (fl.total > 0 && !workspace))
+    return fail(MGX_E_INVALID_ARGUMENT, "the workspace holds %llu bytes, the call needs %llu (%s)", (unsigned long long)workspace_bytes,
+                (unsigned long long)fl.total, fq.any() ? "mgx_summarize_flux_workspace_bytes" : "mgx_summarize_deltas_workspace_bytes");
+  if (fl.total > 0 && reinterpret_cast<uintptr_t>(workspace) % 256 != 0)
+    return fail(MGX_E_INVALID_ARGUMENT, "the workspace is not 256-byte aligned");
+  unsigned char* const ws = static_cast<unsigned char*>(workspace);
+  // the launch's outputs: the caller's per-frame arrays, and for the other pooled, delta'd or flux'd fields the workspace's
+  mgx::Outputs u = x;
+  if (l.total > 0)
+    for (int i = 0; i < mgx::kOutFields; ++i)
+      if (l.frames[i] != UINT64_MAX) mgx::out_field(u, i) = ws + l.frames[i];
+  if (nframes > 0) {
+    const GatherLaunch g{starts, num_samples};
+    LaunchOpts opt;
+    opt.gather = &g;
+    if ((rc = extract_device_impl(p, samples, nframes, (uint64_t)p->n, l.total > 0 ? &u : &x, stream, opt))) return rc;
+  }
+  if (nsignals == 0) return MGX_OK;  // (no signal owns a row: the gather call, no flux written)
+  hipError_t e = hipSetDevice(p->d.device);
+  if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
+  mgx::SummaryArgs& a = sf.a;
+  a.num_signals = nsignals;
+  a.num_frames = nframes;
+  uint64_t* const table = nframes > 0 ? reinterpret_cast<uint64_t*>(ws + l.table) : nullptr;
+  if (nframes > 0) {
+    // the base summaries, exactly as mgx_summarize_device forms them; the table serves the deltas and the flux too
+    for (uint32_t i = 0; i < a.nfields; ++i) a.f[i].src = mgx::out_field(u, sf.index[i]);
+    a.table = table;
+    a.shift = reinterpret_cast<double*>(ws + l.shift);
+    a.part = reinterpret_cast<double*>(ws + l.part);
+    a.row0 = 0;
+    a.rows = nframes;
+    a.slot0 = 0;
+    a.nslots = nframes / mgx::kSummaryBlock + nsignals;
+    e = mgx::launch_summary_table(frame_offsets, table, nsignals, nframes, (hipStream_t)stream);
+    if (e == hipSuccess) e = mgx::launch_summary_partial(a, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, "summary kernel launch");
+  }
+  e = mgx::launch_summary_final(a, (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(e, "summary kernel launch");
+  if (nframes == 0) {
+    // no buffers: every signal is empty, NaN in all four (the final kernel reads neither rows nor table)
+    for (int k = 0; k < 2 && e == hipSuccess; ++k) {
+      q.sf[k].a.num_signals = nsignals;
+      q.sf[k].a.num_frames = 0;
+      e = mgx::launch_summary_final(q.sf[k].a, (hipStream_t)stream);
+    }
+    fq.sf.a.num_signals = nsignals;
+    fq.sf.a.num_frames = 0;
+    if (e == hipSuccess) e = mgx::launch_summary_final(fq.sf.a, (hipStream_t)stream);
+    return e == hipSuccess ? (int)MGX_OK : hip_fail(e, "summary kernel launch");
+  }
+  if (q.any() && (rc = delta_pool(p->d, q, u, ws, dl, table, nframes, nsignals, (hipStream_t)stream))) return rc;
+  if (!fq.any()) return MGX_OK;
+  // the operator per request over the field's rows, then the pooling of the one-column flux arrays
+  float* col[MGX_FLUX_MAX_REQUESTS];
+  for (uint32_t i = 0; i < fq.n; ++i) {
+    col[i] = fq.r[i].per_frame ? fq.r[i].per_frame : reinterpret_cast<float*>(ws + fl.col[i]);
+    e = mgx::launch_flux(mgx::out_field(u, (int)fq.r[i].field), nullptr, col[i], 0, nframes, nframes, fq.cols[i], false, table, nsignals,
+                         fq.r[i].mode, fq.r[i].lag, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, "flux kernel launch");
+  }
+  return flux_pool(fq, col, ws, fl, table, nframes, nsignals, (hipStream_t)stream);
+}
 
 }  // namespace
 
@@ -1921,18 +2141,7 @@ int mgx_summarize_deltas_workspace_bytes(const mgx_plan* p, const mgx_outputs* o
                                          const mgx_summary_outputs* summary, const mgx_delta_summaries* deltas, uint64_t nframes,
                                          uint64_t nsignals, uint64_t* bytes) {
   if (!deltas) return mgx_summary_workspace_bytes(p, o, aux, summary, nframes, nsignals, bytes);
-  if (!bytes) return fail(MGX_E_INVALID_ARGUMENT, "bytes is NULL");
-  const mgx_outputs none{};
-  mgx::Outputs x;
-  DeltaReq q;
-  int rc = check_summary(summary);
-  if (rc || (rc = delta_request(p, deltas, &q)) || (rc = make_outputs(p, o ? o : &none, aux, &x))) return rc;
-  SummaryFields sf;
-  summary_fields(p, summary, &sf);
-  const uint32_t extra = (sf.pooled | q.rows[0]) & ~mgx::out_requested(x);
-  const SummaryLayout l = summary_layout(p->d, extra, sf.a.cols, nframes, nsignals, false, q.any());
-  *bytes = delta_layout(p->d, q, nframes, nsignals, false, l.total).total;
-  return MGX_OK;
+  return summarize_more_workspace_bytes(p, o, aux, summary, deltas, nullptr, 0, nframes, nsignals, bytes);
 }
 
 int mgx_summarize_deltas_device(mgx_plan* p, const float* samples, uint64_t num_samples, const uint64_t* starts, uint64_t nframes,
@@ -1942,75 +2151,58 @@ int mgx_summarize_deltas_device(mgx_plan* p, const float* samples, uint64_t num_
   if (!deltas)
     return mgx_summarize_device(p, samples, num_samples, starts, nframes, frame_offsets, nsignals, o, aux, summary, workspace,
                                 workspace_bytes, stream);
-  const mgx_outputs none{};
-  mgx::Outputs x;
-  DeltaReq q;
-  int rc = check_summary(summary);
-  if (rc || (rc = delta_request(p, deltas, &q)) || (rc = make_outputs(p, o ? o : &none, aux, &x))) return rc;
-  SummaryFields sf;
-  summary_fields(p, summary, &sf);
-  if (!q.any())  // (no field named in either: the summary call)
-    return mgx_summarize_device(p, samples, num_samples, starts, nframes, frame_offsets, nsignals, o, aux, summary, workspace,
-                                workspace_bytes, stream);
-  if ((rc = summary_inputs(p, samples, num_samples, starts, nframes, frame_offsets, nsignals))) return rc;
-  if ((rc = check_outputs(x))) return rc;
-  const uint32_t extra = (sf.pooled | q.rows[0]) & ~mgx::out_requested(x);
-  const SummaryLayout l = summary_layout(p->d, extra, sf.a.cols, nframes, nsignals, false, true);
-  const DeltaLayout dl = delta_layout(p->d, q, nframes, nsignals, false, l.total);
-  if (workspace_bytes < dl.total || (dl.total > 0 && !workspace))
-    return fail(MGX_E_INVALID_ARGUMENT, "the workspace holds %llu bytes, the call needs %llu (mgx_summarize_deltas_workspace_bytes)",
-                (unsigned long long)workspace_bytes, (unsigned long long)dl.total);
-  if (dl.total > 0 && reinterpret_cast<uintptr_t>(workspace) % 256 != 0)
-    return fail(MGX_E_INVALID_ARGUMENT, "the workspace is not 256-byte aligned");
-  unsigned char* const ws = static_cast<unsigned char*>(workspace);
-  // the launch's outputs: the caller's per-frame arrays, and for the other pooled or delta'd fields the workspace's
-  mgx::Outputs u = x;
-  if (l.total > 0)
-    for (int i = 0; i < mgx::kOutFields; ++i)
-      if (l.frames[i] != UINT64_MAX) mgx::out_field(u, i) = ws + l.frames[i];
-  if (nframes > 0) {
-    const GatherLaunch g{starts, num_samples};
-    LaunchOpts opt;
-    opt.gather = &g;
-    if ((rc = extract_device_impl(p, samples, nframes, (uint64_t)p->n, l.total > 0 ? &u : &x, stream, opt))) return rc;
-  }
-  if (nsignals == 0) return MGX_OK;
-  hipError_t e = hipSetDevice(p->d.device);
-  if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
-  mgx::SummaryArgs& a = sf.a;
-  a.num_signals = nsignals;
-  a.num_frames = nframes;
-  uint64_t* const table = nframes > 0 ? reinterpret_cast<uint64_t*>(ws + l.table) : nullptr;
-  if (nframes > 0) {
-    // the base summaries, exactly as mgx_summarize_device forms them; the table serves the deltas too
-    for (uint32_t i = 0; i < a.nfields; ++i) a.f[i].src = mgx::out_field(u, sf.index[i]);
-    a.table = table;
-    a.shift = reinterpret_cast<double*>(ws + l.shift);
-    a.part = reinterpret_cast<double*>(ws + l.part);
-    a.row0 = 0;
-    a.rows = nframes;
-    a.slot0 = 0;
-    a.nslots = nframes / mgx::kSummaryBlock + nsignals;
-    e = mgx::launch_summary_table(frame_offsets, table, nsignals, nframes, (hipStream_t)stream);
-    if (e == hipSuccess) e = mgx::launch_summary_partial(a, (hipStream_t)stream);
-    if (e != hipSuccess) return hip_fail(e, "summary kernel launch");
-  }
-  e = mgx::launch_summary_final(a, (hipStream_t)stream);
-  if (e != hipSuccess) return hip_fail(e, "summary kernel launch");
-  if (nframes > 0) return delta_pool(p->d, q, u, ws, dl, table, nframes, nsignals, (hipStream_t)stream);
-  // no buffers: every signal is empty, NaN in all four (the final kernel reads neither rows nor table)
-  for (int k = 0; k < 2 && e == hipSuccess; ++k) {
-    q.sf[k].a.num_signals = nsignals;
-    q.sf[k].a.num_frames = 0;
-    e = mgx::launch_summary_final(q.sf[k].a, (hipStream_t)stream);
-  }
-  return e == hipSuccess ? MGX_OK : hip_fail(e, "summary kernel launch");
+  return summarize_more_device(p, samples, num_samples, starts, nframes, frame_offsets, nsignals, o, aux, summary, deltas, nullptr, 0,
+                               workspace, workspace_bytes, stream);
 }
 
 int mgx_summarize_deltas_host(mgx_plan* p, const float* samples, uint64_t num_samples, const uint64_t* starts, uint64_t nframes,
                               const uint64_t* frame_offsets, uint64_t nsignals, const mgx_outputs* outputs,
                               const mgx_aux_outputs* aux, const mgx_summary_outputs* summary, const mgx_delta_summaries* deltas) {
   return summarize_host_impl(p, samples, num_samples, starts, nframes, frame_offsets, nsignals, outputs, aux, summary, deltas);
+}
+
+int mgx_flux_device(const void* rows, uint64_t num_frames, uint32_t cols, uint32_t rows_f64, const uint64_t* frame_offsets,
+                    uint64_t num_signals, uint32_t mode, uint32_t lag, void* flux, void* stream) {
+  if (cols == 0) return fail(MGX_E_INVALID_ARGUMENT, "cols is 0");
+  if (mode >= MGX_NUM_FLUX_MODES) return fail(MGX_E_INVALID_ARGUMENT, "mode is %u, expected 0..%d", mode, MGX_NUM_FLUX_MODES - 1);
+  if (lag < 1 || lag > MGX_FLUX_MAX_LAG) return fail(MGX_E_INVALID_ARGUMENT, "lag is %u, expected 1..%d", lag, MGX_FLUX_MAX_LAG);
+  if (rows_f64 > 1) return fail(MGX_E_INVALID_ARGUMENT, "rows_f64 is %u, expected 0 or 1", rows_f64);
+  if (!flux) return fail(MGX_E_INVALID_ARGUMENT, "flux is NULL");
+  if (flux == rows) return fail(MGX_E_INVALID_ARGUMENT, "flux is the rows' own array");
+  if (num_signals > 0 && !frame_offsets) return fail(MGX_E_INVALID_ARGUMENT, "frame_offsets is NULL");
+  if (num_frames == 0) return MGX_OK;
+  if (!rows) return fail(MGX_E_INVALID_ARGUMENT, "rows is NULL");
+  // (frame_offsets with num_signals = 0: a table of one entry, no signal, nothing written)
+  const hipError_t e = mgx::launch_flux(rows, nullptr, flux, 0, num_frames, num_frames, cols, rows_f64 != 0, frame_offsets, num_signals,
+                                        mode, lag, (hipStream_t)stream);
+  return e == hipSuccess ? MGX_OK : hip_fail(e, "flux kernel launch");
+}
+
+int mgx_summarize_flux_workspace_bytes(const mgx_plan* p, const mgx_outputs* o, const mgx_aux_outputs* aux,
+                                       const mgx_summary_outputs* summary, const mgx_delta_summaries* deltas,
+                                       const mgx_flux_request* flux, uint32_t nflux, uint64_t nframes, uint64_t nsignals,
+                                       uint64_t* bytes) {
+  if (nflux == 0) return mgx_summarize_deltas_workspace_bytes(p, o, aux, summary, deltas, nframes, nsignals, bytes);
+  return summarize_more_workspace_bytes(p, o, aux, summary, deltas, flux, nflux, nframes, nsignals, bytes);
+}
+
+int mgx_summarize_flux_device(mgx_plan* p, const float* samples, uint64_t num_samples, const uint64_t* starts, uint64_t nframes,
+                              const uint64_t* frame_offsets, uint64_t nsignals, const mgx_outputs* o, const mgx_aux_outputs* aux,
+                              const mgx_summary_outputs* summary, const mgx_delta_summaries* deltas, const mgx_flux_request* flux,
+                              uint32_t nflux, void* workspace, uint64_t workspace_bytes, void* stream) {
+  if (nflux == 0)
+    return mgx_summarize_deltas_device(p, samples, num_samples, starts, nframes, frame_offsets, nsignals, o, aux, summary, deltas,
+                                       workspace, workspace_bytes, stream);
+  return summarize_more_device(p, samples, num_samples, starts, nframes, frame_offsets, nsignals, o, aux, summary, deltas, flux, nflux,
+                               workspace, workspace_bytes, stream);
+}
+
+int mgx_summarize_flux_host(mgx_plan* p, const float* samples, uint64_t num_samples, const uint64_t* starts, uint64_t nframes,
+                            const uint64_t* frame_offsets, uint64_t nsignals, const mgx_outputs* outputs, const mgx_aux_outputs* aux,
+                            const mgx_summary_outputs* summary, const mgx_delta_summaries* deltas, const mgx_flux_request* flux,
+                            uint32_t nflux) {
+  return summarize_host_impl(p, samples, num_samples, starts, nframes, frame_offsets, nsignals, outputs, aux, summary, deltas, flux,
+                             nflux);
 }
 
 int mgx_summary_workspace_bytes(const mgx_plan* p, const mgx_outputs* o, const mgx_aux_outputs* aux, const mgx_summary_outputs* summary,
@@ -2090,15 +2282,20 @@ int mgx_summarize_host(mgx_plan* p, const float* samples, uint64_t num_samples, 
 
 namespace {
 
-// mgx_summarize_host (deltas null: nothing here differs from what it was) and mgx_summarize_deltas_host
+// mgx_summarize_host (deltas null: nothing here differs from what it was), mgx_summarize_deltas_host and
+// mgx_summarize_flux_host (no request: nothing here differs from the deltas call)
 int summarize_host_impl(mgx_plan* p, const float* samples, uint64_t num_samples, const uint64_t* starts, uint64_t nframes,
                         const uint64_t* frame_offsets, uint64_t nsignals, const mgx_outputs* outputs, const mgx_aux_outputs* aux,
-                        const mgx_summary_outputs* summary, const mgx_delta_summaries* deltas) {
+                        const mgx_summary_outputs* summary, const mgx_delta_summaries* deltas, const mgx_flux_request* flux,
+                        uint32_t nflux) {
   const mgx_outputs none{};
   mgx::Outputs x;
   DeltaReq q;
+  FluxReq fq;
   int rc = check_summary(summary);
-  if (rc || (rc = delta_request(p, deltas, &q)) || (rc = make_outputs(p, outputs ? outputs : &none, aux, &x))) return rc;
+  if (rc || (rc = delta_request(p, deltas, &q)) || (rc = flux_request(p, flux, nflux, nsignals, &fq)) ||
+      (rc = make_outputs(p, outputs ? outputs : &none, aux, &x)))
+    return rc;
   SummaryFields sf;
   summary_fields(p, summary, &sf);
   if ((rc = summary_inputs(p, samples, num_samples, starts, nframes, frame_offsets, nsignals))) return rc;
@@ -2125,9 +2322,10 @@ int summarize_host_impl(mgx_plan* p, const float* samples, uint64_t num_samples,
     for (int k = 0; k < 2; ++k)
       for (uint32_t i = 0; i < q.sf[k].a.nfields; ++i)
         std::fill_n(q.sf[k].a.f[i].dst, nsignals * MGX_NUM_STATS * q.sf[k].a.f[i].width, std::nan(""));
+    for (uint32_t i = 0; i < fq.sf.a.nfields; ++i) std::fill_n(fq.sf.a.f[i].dst, nsignals * MGX_NUM_STATS, std::nan(""));
     return MGX_OK;
   }
-  if (nsignals == 0 || (a.cols == 0 && !q.any())) return gather_host_chunked(p, samples, starts, nframes, &x, nullptr);
+  if (nsignals == 0 || (a.cols == 0 && !q.any() && !fq.any())) return gather_host_chunked(p, samples, starts, nframes, &x, nullptr);
   const SummaryLayout l = summary_layout(p->d, 0, a.cols, nframes, nsignals, true);
   hipError_t e = hipSetDevice(p->d.device);
   if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
@@ -2153,6 +2351,21 @@ int summarize_host_impl(mgx_plan* p, const float* samples, uint64_t num_samples,
     if (e != hipSuccess) { p->s_delta = nullptr; return hip_fail(e, "hipMalloc(delta rows)"); }
     p->s_delta_bytes = dl.total;
   }
+  // the flux's own buffer: no rows but the carries, and the flux columns of the whole call
+  const FluxLayout fl = flux_layout(fq, nframes, nsignals, true, 0);
+  if (fq.any() && p->s_flux_bytes < fl.total) {
+    if (p->s_flux) (void)hipFree(p->s_flux);
+    p->s_flux = nullptr;
+    p->s_flux_bytes = 0;
+    e = hipMalloc(reinterpret_cast<void**>(&p->s_flux), fl.total);
+    if (e != hipSuccess) { p->s_flux = nullptr; return hip_fail(e, "hipMalloc(flux columns)"); }
+    p->s_flux_bytes = fl.total;
+  }
+  if (fq.any()) {
+    e = hipMemcpyAsync(p->s_flux + fl.table, frame_offsets, (nsignals + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, p->s_comp);
+    if (e != hipSuccess) return hip_fail(e, "hipMemcpyAsync(frame_offsets)");
+  }
+  int carry_now = 0;  // which of a request's two carries holds the rows before the next chunk
   a.num_signals = nsignals;
   a.num_frames = nframes;
   if (a.cols > 0) {
@@ -2167,7 +2380,7 @@ int summarize_host_impl(mgx_plan* p, const float* samples, uint64_t num_samples,
     if (e != hipSuccess) return hip_fail(e, "hipMemcpyAsync(frame_offsets)");
   }
   ChunkHook hook;
-  hook.pooled = sf.pooled | q.rows[0];
+  hook.pooled = sf.pooled | q.rows[0] | fq.rows;
   auto reduce_chunk = [&](uint64_t f0, uint64_t cnt, const mgx::Outputs& d) {
     // the chunk's rows [f0, f0 + cnt) and the slots they can belong to: from the block that holds the first of
     // them that a signal owns to the block that holds the last (the kernel passes over a slot without rows here)
@@ -2200,7 +2413,24 @@ int summarize_host_impl(mgx_plan* p, const float* samples, uint64_t num_samples,
       const uint64_t fb = mgx::out_field_bytes(p->d, i);
       ce = hipMemcpyAsync(p->s_delta + xoff[i] + f0 * fb, mgx::out_field(d, i), cnt * fb, hipMemcpyDeviceToDevice, p->s_comp);
     }
-    return ce == hipSuccess ? (int)MGX_OK : hip_fail(ce, "hipMemcpyAsync(delta rows)");
+    if (ce != hipSuccess) return hip_fail(ce, "hipMemcpyAsync(delta rows)");
+    // the chunk's flux over the slot's rows and the carry, into the call's columns; then the chunk's last lag rows
+    // (behind what is left of the carry, when the chunk has fewer) into the other carry, before the slot is reused
+    for (uint32_t i = 0; i < fq.n && ce == hipSuccess; ++i) {
+      const uint64_t lag = fq.r[i].lag, rb = (uint64_t)fq.cols[i] * sizeof(float);
+      const unsigned char* const rows = static_cast<const unsigned char*>(mgx::out_field(d, (int)fq.r[i].field));
+      unsigned char* const now = p->s_flux + fl.carry[i][carry_now];
+      unsigned char* const next = p->s_flux + fl.carry[i][carry_now ^ 1];
+      ce = mgx::launch_flux(rows, f0 > 0 ? now : nullptr, reinterpret_cast<float*>(p->s_flux + fl.col[i]) + f0, f0, cnt, nframes,
+                            fq.cols[i], false, reinterpret_cast<const uint64_t*>(p->s_flux + fl.table), nsignals, fq.r[i].mode,
+                            fq.r[i].lag, p->s_comp);
+      const uint64_t keep = cnt < lag ? lag - cnt : 0, take = lag - keep;
+      if (ce == hipSuccess && keep > 0) ce = hipMemcpyAsync(next, now + (lag - keep) * rb, keep * rb, hipMemcpyDeviceToDevice, p->s_comp);
+      if (ce == hipSuccess)
+        ce = hipMemcpyAsync(next + keep * rb, rows + (cnt - take) * rb, take * rb, hipMemcpyDeviceToDevice, p->s_comp);
+    }
+    carry_now ^= 1;
+    return ce == hipSuccess ? (int)MGX_OK : hip_fail(ce, "flux kernel launch and carry copies");
   };
   if ((rc = gather_host_chunked(p, samples, starts, nframes, &x, &hook))) return rc;
   // the signals' partials into the summaries, and those alone back to the caller
@@ -2233,6 +2463,26 @@ int summarize_host_impl(mgx_plan* p, const float* samples, uint64_t num_samples,
         e = hipMemcpyAsync(delta_dst[k][i], da.f[i].dst, nsignals * MGX_NUM_STATS * da.f[i].width * sizeof(double),
                            hipMemcpyDeviceToHost, p->s_comp);
     }
+  }
+  if (fq.any() && rc == MGX_OK && e == hipSuccess) {
+    // the pooling over the whole call's flux columns, as the device call runs it
+    mgx::SummaryArgs& fa = fq.sf.a;
+    double* const fres = reinterpret_cast<double*>(p->s_flux + fl.result);
+    double* flux_dst[MGX_FLUX_MAX_REQUESTS];
+    float* col[MGX_FLUX_MAX_REQUESTS];
+    for (uint32_t i = 0; i < fq.n; ++i) col[i] = reinterpret_cast<float*>(p->s_flux + fl.col[i]);
+    for (uint32_t k = 0; k < fa.nfields; ++k) {
+      flux_dst[k] = fa.f[k].dst;
+      fa.f[k].dst = fres + nsignals * MGX_NUM_STATS * k;
+    }
+    rc = flux_pool(fq, col, p->s_flux, fl, reinterpret_cast<const uint64_t*>(p->s_flux + fl.table), nframes, nsignals, p->s_comp);
+    for (uint32_t k = 0; k < fa.nfields && rc == MGX_OK && e == hipSuccess; ++k)
+      e = hipMemcpyAsync(flux_dst[k], fa.f[k].dst, nsignals * MGX_NUM_STATS * sizeof(double), hipMemcpyDeviceToHost, p->s_comp);
+    for (uint32_t i = 0; i < fq.n && rc == MGX_OK && e == hipSuccess; ++i)
+      // (the rows of the signals, [frame_offsets[0], frame_offsets[S]): the others are not written, as in the device call)
+      if (fq.r[i].per_frame && frame_offsets[nsignals] > frame_offsets[0])
+        e = hipMemcpyAsync(fq.r[i].per_frame + frame_offsets[0], col[i] + frame_offsets[0],
+                           (frame_offsets[nsignals] - frame_offsets[0]) * sizeof(float), hipMemcpyDeviceToHost, p->s_comp);
   }
   const hipError_t es = hipStreamSynchronize(p->s_comp);
   if (rc) return rc;

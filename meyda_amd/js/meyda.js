@@ -28,7 +28,7 @@
 //                                   signals: an array of Float32Arrays (a corpus); every signal's buffers
 //                                   in one launch, none across two signals; getBatch's result plus
 //                                   frameOffsets (signal s: rows frameOffsets[s] .. frameOffsets[s + 1])
-//   getSignalSummaries(features, signals, hopSize[, {deltaWidth, deltaOrder}]) / getSignalSummariesAsync(...)
+//   getSignalSummaries(features, signals, hopSize[, {deltaWidth, deltaOrder, flux}]) / getSignalSummariesAsync(...)
 //                                   getBatchSignals' signals pooled per signal on the device: per feature
 //                                   {mean, variance, min, max}, Float64Arrays of signals x width, plus frameOffsets
 //   Meyda.signalsFrameStarts(lengths, bufferSize, hopSize)
@@ -453,10 +453,16 @@ class Meyda {
   // deltaWidth (1..8) within each signal, and at order 2 of the deltas' deltas (MFCC + delta + delta-delta pooled
   // per clip): the result gains `delta` (and `delta2`), objects of the result's own shape. The deltas of a
   // spectrum are not pooled (the library's error). Without the option the result is as it was.
+  // options {flux: [{feature, mode: 'rectified' | 'l1' | 'l2', lag: 1..8, perFrame}]} (up to 4): the spectral flux
+  // of 'loudness' (its specific rows), 'mfcc', 'amplitudeSpectrum', 'powerSpectrum' or 'melBands' -- the distance
+  // of every buffer's row from the row `lag` buffers before it in the same signal (include/meyda_gpu.h) -- pooled
+  // per signal: the result gains `flux`, one object per request with mean, variance, min, max (Float64Arrays of
+  // signals.length) and, with perFrame, the onset envelope `perFrame` (a Float32Array, a value per buffer). An
+  // options object with flux and no delta key asks for no deltas.
   getSignalSummaries(features, signals, hopSize, options) {
     const names = this._checkNames(checkSummaryNames(features));
     const c = this._concatSignals(signals, hopSize);
-    const d = deltaOptions(options);
+    const d = summaryOptions(options);
     const raw = d ? addon.summarizeGather(this._plan(), c.samples, c.starts, c.frameOffsets, names, d)
       : addon.summarizeGather(this._plan(), c.samples, c.starts, c.frameOffsets, names);
     return summaryResult(names, raw, c.frameOffsets);
@@ -465,7 +471,7 @@ class Meyda {
   getSignalSummariesAsync(features, signals, hopSize, options) {
     const names = this._checkNames(checkSummaryNames(features));
     const c = this._concatSignals(signals, hopSize);
-    const d = deltaOptions(options);
+    const d = summaryOptions(options);
     return this._runAsync((plan) => (d ? addon.summarizeGatherAsync(plan, c.samples, c.starts, c.frameOffsets, names, d)
       : addon.summarizeGatherAsync(plan, c.samples, c.starts, c.frameOffsets, names)))
       .then((r) => summaryResult(names, r, c.frameOffsets));
@@ -699,7 +705,43 @@ function summaryResult(names, raw, frameOffsets) {
   }
   // (the delta summaries the addon hangs on its result: the same fields, the same shape)
   for (const k of ['delta', 'delta2']) if (raw[k]) r[k] = summaryResult(names, raw[k], frameOffsets);
+  // (the flux: per request the four statistics of the signals, and the per-frame column where it was asked for)
+  if (raw.flux) {
+    r.flux = raw.flux.map((f) => {
+      const o = {};
+      STATS.forEach((k, j) => {
+        o[k] = new Float64Array(S);
+        for (let s = 0; s < S; ++s) o[k][s] = f.summary[s * STATS.length + j];
+      });
+      if (f.perFrame) o.perFrame = f.perFrame;
+      return o;
+    });
+  }
   return r;
+}
+
+// The fields a flux is taken of and its modes, as mgx_flux_request numbers them
+const FLUX_FIELDS = { loudness: 13, mfcc: 14, amplitudeSpectrum: 15, powerSpectrum: 16, melBands: 19 };
+const FLUX_MODES = { rectified: 0, l1: 1, l2: 2 };
+
+// getSignalSummaries' options as the addon takes them (the delta options, and flux in the library's numbers), or
+// null when neither deltas nor flux are asked for
+function summaryOptions(options) {
+  const d = deltaOptions(options);
+  if (options === undefined || options === null || options.flux === undefined) return d;
+  if (!Array.isArray(options.flux) || options.flux.length < 1 || options.flux.length > 4) {
+    throw new RangeError('flux must be an array of 1 to 4 requests');
+  }
+  const flux = options.flux.map((f) => {
+    if (f === null || typeof f !== 'object') throw new TypeError('a flux request must be an object: {feature, mode, lag, perFrame}');
+    if (!Object.prototype.hasOwnProperty.call(FLUX_FIELDS, f.feature)) throw new TypeError("'" + f.feature + "' has no flux");
+    const mode = f.mode === undefined ? 'rectified' : f.mode;
+    if (!Object.prototype.hasOwnProperty.call(FLUX_MODES, mode)) throw new RangeError("flux mode must be 'rectified', 'l1' or 'l2'");
+    const lag = f.lag === undefined ? 1 : f.lag;
+    if (!Number.isInteger(lag) || lag < 1 || lag > 8) throw new RangeError('flux lag must be an integer from 1 to 8');
+    return { field: FLUX_FIELDS[f.feature], mode: FLUX_MODES[mode], lag, perFrame: !!f.perFrame };
+  });
+  return Object.assign({}, d || {}, { flux });
 }
 
 // getSignalSummaries' options as the addon takes them, or null when no deltas are asked for
