@@ -661,6 +661,80 @@ int mgx_summarize_flux_host(mgx_plan* plan, const float* samples, uint64_t num_s
                             const mgx_summary_outputs* summary, const mgx_delta_summaries* deltas,
                             const mgx_flux_request* flux, uint32_t num_flux);
 
+/* ---- Onsets: the peaks of a clip's envelope, picked on the device ------------------------------
+ * Replaces, in a host application, the loop that runs over the flux column after it was copied back: a moving
+ * maximum, a moving mean, a threshold and a greedy minimum distance (librosa.util.peak_pick, with the edges
+ * handled as this library handles them). With it, envelope -> onsets -> onset-aligned starts -> a second gather
+ * launch runs without a host round trip. The reference has no counterpart. Like the statistics, the deltas and
+ * the flux it is no feature: MGX_NUM_FEATURES, the name table and every struct above are as they were.
+ *
+ * A signal owns rows [a, b) of a one-column envelope x of num_frames values, float32 or float64; values are
+ * taken as float64. Rows outside the signal repeat its first or last row, as for the deltas:
+ * x~(u) = x(min(max(u, a), b - 1)). The parameters are pre_max, post_max, pre_avg, post_avg (each 0 ..
+ * MGX_PEAK_MAX_REACH), delta (a double, not NaN) and wait (any uint32). Row t of [a, b) is a candidate if
+ *
+ *   1. no u in [t - pre_max, t + post_max] has x~(u) > x(t) -- an IEEE comparison: a NaN neighbour does not
+ *      block --, and
+ *   2. x(t) >= m + delta, where m starts at +0, m += x~(u) for u = t - pre_avg .. t + post_avg ascending, each
+ *      addition rounded to float64; m is then divided by (pre_avg + post_avg + 1) and rounded once, delta is
+ *      added and the sum rounded once. A NaN on either side makes the comparison false: a NaN row is never a
+ *      candidate, and a NaN inside the averaging window rejects the row.
+ *
+ * The peaks of the signal are chosen from its candidates in ascending order: the first candidate is a peak; a
+ * later candidate t is a peak iff t - (the last peak) > wait. A peak is a function of its own signal's rows
+ * alone; rows of no signal are never peaks and are never written; an empty signal has no peaks. No atomics:
+ * every call below, a repeated call and any grid give the same values (integers all, so the same bits). */
+#define MGX_PEAK_MAX_REACH 64
+typedef struct mgx_peak_params {
+  uint32_t struct_size;  /* = sizeof(mgx_peak_params), 32; anything else: MGX_E_INVALID_ARGUMENT */
+  uint32_t pre_max, post_max, pre_avg, post_avg, wait;
+  double delta;
+} mgx_peak_params;
+typedef struct mgx_peak_outputs {
+  uint32_t struct_size;    /* = sizeof(mgx_peak_outputs), 56 */
+  uint32_t reserved;
+  uint8_t* mask;           /* num_frames, 1 = peak, 0 = row of a signal that is no peak; or NULL */
+  uint64_t* peak_offsets;  /* S + 1 entries: signal s's peaks are peaks[peak_offsets[s] .. peak_offsets[s+1]); or NULL */
+  uint64_t* peaks;         /* row indices of the whole array, ascending; `capacity` entries; or NULL */
+  uint64_t capacity;
+  const uint64_t* starts;  /* optional: the gather table the rows came from ...                       */
+  uint64_t* peak_starts;   /* ... and starts[peaks[i]] for every peak written: the next launch's table */
+} mgx_peak_outputs;
+
+/* The bytes mgx_peaks_device works in: a multiple of 256, non-decreasing in both arguments (bitmaps of one bit
+ * per row and the scan's block sums: about half a byte per row). Host only. */
+int mgx_peaks_workspace_bytes(uint64_t num_frames, uint64_t num_signals, uint64_t* bytes);
+
+/* The picker on device arrays; no plan: asynchronous on `stream`, no allocation, no host-side state, capturable.
+ * Every pointer is a device pointer. envelope_f64: 0 float32, 1 float64. S is num_signals, or 1 when
+ * frame_offsets is NULL and num_signals is 0: one signal [0, num_frames). The table is read as mgx_delta_device
+ * reads it, every entry limited to num_frames: a non-decreasing one gives the definition above, any other gives
+ * unspecified values, and no access is made outside the arrays -- no write to peaks or peak_starts at or beyond
+ * `capacity` either. peak_offsets always holds the true counts; of peaks (and peak_starts) the first
+ * min(total, capacity) entries are written, so a caller can size the list and call again. num_frames = 0 writes
+ * peak_offsets (all 0) and nothing else.
+ * MGX_E_INVALID_ARGUMENT before any launch: a bad struct_size in either struct, a reach above
+ * MGX_PEAK_MAX_REACH, a NaN delta, envelope_f64 > 1, mask, peak_offsets and peaks all NULL, peaks set with
+ * capacity 0, peak_starts without starts or without peaks, num_signals > 0 with NULL frame_offsets, NULL envelope
+ * with num_frames > 0, a workspace smaller than mgx_peaks_workspace_bytes or not 256-byte aligned. */
+int mgx_peaks_device(const void* envelope, uint64_t num_frames, uint32_t envelope_f64,
+                     const uint64_t* frame_offsets, uint64_t num_signals, const mgx_peak_params* params,
+                     const mgx_peak_outputs* out, void* workspace, uint64_t workspace_bytes, void* stream);
+
+/* Host pointers throughout: mgx_summarize_flux_host with exactly the one request `flux` (no other output, summary
+ * or delta), followed by the picker. flux->per_frame and flux->summary are honoured when set and written bit for
+ * bit as that call writes them; unlike there, both may be NULL. The picker runs once, after the last chunk, over
+ * the plan-owned flux column the flux host path keeps on the device for the length of the call: the envelope is
+ * not uploaded again, and only peak_offsets, peaks and what the request names cross back. The result equals
+ * mgx_peaks_device on the column mgx_summarize_flux_host returns, wherever the chunks end.
+ * peak_offsets: num_signals + 1 entries, non-NULL (the true counts); peaks: `capacity` entries, the first
+ * min(total, capacity) written, or NULL with capacity 0 for the counts alone. num_signals = 0 is
+ * MGX_E_INVALID_ARGUMENT: onsets need signals. Every other refusal is that of the two calls it is made of. */
+int mgx_onsets_host(mgx_plan* plan, const float* samples, uint64_t num_samples, const uint64_t* starts,
+                    uint64_t num_frames, const uint64_t* frame_offsets, uint64_t num_signals,
+                    const mgx_flux_request* flux, const mgx_peak_params* params,
+                    uint64_t* peak_offsets, uint64_t* peaks, uint64_t capacity);
+
 /* ---- Multi-device groups -------------------------------
  * Replaces nothing in the reference (single-threaded browser code); it exists because
  * buffers are independent (src/meyda.js:69-91 keeps no cross-buffer state), so a batch

@@ -20,6 +20,11 @@
  *     {summary: Float64Array(nsignals x 4), perFrame: Float32Array(nframes)} per request
  *                                        -> { name: Float64Array(S x 4 x width) }: mean, variance, min, max
  *                                           of each field over every signal's buffers (mgx_summarize_host)
+ *   onsetsGather(plan, samples, starts, frameOffsets, {field, mode, lag, preMax, postMax, preAvg, postAvg, delta, wait,
+ *     envelope}) / onsetsGatherAsync(...)
+ *                                        -> { onsetOffsets: Float64Array(S + 1), onsets: Float64Array(total)[, envelope:
+ *                                           Float32Array(nframes)] }: the peaks of the field's flux within every
+ *                                           signal, picked on the device (mgx_onsets_host)
  *   wavParse(wavBytes)                   -> { pcmFormat, channels, sampleRate, bitsPerSample, ... }
  *   hostTables(opts)                     -> { hanning, hamming, window, barkScale, barkLimits, melBins, dct }
  *   isPowerOfTwo(n), deviceCount(), featureNames(), featureInfo(name), abiVersion()
@@ -290,6 +295,12 @@ typedef struct {
   mgx_flux_request flux[MGX_FLUX_MAX_REQUESTS];
   int flux_per_frame[MGX_FLUX_MAX_REQUESTS];
   napi_ref frefs[2][MGX_FLUX_MAX_REQUESTS];  /* [0] the summaries, [1] the per-frame columns */
+  /* onsetsGather: a gather job whose outputs are the peaks of flux[0]'s column within every signal (mgx_onsets_host);
+   * peak_offsets: nsignals + 1 entries, peaks: nframes entries, which always hold them (both malloc'd) */
+  int onsets;
+  mgx_peak_params peak;
+  uint64_t* peak_offsets;
+  uint64_t* peaks;
   mgx_outputs out;
   mgx_aux_outputs aux;  /* melBands (SLOT_MEL): the job then makes the mgx_extract_*_ex call */
   /* The outputs are written straight into JS ArrayBuffers (napi_create_arraybuffer), held by
@@ -313,6 +324,10 @@ static void job_free_buffers(napi_env env, job* j) {
   j->starts = NULL;
   free(j->frame_offsets);
   j->frame_offsets = NULL;
+  free(j->peak_offsets);
+  j->peak_offsets = NULL;
+  free(j->peaks);
+  j->peaks = NULL;
   for (int i = 0; i < NSLOTS; ++i)
     if (j->refs[i]) {
       napi_delete_reference(env, j->refs[i]);
@@ -643,6 +658,96 @@ static int job_prepare_summary(napi_env env, job* j, napi_value samples_v, napi_
   return job_prepare_gather(env, j, samples_v, starts_v, feats) && job_alloc_flux(env, j);
 }
 
+/* onsetsGather(plan, samples, starts, frameOffsets, options): summarizeGather's inputs; options: {field, mode = 0,
+ * lag = 1, preMax = 0, postMax = 0, preAvg = 0, postAvg = 0, delta = 0, wait = 0, envelope = false}. */
+static int job_prepare_onsets(napi_env env, job* j, napi_value samples_v, napi_value starts_v, napi_value offsets_v,
+                              napi_value options_v) {
+  napi_valuetype ot = napi_undefined;
+  napi_typeof(env, options_v, &ot);
+  if (ot != napi_object) {
+    napi_throw_type_error(env, NULL, "options must be an object: {field, mode, lag, preMax, postMax, preAvg, postAvg, delta, wait, envelope}");
+    return 0;
+  }
+  j->onsets = 1;
+  mgx_flux_request* r = &j->flux[0];
+  r->struct_size = sizeof *r;
+  if (!option_u32(env, options_v, "field", 0, MGX_NUM_FEATURES - 1, MGX_NUM_FEATURES, &r->field)) return 0;
+  if (r->field == MGX_NUM_FEATURES) {
+    napi_throw_type_error(env, NULL, "the onsets' flux names its field");
+    return 0;
+  }
+  if (!option_u32(env, options_v, "mode", 0, MGX_NUM_FLUX_MODES - 1, MGX_FLUX_RECTIFIED, &r->mode)) return 0;
+  if (!option_u32(env, options_v, "lag", 1, MGX_FLUX_MAX_LAG, 1, &r->lag)) return 0;
+  mgx_peak_params* pp = &j->peak;
+  pp->struct_size = sizeof *pp;
+  if (!option_u32(env, options_v, "preMax", 0, MGX_PEAK_MAX_REACH, 0, &pp->pre_max)) return 0;
+  if (!option_u32(env, options_v, "postMax", 0, MGX_PEAK_MAX_REACH, 0, &pp->post_max)) return 0;
+  if (!option_u32(env, options_v, "preAvg", 0, MGX_PEAK_MAX_REACH, 0, &pp->pre_avg)) return 0;
+  if (!option_u32(env, options_v, "postAvg", 0, MGX_PEAK_MAX_REACH, 0, &pp->post_avg)) return 0;
+  if (!option_u32(env, options_v, "wait", 0, 4294967295u, 0, &pp->wait)) return 0;
+  napi_value v;
+  if (option_given(env, options_v, "delta", &v)) {
+    napi_valuetype t = napi_undefined;
+    napi_typeof(env, v, &t);
+    if (t != napi_number) {
+      napi_throw_type_error(env, NULL, "delta must be a number");
+      return 0;
+    }
+    napi_get_value_double(env, v, &pp->delta);
+    if (pp->delta != pp->delta) {
+      napi_throw_range_error(env, NULL, "delta must not be NaN");
+      return 0;
+    }
+  }
+  bool b = false;
+  if (option_given(env, options_v, "envelope", &v)) napi_coerce_to_bool(env, v, &v), napi_get_value_bool(env, v, &b);
+  j->flux_per_frame[0] = b ? 1 : 0;
+  size_t count = 0, len = 0, off = 0;
+  j->frame_offsets = u64_of_f64(env, offsets_v, "frameOffsets", &count);
+  if (!j->frame_offsets) return 0;
+  if (count < 2) {
+    napi_throw_range_error(env, NULL, "frameOffsets holds one entry more than there are signals, and onsets need a signal");
+    return 0;
+  }
+  j->nsignals = count - 1;
+  bool is_ta = false;
+  napi_typedarray_type tt = napi_int8_array;
+  void* data = NULL;
+  napi_value ab;
+  napi_is_typedarray(env, samples_v, &is_ta);
+  if (is_ta) napi_get_typedarray_info(env, samples_v, &tt, &len, &data, &ab, &off);
+  if (!is_ta || tt != napi_float32_array) {
+    napi_throw_type_error(env, NULL, "samples must be a Float32Array");
+    return 0;
+  }
+  if (j->box->group) {
+    napi_throw_error(env, NULL, "starts are not supported on a plan created with `devices`: device groups take dense buffers only");
+    return 0;
+  }
+  j->starts = u64_of_f64(env, starts_v, "starts", &count);
+  if (!j->starts) return 0;
+  j->gather = 1;
+  j->frames = (const float*)data;
+  j->nsamples = len;
+  j->nframes = count;
+  j->peak_offsets = (uint64_t*)calloc(j->nsignals + 1, sizeof(uint64_t));
+  j->peaks = (uint64_t*)calloc(j->nframes ? j->nframes : 1, sizeof(uint64_t));
+  if (!j->peak_offsets || !j->peaks) {
+    napi_throw_error(env, NULL, "out of host memory");
+    return 0;
+  }
+  if (j->flux_per_frame[0]) {
+    if (napi_create_arraybuffer(env, (size_t)j->nframes * sizeof(float), &data, &ab) != napi_ok ||
+        napi_create_reference(env, ab, 1, &j->frefs[1][0]) != napi_ok) {
+      napi_throw_error(env, NULL, "out of host memory");
+      return 0;
+    }
+    memset(data, 0, (size_t)j->nframes * sizeof(float));
+    r->per_frame = (float*)data;
+  }
+  return 1;
+}
+
 /* Field i of a summary (the complex spectrum has none) */
 static void set_summary_field(mgx_summary_outputs* s, int i, double* p) {
   double** const arrays[NSLOTS - SLOT_LOUD] = {&s->loudness_specific, &s->mfcc, &s->amplitude_spectrum, &s->power_spectrum,
@@ -763,7 +868,10 @@ static void job_run(job* j) {
     return;
   }
   const uint32_t n = j->box->desc.buffer_size;
-  if (j->summary && j->num_flux)
+  if (j->onsets)
+    j->rc = mgx_onsets_host(j->box->plan, j->frames, j->nsamples, j->starts, j->nframes, j->frame_offsets, j->nsignals, &j->flux[0],
+                            &j->peak, j->peak_offsets, j->nframes ? j->peaks : NULL, j->nframes);
+  else if (j->summary && j->num_flux)
     j->rc = mgx_summarize_flux_host(j->box->plan, j->frames, j->nsamples, j->starts, j->nframes, j->frame_offsets, j->nsignals,
                                     NULL, NULL, &j->sum, j->delta_order ? &j->deltas : NULL, j->flux, j->num_flux);
   else if (j->summary && j->delta_order)
@@ -814,6 +922,24 @@ static napi_value job_result(napi_env env, job* j) {
       "perceptualSharpness"};
   napi_value obj;
   if (napi_create_object(env, &obj) != napi_ok) return NULL;
+  if (j->onsets) {  /* the index arrays as signalsFrameStarts returns its own: Float64Arrays */
+    const uint64_t total = j->peak_offsets[j->nsignals];
+    const uint64_t* const src[2] = {j->peak_offsets, j->peaks};
+    const uint64_t count[2] = {j->nsignals + 1, total};
+    static const char* const nm[2] = {"onsetOffsets", "onsets"};
+    for (int k = 0; k < 2; ++k) {
+      napi_value abv, ta;
+      void* data = NULL;
+      if (napi_create_arraybuffer(env, (size_t)count[k] * sizeof(double), &data, &abv) != napi_ok ||
+          napi_create_typedarray(env, napi_float64_array, (size_t)count[k], abv, 0, &ta) != napi_ok)
+        return NULL;
+      for (uint64_t i = 0; i < count[k]; ++i) ((double*)data)[i] = (double)src[k][i];
+      napi_set_named_property(env, obj, nm[k], ta);
+    }
+    if (j->frefs[1][0])
+      napi_set_named_property(env, obj, "envelope", typed_of(env, j->frefs[1][0], (size_t)j->nframes * sizeof(float), napi_float32_array, 4));
+    return obj;
+  }
   if (j->summary) {  /* every summary is float64: the same names, each nsignals x 4 x width */
     static const char* arrays[NSLOTS - SLOT_LOUD] = {"loudness.specific", "mfcc", "amplitudeSpectrum", "powerSpectrum", NULL, NULL, "melBands"};
     for (int i = 0; i < NSLOTS; ++i) {
@@ -862,13 +988,14 @@ static napi_value job_result(napi_env env, job* j) {
 }
 
 /* kind: the input of an extraction job */
-enum { IN_FRAMES = 0, IN_WAV = 1, IN_SIGNAL = 2, IN_GATHER = 3, IN_SUMMARY = 4 };
+enum { IN_FRAMES = 0, IN_WAV = 1, IN_SIGNAL = 2, IN_GATHER = 3, IN_SUMMARY = 4, IN_ONSETS = 5 };
 
 static int job_prepare_kind(napi_env env, job* j, int kind, size_t argc, napi_value* argv) {
   if (kind == IN_WAV) return job_prepare_wav(env, j, argv[1], argv[2], argc > 3 ? argv[3] : NULL, argc > 4 ? argv[4] : NULL);
   if (kind == IN_SIGNAL) return job_prepare_signal(env, j, argv[1], argv[2], argv[3]);
   if (kind == IN_GATHER) return job_prepare_gather(env, j, argv[1], argv[2], argv[3]);
   if (kind == IN_SUMMARY) return job_prepare_summary(env, j, argv[1], argv[2], argv[3], argv[4], argc > 5 ? argv[5] : NULL);
+  if (kind == IN_ONSETS) return job_prepare_onsets(env, j, argv[1], argv[2], argv[3], argv[4]);
   return job_prepare(env, j, argv[1], argv[2]);
 }
 
@@ -876,8 +1003,9 @@ static napi_value extract_common(napi_env env, napi_callback_info info, int kind
   size_t argc = 6;
   napi_value argv[6];
   CHECK(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
-  if (argc < (kind == IN_SUMMARY ? 5u : kind == IN_SIGNAL || kind == IN_GATHER ? 4u : 3u)) {
+  if (argc < (kind == IN_SUMMARY || kind == IN_ONSETS ? 5u : kind == IN_SIGNAL || kind == IN_GATHER ? 4u : 3u)) {
     napi_throw_type_error(env, NULL, kind == IN_WAV ? "extractWav(plan, wavBytes, features[, channel[, hop]])"
+                                   : kind == IN_ONSETS ? "onsetsGather(plan, samples, starts, frameOffsets, {field, ...})"
                                    : kind == IN_SUMMARY ? "summarizeGather(plan, samples, starts, frameOffsets, features[, {deltaWidth, deltaOrder}])"
                                    : kind == IN_GATHER ? "extractGather(plan, samples, starts, features)"
                                    : kind == IN_SIGNAL ? "extractSignal(plan, samples, hop, features)"
@@ -1000,6 +1128,7 @@ static napi_value extract_wav_sync(napi_env env, napi_callback_info info) { retu
 static napi_value extract_signal_sync(napi_env env, napi_callback_info info) { return extract_common(env, info, IN_SIGNAL); }
 static napi_value extract_gather_sync(napi_env env, napi_callback_info info) { return extract_common(env, info, IN_GATHER); }
 static napi_value summarize_gather_sync(napi_env env, napi_callback_info info) { return extract_common(env, info, IN_SUMMARY); }
+static napi_value onsets_gather_sync(napi_env env, napi_callback_info info) { return extract_common(env, info, IN_ONSETS); }
 
 static void async_execute(napi_env env, void* data) {
   (void)env;
@@ -1030,8 +1159,9 @@ static napi_value extract_async_common(napi_env env, napi_callback_info info, in
   size_t argc = 6;
   napi_value argv[6];
   CHECK(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
-  if (argc < (kind == IN_SUMMARY ? 5u : kind == IN_SIGNAL || kind == IN_GATHER ? 4u : 3u)) {
+  if (argc < (kind == IN_SUMMARY || kind == IN_ONSETS ? 5u : kind == IN_SIGNAL || kind == IN_GATHER ? 4u : 3u)) {
     napi_throw_type_error(env, NULL, kind == IN_WAV ? "extractWavAsync(plan, wavBytes, features[, channel[, hop]])"
+                                   : kind == IN_ONSETS ? "onsetsGatherAsync(plan, samples, starts, frameOffsets, {field, ...})"
                                    : kind == IN_SUMMARY ? "summarizeGatherAsync(plan, samples, starts, frameOffsets, features[, {deltaWidth, deltaOrder}])"
                                    : kind == IN_GATHER ? "extractGatherAsync(plan, samples, starts, features)"
                                    : kind == IN_SIGNAL ? "extractSignalAsync(plan, samples, hop, features)"
@@ -1067,6 +1197,7 @@ static napi_value extract_wav_async(napi_env env, napi_callback_info info) { ret
 static napi_value extract_signal_async(napi_env env, napi_callback_info info) { return extract_async_common(env, info, IN_SIGNAL); }
 static napi_value extract_gather_async(napi_env env, napi_callback_info info) { return extract_async_common(env, info, IN_GATHER); }
 static napi_value summarize_gather_async(napi_env env, napi_callback_info info) { return extract_async_common(env, info, IN_SUMMARY); }
+static napi_value onsets_gather_async(napi_env env, napi_callback_info info) { return extract_async_common(env, info, IN_ONSETS); }
 
 /* signalsFrameStarts(lengths, bufferSize, hop): mgx_signals_frame_starts (host only) for signals stored one after
  * another; lengths: a Float64Array. Returns {starts, frameOffsets}, Float64Arrays. */
@@ -1297,6 +1428,8 @@ static napi_value init(napi_env env, napi_value exports) {
       {"extractGatherAsync", NULL, extract_gather_async, NULL, NULL, NULL, napi_enumerable, NULL},
       {"summarizeGather", NULL, summarize_gather_sync, NULL, NULL, NULL, napi_enumerable, NULL},
       {"summarizeGatherAsync", NULL, summarize_gather_async, NULL, NULL, NULL, napi_enumerable, NULL},
+      {"onsetsGather", NULL, onsets_gather_sync, NULL, NULL, NULL, napi_enumerable, NULL},
+      {"onsetsGatherAsync", NULL, onsets_gather_async, NULL, NULL, NULL, napi_enumerable, NULL},
       {"signalsFrameStarts", NULL, signals_frame_starts, NULL, NULL, NULL, napi_enumerable, NULL},
       {"wavParse", NULL, wav_parse, NULL, NULL, NULL, napi_enumerable, NULL},
       {"hostTables", NULL, host_tables, NULL, NULL, NULL, napi_enumerable, NULL},

@@ -42,6 +42,7 @@ EXPORTS = ["mgx_plan_desc_init", "mgx_plan_create", "mgx_plan_destroy", "mgx_pla
            "mgx_delta_device", "mgx_summarize_deltas_workspace_bytes", "mgx_summarize_deltas_device",
            "mgx_summarize_deltas_host",
            "mgx_flux_device", "mgx_summarize_flux_workspace_bytes", "mgx_summarize_flux_device", "mgx_summarize_flux_host",
+           "mgx_peaks_workspace_bytes", "mgx_peaks_device", "mgx_onsets_host",
            "mgx_shard_range", "mgx_packed_layout", "mgx_comm_unique_id", "mgx_group_create",
            "mgx_group_create_rank", "mgx_group_create_loopback", "mgx_group_create_loopback_rccl", "mgx_group_destroy",
            "mgx_group_info", "mgx_group_comm_info", "mgx_group_extract_device", "mgx_group_extract_host"]
@@ -138,6 +139,32 @@ class FluxRequest(ctypes.Structure):
     """mgx_flux_request: one flux of one field through the mgx_summarize_flux_* calls."""
     _fields_ = [("struct_size", ctypes.c_uint32), ("field", ctypes.c_uint32), ("mode", ctypes.c_uint32), ("lag", ctypes.c_uint32),
                 ("per_frame", ctypes.c_void_p), ("summary", ctypes.c_void_p)]
+
+
+PEAK_MAX_REACH = 64  # MGX_PEAK_MAX_REACH
+PEAK_PARAMS = ("pre_max", "post_max", "pre_avg", "post_avg", "delta", "wait")
+
+
+class PeakParams(ctypes.Structure):
+    """mgx_peak_params: the windows, the threshold and the minimum distance of the peak picker."""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("pre_max", ctypes.c_uint32), ("post_max", ctypes.c_uint32),
+                ("pre_avg", ctypes.c_uint32), ("post_avg", ctypes.c_uint32), ("wait", ctypes.c_uint32),
+                ("delta", ctypes.c_double)]
+
+
+class PeakOutputs(ctypes.Structure):
+    """mgx_peak_outputs: what mgx_peaks_device writes (device pointers)."""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("reserved", ctypes.c_uint32), ("mask", ctypes.c_void_p),
+                ("peak_offsets", ctypes.c_void_p), ("peaks", ctypes.c_void_p), ("capacity", ctypes.c_uint64),
+                ("starts", ctypes.c_void_p), ("peak_starts", ctypes.c_void_p)]
+
+
+def peak_params(pre_max=0, post_max=0, pre_avg=0, post_avg=0, delta=0.0, wait=0):
+    """A PeakParams; numbers out of range pass through: the library refuses them with its message."""
+    p = PeakParams()
+    p.struct_size = ctypes.sizeof(PeakParams)
+    p.pre_max, p.post_max, p.pre_avg, p.post_avg, p.wait, p.delta = pre_max, post_max, pre_avg, post_avg, wait, delta
+    return p
 
 
 class HostTables(ctypes.Structure):
@@ -254,6 +281,13 @@ def lib():
         L.mgx_summarize_flux_host.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p,
                                               ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(Outputs), aux,
                                               summ, dsum, freq, ctypes.c_uint32]
+        L.mgx_peaks_workspace_bytes.argtypes = [ctypes.c_uint64, ctypes.c_uint64, u64p]
+        L.mgx_peaks_device.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint64,
+                                       ctypes.POINTER(PeakParams), ctypes.POINTER(PeakOutputs), ctypes.c_void_p, ctypes.c_uint64,
+                                       ctypes.c_void_p]
+        L.mgx_onsets_host.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64,
+                                      ctypes.c_void_p, ctypes.c_uint64, freq, ctypes.POINTER(PeakParams), ctypes.c_void_p,
+                                      ctypes.c_void_p, ctypes.c_uint64]
         L.mgx_shard_range.argtypes = [ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, u64p, u64p]
         L.mgx_packed_layout.argtypes = [ctypes.POINTER(PlanDesc), ctypes.c_uint32, ctypes.c_uint64, u64p]
         L.mgx_packed_layout.restype = ctypes.c_uint64
@@ -699,6 +733,45 @@ class Plan:
                                        frame_offsets.ctypes.data, S, ctypes.byref(o), _aux_ref(o), ctypes.byref(so)))
         return summ, rows
 
+    def onsets(self, samples, starts, frame_offsets, feature="melBands", mode="rectified", lag=1, envelope=False, summary=False,
+               capacity=None, **params):
+        """Host numpy in / numpy out (mgx_onsets_host): the flux of `feature` over the buffers at `starts`, and its
+        peaks within each signal picked on the device (params: pre_max, post_max, pre_avg, post_avg, delta, wait).
+        Returns a dict: "peak_offsets" (S + 1, uint64: the true counts), "peaks" (the row indices, ascending; the
+        first `capacity` when that is given and smaller, None with capacity 0), and "envelope" ((F,) float32, zero
+        in rows of no signal) and "summary" ((S, 4)) when asked. Without `capacity` the call is made twice: once for
+        the counts, once for the list."""
+        samples = np.ascontiguousarray(samples, dtype=np.float32)
+        starts = np.ascontiguousarray(starts, dtype=np.uint64)
+        frame_offsets = np.ascontiguousarray(frame_offsets, dtype=np.uint64)
+        assert samples.ndim == 1 and starts.ndim == 1 and frame_offsets.ndim == 1 and frame_offsets.size >= 1
+        S = frame_offsets.size - 1
+        req = {"feature": feature, "mode": mode, "lag": lag, "per_frame": envelope, "summary": summary}
+        reqs, fres = self._flux_requests(starts.size, S, [req], lambda shape: np.empty(shape, np.float64),
+                                         lambda shape: np.zeros(shape, np.float32))
+        pp = peak_params(**params)
+        offsets = np.zeros(S + 1, np.uint64)
+
+        def call(peaks, cap):
+            check(lib().mgx_onsets_host(self._h, samples.ctypes.data, samples.size, starts.ctypes.data, starts.size,
+                                        frame_offsets.ctypes.data, S, reqs, ctypes.byref(pp), offsets.ctypes.data,
+                                        None if peaks is None else peaks.ctypes.data, cap))
+        peaks = None
+        if capacity is None or capacity == 0:
+            call(None, 0)
+            if capacity is None:
+                capacity, peaks = int(offsets[S]), np.zeros(0, np.uint64)
+        if capacity > 0:
+            peaks = np.zeros(capacity, np.uint64)
+            call(peaks, capacity)
+            peaks = peaks[:min(capacity, int(offsets[S]))]
+        res = {"peak_offsets": offsets, "peaks": peaks}
+        if envelope:
+            res["envelope"] = fres[0]["per_frame"]
+        if summary:
+            res["summary"] = fres[0]["summary"]
+        return res
+
     def summarize_signals(self, signals, hop, features, per_frame=(), deltas=None, flux=None):
         """A list of 1-D host signals in one call, pooled per signal: returns (summaries, frame_offsets), summaries
         being {name: ndarray (S, 4, width)} of mean, variance, min, max (STATS) over each signal's buffers; with
@@ -1016,3 +1089,63 @@ def flux_torch(rows, frame_offsets=None, mode="rectified", lag=1, stream=None, o
     flux_device(rows.data_ptr(), F, cols, rows.dtype == torch.float64, None if frame_offsets is None else frame_offsets.data_ptr(),
                 S, mode, lag, out.data_ptr(), stream)
     return out
+
+
+def peaks_workspace_bytes(num_frames, num_signals=0):
+    """mgx_peaks_workspace_bytes (host only)."""
+    b = ctypes.c_uint64()
+    check(lib().mgx_peaks_workspace_bytes(num_frames, num_signals, ctypes.byref(b)))
+    return b.value
+
+
+def peaks_device(envelope_ptr, num_frames, envelope_f64, offsets_ptr, num_signals, params, out, workspace_ptr, workspace_bytes,
+                 stream=None):
+    """mgx_peaks_device on device pointers (async on `stream`); params: a PeakParams, out: a PeakOutputs; a pointer may be None."""
+    check(lib().mgx_peaks_device(ctypes.c_void_p(envelope_ptr or 0), num_frames, 1 if envelope_f64 else 0,
+                                 ctypes.c_void_p(offsets_ptr or 0), num_signals, ctypes.byref(params), ctypes.byref(out),
+                                 ctypes.c_void_p(workspace_ptr or 0), workspace_bytes, ctypes.c_void_p(stream or 0)))
+
+
+def peaks_torch(envelope, frame_offsets=None, capacity=None, starts=None, stream=None, mask_fill=0, **params):
+    """The peaks of `envelope`, a (F,) float32 or float64 CUDA tensor, within each signal (include/meyda_gpu.h):
+    params are pre_max, post_max, pre_avg, post_avg, delta, wait. Signal s owns rows [frame_offsets[s],
+    frame_offsets[s + 1]) (an int64 CUDA tensor, or anything numpy turns into one; None: one signal, every row).
+    Returns (mask, peak_offsets, peaks) -- a (F,) uint8 tensor, `mask_fill` in rows that belong to no signal; a
+    (S + 1,) int64 tensor of the true counts; a (capacity,) int64 tensor of row indices, of which the first
+    min(peak_offsets[S], capacity) are written (capacity None: F, which always holds them) -- and, with `starts`
+    (the gather table the rows came from), a fourth tensor: starts[peaks[i]], the next launch's table.
+    The workspace is allocated here, as summarize_gather_torch allocates its own."""
+    import torch
+    assert envelope.is_cuda and envelope.is_contiguous() and envelope.dim() == 1
+    assert envelope.dtype in (torch.float32, torch.float64)
+    dev = envelope.device
+    F = envelope.shape[0]
+    S = 0
+    if frame_offsets is not None:
+        if not torch.is_tensor(frame_offsets):
+            frame_offsets = torch.from_numpy(np.ascontiguousarray(frame_offsets, dtype=np.uint64).view(np.int64)).to(dev)
+        assert frame_offsets.is_cuda and frame_offsets.dtype == torch.int64 and frame_offsets.is_contiguous()
+        assert frame_offsets.dim() == 1 and frame_offsets.shape[0] >= 1
+        S = frame_offsets.shape[0] - 1
+    if capacity is None:
+        capacity = max(F, 1)
+    mask = torch.full((F,), mask_fill, dtype=torch.uint8, device=dev)
+    offsets = torch.zeros((S if frame_offsets is not None else 1) + 1, dtype=torch.int64, device=dev)
+    peaks = torch.zeros(capacity, dtype=torch.int64, device=dev)
+    o = PeakOutputs()
+    o.struct_size = ctypes.sizeof(PeakOutputs)
+    o.mask, o.peak_offsets, o.peaks, o.capacity = mask.data_ptr(), offsets.data_ptr(), peaks.data_ptr(), capacity
+    peak_starts = None
+    if starts is not None:
+        if not torch.is_tensor(starts):
+            starts = torch.from_numpy(np.ascontiguousarray(starts, dtype=np.uint64).view(np.int64)).to(dev)
+        assert starts.is_cuda and starts.dtype == torch.int64 and starts.is_contiguous() and starts.shape == (F,)
+        peak_starts = torch.zeros(capacity, dtype=torch.int64, device=dev)
+        o.starts, o.peak_starts = starts.data_ptr(), peak_starts.data_ptr()
+    nbytes = peaks_workspace_bytes(F, S)
+    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+    if stream is None:
+        stream = torch.cuda.current_stream(dev).cuda_stream
+    peaks_device(envelope.data_ptr(), F, envelope.dtype == torch.float64, None if frame_offsets is None else frame_offsets.data_ptr(),
+                 S, peak_params(**params), o, ws.data_ptr(), nbytes, stream)
+    return (mask, offsets, peaks) if starts is None else (mask, offsets, peaks, peak_starts)

@@ -3464,6 +3464,391 @@ hipError_t launch_flux(const void* rows, const void* carry, void* out, uint64_t 
   return hipGetLastError();
 }
 
+// ---- Onsets (mgx_peaks_device, mgx_onsets_host): the peaks of a one-column envelope within each signal ----
+// Four steps over bitmaps of one bit per row, the words aligned to row 0 of the array:
+//   peak_candidate_kernel<T>: a workgroup owns a tile of 256 consecutive rows and keeps them, with a halo of
+//     MGX_PEAK_MAX_REACH rows on each side, in LDS as float64; a thread resolves one row -- its signal by a binary
+//     search of the table, as flux_kernel does, the two windows over the clamped rows of LDS -- and a wave's
+//     __ballot is one word of the candidate bitmap and one of the bitmap of the rows that belong to a signal,
+//     each written by one lane with a plain store.
+//   peak_wait_kernel: the greedy minimum distance, over the candidate words and not over the envelope. A walk
+//     goes through a signal's words in ascending order carrying one number, the first row allowed; inside a word
+//     the lowest set bit at or above that row is taken and the bits up to `wait` behind it are cleared. A thread
+//     owns a chunk of four words (256 rows) whatever the signals are: the signals that begin in the chunk it walks
+//     from a fresh start, and the one that holds the chunk's first row from a restart row, found by scanning the
+//     words below the chunk for `wait` empty rows -- a candidate with no candidate in the `wait` rows before it is
+//     a peak whatever came before. A corpus of short clips and one long signal are both parallel over chunks.
+//   peak_count_kernel, peak_scan_kernel: the set bits of every block of kPeakScanWords accepted words, and the
+//     exclusive scan of those sums by one workgroup, in ascending order.
+//   peak_write_kernel, peak_offsets_kernel: a word's rank is its block's plus the scan of the popcounts before it
+//     in the block; a thread writes the rows of its words' set bits to peaks (and their starts to peak_starts)
+//     below `capacity`, the workgroup writes the mask of the rows that belong to a signal, and peak_offsets[s] is
+//     the rank at the signal's first row.
+// No atomics, one writer per word and per output, nothing depends on the grid.
+namespace {
+
+constexpr uint32_t kPeakTileRows = 256;     // a thread resolves one row; a wave's ballot is one word
+constexpr uint32_t kPeakHalo = MGX_PEAK_MAX_REACH;
+constexpr uint32_t kPeakScanWords = 1024;   // words of a scan block: four consecutive words per thread
+static_assert(kPeakHalo == 64 && kPeakTileRows % 64 == 0, "a tile is whole words, the halo one word");
+
+struct PeakArgs {
+  const void* env;
+  const uint64_t* table;   // null: one signal, rows [0, num_frames)
+  uint64_t num_signals;    // entries of the table less one (1 with a null table)
+  uint64_t num_frames, nwords, nblocks, ntiles;
+  uint64_t* cand;          // nwords: the candidates
+  uint64_t* acc;           // nwords: the peaks (cand itself when wait is 0)
+  uint64_t* member;        // nwords: the rows that belong to a signal
+  uint64_t* wrank;         // nwords: the peaks before the word
+  uint64_t* bsum;          // nblocks + 1: the peaks before the scan block; the total
+  uint32_t pre_max, post_max, pre_avg, post_avg, wait, pad;
+  double delta;
+  uint8_t* mask;
+  uint64_t* peak_offsets;
+  uint64_t* peaks;
+  uint64_t capacity;
+  const uint64_t* starts;
+  uint64_t* peak_starts;
+};
+
+// signal s of the table, every entry limited to num_frames
+__device__ __forceinline__ void peak_signal(const PeakArgs& g, uint64_t s, uint64_t& a, uint64_t& b) {
+  const uint64_t T_ = g.num_frames;
+  if (!g.table) {
+    a = 0;
+    b = T_;
+    return;
+  }
+  a = g.table[s];
+  b = g.table[s + 1];
+  a = a < T_ ? a : T_;
+  b = b < T_ ? b : T_;
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void peak_candidate_kernel(PeakArgs g) {
+  __shared__ double xs[kPeakTileRows + 2 * kPeakHalo];
+  const T* __restrict__ const env = static_cast<const T*>(g.env);
+  const uint64_t T_ = g.num_frames;
+  const double count = (double)(g.pre_avg + g.post_avg + 1);
+  for (uint64_t tile = blockIdx.x; tile < g.ntiles; tile += gridDim.x) {
+    const uint64_t r0 = tile * kPeakTileRows;
+    // xs[i]: row r0 - halo + i, where the array has it (a row a window reads is one of its signal, so of the array)
+    for (uint32_t i = threadIdx.x; i < kPeakTileRows + 2 * kPeakHalo; i += 256) {
+      const uint64_t u = r0 + i;
+      xs[i] = u >= kPeakHalo && u - kPeakHalo < T_ ? (double)env[u - kPeakHalo] : 0.0;
+    }
+    const uint64_t t = r0 + threadIdx.x;
+    // the row's signal: the last s with table[s] <= t; [a, b) empty when the row belongs to none
+    uint64_t a = 0, b = T_;
+    if (g.table) {
+      uint64_t lo = 0, hi = g.num_signals + 1;  // the first entry above t
+      while (lo < hi) {
+        const uint64_t mid = lo + (hi - lo) / 2;
+        if (g.table[mid] <= t) lo = mid + 1;
+        else hi = mid;
+      }
+      a = b = 0;
+      if (lo > 0 && lo <= g.num_signals) peak_signal(g, lo - 1, a, b);
+    }
+    const bool in = t >= a && t < b;  // (whatever the table holds: a <= t <= b - 1 < num_frames where it is true)
+    __syncthreads();
+    bool cand = false;
+    if (in) {
+      // row u of the signal's clamped rows, for t - halo <= u + halo: xs[clamp(u) - r0 + halo], clamp(u) within the halo of t
+      const int64_t lo_i = (int64_t)(a - r0) + (int64_t)kPeakHalo, hi_i = (int64_t)(b - 1 - r0) + (int64_t)kPeakHalo;
+      const int64_t c = (int64_t)threadIdx.x + (int64_t)kPeakHalo;
+      auto at = [&](int64_t i) {
+        i = i < lo_i ? lo_i : i;
+        i = i > hi_i ? hi_i : i;
+        return xs[i];
+      };
+      const double x = xs[c];
+      bool top = true;
+      for (int64_t i = c - (int64_t)g.pre_max; i <= c + (int64_t)g.post_max; ++i) top = top && !(at(i) > x);
+      double m = 0.0;
+      for (int64_t i = c - (int64_t)g.pre_avg; i <= c + (int64_t)g.post_avg; ++i) m += at(i);
+      m = m / count;
+      m = m + g.delta;
+      cand = top && x >= m;
+    }
+    const uint64_t cw = __ballot(cand), mw = __ballot(in);
+    const uint64_t w = (r0 >> 6) + (threadIdx.x >> 6);
+    if ((threadIdx.x & 63) == 0 && w < g.nwords) {
+      g.cand[w] = cw;
+      g.member[w] = mw;
+    }
+    __syncthreads();
+  }
+}
+
+// the bits of rows [lo, hi) in the word of rows [base, base + 64); lo < hi
+__device__ __forceinline__ uint64_t peak_row_bits(uint64_t base, uint64_t lo, uint64_t hi) {
+  uint64_t m = ~0ull;
+  if (lo > base) m &= lo - base >= 64 ? 0ull : ~0ull << (lo - base);
+  if (hi < base + 64) m &= hi <= base ? 0ull : ~0ull >> (base + 64 - hi);
+  return m;
+}
+
+// The greedy step in one word: the lowest candidate at or above `allowed` is a peak, and the next one allowed is
+// wait + 1 rows behind it.
+__device__ __forceinline__ uint64_t peak_walk_word(uint64_t bits, uint64_t base, uint64_t& allowed, uint64_t wait) {
+  uint64_t got = 0;
+  if (allowed > base) bits &= allowed - base >= 64 ? 0ull : ~0ull << (allowed - base);
+  while (bits) {
+    const uint64_t p = (uint64_t)(__ffsll((unsigned long long)bits) - 1), next = p + wait + 1;
+    got |= 1ull << p;
+    bits = next >= 64 ? 0ull : bits & (~0ull << next);
+    allowed = base + next;
+  }
+  return got;
+}
+
+// The first row allowed for a walk that enters the signal [a, ...) at the word-aligned row r0 > a without its
+// history: a row g in [a, r0] with no candidate in the `wait` rows below it (or g = a). A candidate at or above such
+// a row with none between is a peak whatever came before -- every earlier peak is a candidate, so more than `wait`
+// rows away -- and the walk from g gives the peaks the walk from a gives from there on. The words below r0 are
+// scanned downwards for the highest run of `wait` empty rows: across a word's top with the count carried from the
+// words above, or inside the word (wait < 64) by AND-ing the empty mask with itself shifted, a few steps per word.
+__device__ __forceinline__ uint64_t peak_restart_row(const uint64_t* __restrict__ cand, uint64_t a, uint64_t r0, uint64_t wait) {
+  uint64_t carry = 0;  // empty rows directly above the word's top
+  for (uint64_t w = r0 >> 6; w-- > (a >> 6);) {
+    const uint64_t base = w << 6;
+    uint64_t bits = cand[w];
+    if (a > base) bits |= ~(~0ull << (a - base));  // rows of another signal: never empty
+    const uint64_t top = bits ? (uint64_t)__clzll((long long)bits) : 64;
+    if (carry + top >= wait) return base + 64 + carry;
+    if (wait < 64) {
+      uint64_t r = ~bits;  // bit i: rows i .. i + k - 1 are empty
+      for (uint64_t k = 1; k < wait;) {
+        const uint64_t step = k < wait - k ? k : wait - k;
+        r &= r >> step;
+        k += step;
+      }
+      if (r) return base + (63 - (uint64_t)__clzll((long long)r)) + wait;
+    }
+    carry = bits ? (uint64_t)(__ffsll((unsigned long long)bits) - 1) : carry + 64;
+  }
+  return a;
+}
+
+constexpr uint32_t kPeakWalkWords = 4;  // words of a thread's chunk of the walk
+
+// A thread owns kPeakWalkWords consecutive words and walks the signals that have rows in them, in ascending order:
+// a signal that begins in the chunk from a fresh start, the one that holds the chunk's first row from its restart
+// row (peak_restart_row; the words from there to the chunk are walked for the carry alone). One writer per word.
+__global__ __launch_bounds__(64) void peak_wait_kernel(PeakArgs g) {
+  const uint64_t wait = g.wait, S = g.num_signals;
+  const uint64_t nchunks = (g.nwords + kPeakWalkWords - 1) / kPeakWalkWords;
+  for (uint64_t c = (uint64_t)blockIdx.x * 64 + threadIdx.x; c < nchunks; c += (uint64_t)gridDim.x * 64) {
+    const uint64_t w0 = c * kPeakWalkWords, r0 = w0 << 6;
+    const uint64_t w1 = w0 + kPeakWalkWords < g.nwords ? w0 + kPeakWalkWords : g.nwords;
+    // the signal of the chunk's first row: the last s with table[s] <= r0, or the first signal
+    uint64_t s = 0;
+    if (g.table) {
+      uint64_t lo = 0, hi = S + 1;  // the first entry above r0
+      while (lo < hi) {
+        const uint64_t mid = lo + (hi - lo) / 2;
+        if (g.table[mid] <= r0) lo = mid + 1;
+        else hi = mid;
+      }
+      s = lo > 0 ? lo - 1 : 0;
+    }
+    uint64_t a = 0, b = 0, allowed = 0;
+    if (s < S) {
+      peak_signal(g, s, a, b);
+      allowed = a;
+      if (a < r0 && r0 < b) {
+        allowed = peak_restart_row(g.cand, a, r0, wait);
+        for (uint64_t w = allowed >> 6; w < w0; ++w) (void)peak_walk_word(g.cand[w] & peak_row_bits(w << 6, a, b), w << 6, allowed, wait);
+      }
+    }
+    for (uint64_t w = w0; w < w1; ++w) {
+      const uint64_t base = w << 6, whole = g.cand[w];
+      uint64_t got = 0;
+      while (s < S) {
+        if (b <= base || !(a < b)) {  // the signal ended below the word, or has no rows: the next one, from a fresh start
+          if (++s < S) {
+            peak_signal(g, s, a, b);
+            allowed = a;
+          }
+          continue;
+        }
+        if (a >= base + 64) break;
+        got |= peak_walk_word(whole & peak_row_bits(base, a, b), base, allowed, wait);
+        if (b >= base + 64) break;  // it goes on in the next word
+        if (++s < S) {
+          peak_signal(g, s, a, b);
+          allowed = a;
+        }
+      }
+      g.acc[w] = got;
+    }
+  }
+}
+
+__device__ __forceinline__ uint32_t peak_popc(uint64_t w) { return (uint32_t)__popcll((unsigned long long)w); }
+
+// the inclusive scan of v over the workgroup's 256 threads, in thread order
+__device__ __forceinline__ uint64_t peak_block_scan(uint64_t v, uint64_t* tmp) {
+  tmp[threadIdx.x] = v;
+  __syncthreads();
+  for (uint32_t d = 1; d < 256; d <<= 1) {
+    const uint64_t add = threadIdx.x >= d ? tmp[threadIdx.x - d] : 0;
+    __syncthreads();
+    tmp[threadIdx.x] += add;
+    __syncthreads();
+  }
+  return tmp[threadIdx.x];
+}
+
+__global__ __launch_bounds__(256) void peak_count_kernel(PeakArgs g) {
+  __shared__ uint64_t tmp[256];
+  for (uint64_t blk = blockIdx.x; blk < g.nblocks; blk += gridDim.x) {
+    const uint64_t w0 = blk * kPeakScanWords + 4 * threadIdx.x;
+    uint64_t n = 0;
+    for (uint32_t k = 0; k < 4; ++k)
+      if (w0 + k < g.nwords) n += peak_popc(g.acc[w0 + k]);
+    const uint64_t incl = peak_block_scan(n, tmp);
+    if (threadIdx.x == 255) g.bsum[blk] = incl;
+    __syncthreads();
+  }
+}
+
+// bsum[i] = the sum of the entries before it; bsum[nblocks] = the total (one workgroup)
+__global__ __launch_bounds__(256) void peak_scan_kernel(PeakArgs g) {
+  __shared__ uint64_t tmp[256];
+  uint64_t carry = 0;
+  for (uint64_t i0 = 0; i0 < g.nblocks; i0 += 256) {
+    const uint64_t i = i0 + threadIdx.x;
+    const uint64_t v = i < g.nblocks ? g.bsum[i] : 0;
+    const uint64_t incl = peak_block_scan(v, tmp);
+    if (i < g.nblocks) g.bsum[i] = carry + incl - v;
+    carry += tmp[255];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) g.bsum[g.nblocks] = carry;
+}
+
+__global__ __launch_bounds__(256) void peak_write_kernel(PeakArgs g) {
+  __shared__ uint64_t tmp[256];
+  __shared__ uint64_t acc_s[kPeakScanWords], mem_s[kPeakScanWords];
+  for (uint64_t blk = blockIdx.x; blk < g.nblocks; blk += gridDim.x) {
+    const uint64_t w0 = blk * kPeakScanWords + 4 * threadIdx.x;
+    uint64_t word[4], n = 0;
+    for (uint32_t k = 0; k < 4; ++k) {
+      word[k] = w0 + k < g.nwords ? g.acc[w0 + k] : 0;
+      acc_s[4 * threadIdx.x + k] = word[k];
+      mem_s[4 * threadIdx.x + k] = g.mask && w0 + k < g.nwords ? g.member[w0 + k] : 0;
+      n += peak_popc(word[k]);
+    }
+    uint64_t rank = g.bsum[blk] + peak_block_scan(n, tmp) - n;
+    for (uint32_t k = 0; k < 4; ++k) {
+      if (!(w0 + k < g.nwords)) break;
+      g.wrank[w0 + k] = rank;
+      uint64_t bits = word[k];
+      while (bits) {
+        const uint64_t row = ((w0 + k) << 6) + (uint64_t)(__ffsll((unsigned long long)bits) - 1);
+        bits &= bits - 1;
+        if (g.peaks && rank < g.capacity) {
+          g.peaks[rank] = row;
+          if (g.peak_starts) g.peak_starts[rank] = g.starts[row];
+        }
+        ++rank;
+      }
+    }
+    // (acc_s, mem_s: written before the scan's barriers)
+    if (g.mask) {
+      const uint64_t row0 = blk * kPeakScanWords * 64;
+      for (uint32_t j = threadIdx.x; j < kPeakScanWords * 64; j += 256) {
+        const uint64_t t = row0 + j;
+        if (t >= g.num_frames) break;
+        if ((mem_s[j >> 6] >> (j & 63)) & 1) g.mask[t] = (uint8_t)((acc_s[j >> 6] >> (j & 63)) & 1);
+      }
+    }
+    __syncthreads();
+  }
+}
+
+__global__ __launch_bounds__(256) void peak_offsets_kernel(PeakArgs g) {
+  const uint64_t n = g.num_signals + 1;
+  for (uint64_t s = (uint64_t)blockIdx.x * 256 + threadIdx.x; s < n; s += (uint64_t)gridDim.x * 256) {
+    uint64_t a = g.table ? g.table[s] : (s == 0 ? 0 : g.num_frames);
+    a = a < g.num_frames ? a : g.num_frames;
+    const uint64_t w = a >> 6;
+    g.peak_offsets[s] = a >= g.num_frames ? g.bsum[g.nblocks] : g.wrank[w] + peak_popc(g.acc[w] & ~(~0ull << (a & 63)));
+  }
+}
+
+}  // namespace
+
+uint64_t peaks_workspace_bytes(uint64_t num_frames, PeakLayout* l) {
+  PeakLayout x{};
+  const uint64_t nwords = (num_frames + 63) / 64, nblocks = (nwords + kPeakScanWords - 1) / kPeakScanWords;
+  auto take = [&x](uint64_t bytes) {
+    const uint64_t at = x.total;
+    x.total += (bytes + 255) / 256 * 256;
+    return at;
+  };
+  if (num_frames > 0) {
+    x.cand = take(nwords * 8);
+    x.acc = take(nwords * 8);
+    x.member = take(nwords * 8);
+    x.wrank = take(nwords * 8);
+    x.bsum = take((nblocks + 1) * 8);
+  }
+  if (l) *l = x;
+  return x.total;
+}
+
+hipError_t launch_peaks(const void* env, uint64_t num_frames, bool f64, const uint64_t* table, uint64_t num_signals,
+                        const mgx_peak_params& p, const mgx_peak_outputs& o, void* workspace, hipStream_t stream) {
+  if (num_frames == 0) return hipSuccess;
+  if (p.pre_max > kPeakHalo || p.post_max > kPeakHalo || p.pre_avg > kPeakHalo || p.post_avg > kPeakHalo || !workspace)
+    return hipErrorInvalidValue;
+  PeakLayout l;
+  peaks_workspace_bytes(num_frames, &l);
+  unsigned char* const ws = static_cast<unsigned char*>(workspace);
+  PeakArgs g{};
+  g.env = env;
+  g.table = table;
+  g.num_signals = table ? num_signals : 1;
+  g.num_frames = num_frames;
+  g.nwords = (num_frames + 63) / 64;
+  g.nblocks = (g.nwords + kPeakScanWords - 1) / kPeakScanWords;
+  g.ntiles = (num_frames + kPeakTileRows - 1) / kPeakTileRows;
+  g.cand = reinterpret_cast<uint64_t*>(ws + l.cand);
+  g.acc = p.wait == 0 ? g.cand : reinterpret_cast<uint64_t*>(ws + l.acc);  // no distance to keep: every candidate
+  g.member = reinterpret_cast<uint64_t*>(ws + l.member);
+  g.wrank = reinterpret_cast<uint64_t*>(ws + l.wrank);
+  g.bsum = reinterpret_cast<uint64_t*>(ws + l.bsum);
+  g.pre_max = p.pre_max;
+  g.post_max = p.post_max;
+  g.pre_avg = p.pre_avg;
+  g.post_avg = p.post_avg;
+  g.wait = p.wait;
+  g.delta = p.delta;
+  g.mask = o.mask;
+  g.peak_offsets = o.peak_offsets;
+  g.peaks = o.peaks;
+  g.capacity = o.capacity;
+  g.starts = o.starts;
+  g.peak_starts = o.peak_starts;
+  auto blocks = [](uint64_t n) { return dim3((unsigned)(n < 16384 ? n : 16384)); };
+  if (f64) hipLaunchKernelGGL((peak_candidate_kernel<double>), blocks(g.ntiles), dim3(256), 0, stream, g);
+  else hipLaunchKernelGGL((peak_candidate_kernel<float>), blocks(g.ntiles), dim3(256), 0, stream, g);
+  if (g.acc != g.cand)
+    hipLaunchKernelGGL(peak_wait_kernel, blocks(((g.nwords + kPeakWalkWords - 1) / kPeakWalkWords + 63) / 64), dim3(64), 0, stream, g);
+  if (g.peaks || g.peak_offsets) {
+    hipLaunchKernelGGL(peak_count_kernel, blocks(g.nblocks), dim3(256), 0, stream, g);
+    hipLaunchKernelGGL(peak_scan_kernel, dim3(1), dim3(256), 0, stream, g);
+  }
+  if (g.peaks || g.peak_offsets || g.mask) hipLaunchKernelGGL(peak_write_kernel, blocks(g.nblocks), dim3(256), 0, stream, g);
+  if (g.peak_offsets) hipLaunchKernelGGL(peak_offsets_kernel, blocks((g.num_signals + 256) / 256), dim3(256), 0, stream, g);
+  return hipGetLastError();
+}
+
 }  // namespace mgx
 
 #if MGX_WAVE_TIMES

@@ -239,6 +239,17 @@ hipError_t launch_delta(const void* rows, void* out, uint64_t num_frames, uint32
 hipError_t launch_flux(const void* rows, const void* carry, void* out, uint64_t row0, uint64_t nrows, uint64_t num_frames,
                        uint32_t cols, bool f64, const uint64_t* table, uint64_t num_signals, uint32_t mode, uint32_t lag,
                        hipStream_t stream);
+// Onsets (mgx_peaks_device, mgx_onsets_host; kernels.hip peak_*_kernel): the peaks of the one-column envelope env
+// (num_frames values, float32 or float64 as f64 says) within each signal, the table as launch_delta reads it (null:
+// one signal, every row). The workspace holds four bitmaps of one bit per row (the candidates, the peaks, the rows of
+// a signal, and per word the peaks before it) and the scan's block sums: peaks_workspace_bytes(num_frames), a
+// multiple of 256 (0 for no rows). Up to six launches, asynchronous; p and o are checked by the caller.
+struct PeakLayout {
+  uint64_t cand, acc, member, wrank, bsum, total;
+};
+uint64_t peaks_workspace_bytes(uint64_t num_frames, PeakLayout* l = nullptr);
+hipError_t launch_peaks(const void* env, uint64_t num_frames, bool f64, const uint64_t* table, uint64_t num_signals,
+                        const mgx_peak_params& p, const mgx_peak_outputs& o, void* workspace, hipStream_t stream);
 size_t extract_lds_bytes(int n, int ncoef, int nfilt, bool chain);
 size_t lds_image_bytes(int n, int ncoef, int nfilt);  // DevTables::lds_image, a multiple of 16
 hipError_t launch_lds_image(int n, int precision, int mode, const KernelArgs& a, void* image, hipStream_t stream);

@@ -497,7 +497,8 @@ struct mgx_plan {
   unsigned char* s_delta = nullptr;
   size_t s_delta_bytes = 0;
   // mgx_summarize_flux_host: a table, per request the two carries of lag rows and the flux column of the whole
-  // call, then shifts, partials and summaries (one allocation, grown when a call needs more)
+  // call, then shifts, partials and summaries (one allocation, grown when a call needs more); mgx_onsets_host: behind
+  // them the picker's workspace, its offsets and the peaks the caller has room for
   unsigned char* s_flux = nullptr;
   size_t s_flux_bytes = 0;
   hipStream_t s_copy = nullptr, s_comp = nullptr;
@@ -1889,6 +1890,27 @@ int delta_pool(const mgx_plan_desc& d, DeltaReq& q, const mgx::Outputs& x, unsig
   return e == hipSuccess ? (int)MGX_OK : hip_fail(e, "delta and summary kernel launch");
 }
 
+// mgx_onsets_host: the picker behind the host flux call, over the column of its first request
+struct PeakHost {
+  const mgx_peak_params* params;
+  uint64_t* peak_offsets;  // host, num_signals + 1
+  uint64_t* peaks;         // host, capacity entries, or null
+  uint64_t capacity;
+};
+
+int check_peak_params(const mgx_peak_params* pp) {
+  if (!pp) return fail(MGX_E_INVALID_ARGUMENT, "params is NULL");
+  if (pp->struct_size != sizeof(mgx_peak_params))
+    return fail(MGX_E_INVALID_ARGUMENT, "mgx_peak_params.struct_size is %u, expected %zu", pp->struct_size, sizeof(mgx_peak_params));
+  const uint32_t reach[4] = {pp->pre_max, pp->post_max, pp->pre_avg, pp->post_avg};
+  static const char* const name[4] = {"pre_max", "post_max", "pre_avg", "post_avg"};
+  for (int i = 0; i < 4; ++i)
+    if (reach[i] > MGX_PEAK_MAX_REACH)
+      return fail(MGX_E_INVALID_ARGUMENT, "mgx_peak_params.%s is %u, expected 0..%d", name[i], reach[i], MGX_PEAK_MAX_REACH);
+  if (pp->delta != pp->delta) return fail(MGX_E_INVALID_ARGUMENT, "mgx_peak_params.delta is NaN");
+  return MGX_OK;
+}
+
 // mgx_summarize_flux_*: the caller's requests, the fields whose rows the call has to hold, and the requests that
 // are pooled as the columns of one summary launch (each of width 1; destinations the caller's arrays).
 struct FluxReq {
@@ -1901,7 +1923,8 @@ struct FluxReq {
   bool any() const { return n != 0; }
 };
 
-int flux_request(const mgx_plan* p, const mgx_flux_request* fr, uint32_t num, uint64_t nsignals, FluxReq* q) {
+// (bare: a request may name neither array -- mgx_onsets_host, which reads the column on the device)
+int flux_request(const mgx_plan* p, const mgx_flux_request* fr, uint32_t num, uint64_t nsignals, FluxReq* q, bool bare = false) {
   if (num == 0) return MGX_OK;
   if (!fr) return fail(MGX_E_INVALID_ARGUMENT, "flux is NULL with num_flux = %u", num);
   if (num > MGX_FLUX_MAX_REQUESTS) return fail(MGX_E_INVALID_ARGUMENT, "num_flux is %u, at most %d", num, MGX_FLUX_MAX_REQUESTS);
@@ -1914,7 +1937,7 @@ int flux_request(const mgx_plan* p, const mgx_flux_request* fr, uint32_t num, ui
       return fail(MGX_E_INVALID_ARGUMENT, "mgx_flux_request.mode is %u, expected 0..%d (flux[%u])", r.mode, MGX_NUM_FLUX_MODES - 1, i);
     if (r.lag < 1 || r.lag > MGX_FLUX_MAX_LAG)
       return fail(MGX_E_INVALID_ARGUMENT, "mgx_flux_request.lag is %u, expected 1..%d (flux[%u])", r.lag, MGX_FLUX_MAX_LAG, i);
-    if (!r.per_frame && !r.summary)
+    if (!r.per_frame && !r.summary && !bare)
       return fail(MGX_E_INVALID_ARGUMENT, "mgx_flux_request.per_frame and .summary are both NULL (flux[%u])", i);
     if (r.summary && nsignals == 0)
       return fail(MGX_E_INVALID_ARGUMENT, "mgx_flux_request.summary is set with num_signals = 0 (flux[%u])", i);
@@ -1992,7 +2015,7 @@ int flux_pool(FluxReq& q, float* const* col, unsigned char* buf, const FluxLayou
 int summarize_host_impl(mgx_plan* p, const float* samples, uint64_t num_samples, const uint64_t* starts, uint64_t nframes,
                         const uint64_t* frame_offsets, uint64_t nsignals, const mgx_outputs* outputs, const mgx_aux_outputs* aux,
                         const mgx_summary_outputs* summary, const mgx_delta_summaries* deltas,
-                        const mgx_flux_request* flux = nullptr, uint32_t nflux = 0);
+                        const mgx_flux_request* flux = nullptr, uint32_t nflux = 0, const PeakHost* pick = nullptr);
 
 // mgx_summarize_deltas_workspace_bytes (deltas there, no request) and mgx_summarize_flux_workspace_bytes (deltas or
 // not, requests): the summary call's buffer with the rows of every delta'd or flux'd field kept, then what the
@@ -2197,6 +2220,64 @@ int mgx_summarize_flux_device(mgx_plan* p, const float* samples, uint64_t num_sa
                                workspace, workspace_bytes, stream);
 }
 
+int mgx_peaks_workspace_bytes(uint64_t num_frames, uint64_t num_signals, uint64_t* bytes) {
+  (void)num_signals;  // (the bitmaps are the rows': a table costs nothing)
+  if (!bytes) return fail(MGX_E_INVALID_ARGUMENT, "bytes is NULL");
+  *bytes = mgx::peaks_workspace_bytes(num_frames);
+  return MGX_OK;
+}
+
+int mgx_peaks_device(const void* envelope, uint64_t num_frames, uint32_t envelope_f64, const uint64_t* frame_offsets,
+                     uint64_t num_signals, const mgx_peak_params* params, const mgx_peak_outputs* out, void* workspace,
+                     uint64_t workspace_bytes, void* stream) {
+  int rc = check_peak_params(params);
+  if (rc) return rc;
+  if (!out) return fail(MGX_E_INVALID_ARGUMENT, "out is NULL");
+  if (out->struct_size != sizeof(mgx_peak_outputs))
+    return fail(MGX_E_INVALID_ARGUMENT, "mgx_peak_outputs.struct_size is %u, expected %zu", out->struct_size, sizeof(mgx_peak_outputs));
+  if (envelope_f64 > 1) return fail(MGX_E_INVALID_ARGUMENT, "envelope_f64 is %u, expected 0 or 1", envelope_f64);
+  if (!out->mask && !out->peak_offsets && !out->peaks)
+    return fail(MGX_E_INVALID_ARGUMENT, "mgx_peak_outputs.mask, .peak_offsets and .peaks are all NULL");
+  if (out->peaks && out->capacity == 0) return fail(MGX_E_INVALID_ARGUMENT, "mgx_peak_outputs.peaks is set with capacity 0");
+  if (out->peak_starts && !out->starts) return fail(MGX_E_INVALID_ARGUMENT, "mgx_peak_outputs.peak_starts is set without starts");
+  if (out->peak_starts && !out->peaks) return fail(MGX_E_INVALID_ARGUMENT, "mgx_peak_outputs.peak_starts is set without peaks");
+  if (num_signals > 0 && !frame_offsets) return fail(MGX_E_INVALID_ARGUMENT, "frame_offsets is NULL");
+  if (num_frames > 0 && !envelope) return fail(MGX_E_INVALID_ARGUMENT, "envelope is NULL");
+  const uint64_t need = mgx::peaks_workspace_bytes(num_frames);
+  if (workspace_bytes < need || (need > 0 && !workspace))
+    return fail(MGX_E_INVALID_ARGUMENT, "the workspace holds %llu bytes, the call needs %llu (mgx_peaks_workspace_bytes)",
+                (unsigned long long)workspace_bytes, (unsigned long long)need);
+  if (need > 0 && reinterpret_cast<uintptr_t>(workspace) % 256 != 0)
+    return fail(MGX_E_INVALID_ARGUMENT, "the workspace is not 256-byte aligned");
+  if (num_frames == 0) {
+    // no rows, no peaks: the offsets alone (frame_offsets with num_signals = 0: no signal, one entry)
+    if (!out->peak_offsets) return MGX_OK;
+    const uint64_t S = frame_offsets ? num_signals : 1;
+    const hipError_t e = hipMemsetAsync(out->peak_offsets, 0, (S + 1) * sizeof(uint64_t), (hipStream_t)stream);
+    return e == hipSuccess ? MGX_OK : hip_fail(e, "hipMemsetAsync(peak_offsets)");
+  }
+  const hipError_t e = mgx::launch_peaks(envelope, num_frames, envelope_f64 != 0, frame_offsets, num_signals, *params, *out, workspace,
+                                         (hipStream_t)stream);
+  return e == hipSuccess ? MGX_OK : hip_fail(e, "peak kernel launch");
+}
+
+int mgx_onsets_host(mgx_plan* p, const float* samples, uint64_t num_samples, const uint64_t* starts, uint64_t nframes,
+                    const uint64_t* frame_offsets, uint64_t nsignals, const mgx_flux_request* flux, const mgx_peak_params* params,
+                    uint64_t* peak_offsets, uint64_t* peaks, uint64_t capacity) {
+  int rc = check_peak_params(params);
+  if (rc) return rc;
+  if (nsignals == 0) return fail(MGX_E_INVALID_ARGUMENT, "num_signals is 0: onsets are picked within signals");
+  if (!flux) return fail(MGX_E_INVALID_ARGUMENT, "flux is NULL");
+  if (!peak_offsets) return fail(MGX_E_INVALID_ARGUMENT, "peak_offsets is NULL");
+  if (!peaks && capacity > 0) return fail(MGX_E_INVALID_ARGUMENT, "peaks is NULL with capacity %llu", (unsigned long long)capacity);
+  if (peaks && capacity == 0) return fail(MGX_E_INVALID_ARGUMENT, "peaks is set with capacity 0");
+  mgx_summary_outputs none{};
+  none.struct_size = sizeof(none);
+  const PeakHost pick{params, peak_offsets, peaks, capacity};
+  return summarize_host_impl(p, samples, num_samples, starts, nframes, frame_offsets, nsignals, nullptr, nullptr, &none, nullptr, flux, 1,
+                             &pick);
+}
+
 int mgx_summarize_flux_host(mgx_plan* p, const float* samples, uint64_t num_samples, const uint64_t* starts, uint64_t nframes,
                             const uint64_t* frame_offsets, uint64_t nsignals, const mgx_outputs* outputs, const mgx_aux_outputs* aux,
                             const mgx_summary_outputs* summary, const mgx_delta_summaries* deltas, const mgx_flux_request* flux,
@@ -2287,13 +2368,13 @@ namespace {
 int summarize_host_impl(mgx_plan* p, const float* samples, uint64_t num_samples, const uint64_t* starts, uint64_t nframes,
                         const uint64_t* frame_offsets, uint64_t nsignals, const mgx_outputs* outputs, const mgx_aux_outputs* aux,
                         const mgx_summary_outputs* summary, const mgx_delta_summaries* deltas, const mgx_flux_request* flux,
-                        uint32_t nflux) {
+                        uint32_t nflux, const PeakHost* pick) {
   const mgx_outputs none{};
   mgx::Outputs x;
   DeltaReq q;
   FluxReq fq;
   int rc = check_summary(summary);
-  if (rc || (rc = delta_request(p, deltas, &q)) || (rc = flux_request(p, flux, nflux, nsignals, &fq)) ||
+  if (rc || (rc = delta_request(p, deltas, &q)) || (rc = flux_request(p, flux, nflux, nsignals, &fq, pick != nullptr)) ||
       (rc = make_outputs(p, outputs ? outputs : &none, aux, &x)))
     return rc;
   SummaryFields sf;
@@ -2323,6 +2404,7 @@ int summarize_host_impl(mgx_plan* p, const float* samples, uint64_t num_samples,
       for (uint32_t i = 0; i < q.sf[k].a.nfields; ++i)
         std::fill_n(q.sf[k].a.f[i].dst, nsignals * MGX_NUM_STATS * q.sf[k].a.f[i].width, std::nan(""));
     for (uint32_t i = 0; i < fq.sf.a.nfields; ++i) std::fill_n(fq.sf.a.f[i].dst, nsignals * MGX_NUM_STATS, std::nan(""));
+    if (pick) std::fill_n(pick->peak_offsets, nsignals + 1, (uint64_t)0);
     return MGX_OK;
   }
   if (nsignals == 0 || (a.cols == 0 && !q.any() && !fq.any())) return gather_host_chunked(p, samples, starts, nframes, &x, nullptr);
@@ -2353,13 +2435,18 @@ int summarize_host_impl(mgx_plan* p, const float* samples, uint64_t num_samples,
   }
   // the flux's own buffer: no rows but the carries, and the flux columns of the whole call
   const FluxLayout fl = flux_layout(fq, nframes, nsignals, true, 0);
-  if (fq.any() && p->s_flux_bytes < fl.total) {
+  // behind it, for mgx_onsets_host: the picker's workspace, its offsets and the peaks the caller has room for
+  const uint64_t pick_ws = fl.total, pick_ws_bytes = pick ? mgx::peaks_workspace_bytes(nframes) : 0;
+  const uint64_t pick_off = pick_ws + pick_ws_bytes, pick_off_bytes = pick ? ((nsignals + 1) * 8 + 255) / 256 * 256 : 0;
+  const uint64_t pick_cap = pick && pick->peaks ? std::min(pick->capacity, nframes) : 0;
+  const uint64_t pick_peaks = pick_off + pick_off_bytes, flux_total = pick_peaks + (pick_cap * 8 + 255) / 256 * 256;
+  if (fq.any() && p->s_flux_bytes < flux_total) {
     if (p->s_flux) (void)hipFree(p->s_flux);
     p->s_flux = nullptr;
     p->s_flux_bytes = 0;
-    e = hipMalloc(reinterpret_cast<void**>(&p->s_flux), fl.total);
+    e = hipMalloc(reinterpret_cast<void**>(&p->s_flux), flux_total);
     if (e != hipSuccess) { p->s_flux = nullptr; return hip_fail(e, "hipMalloc(flux columns)"); }
-    p->s_flux_bytes = fl.total;
+    p->s_flux_bytes = flux_total;
   }
   if (fq.any()) {
     e = hipMemcpyAsync(p->s_flux + fl.table, frame_offsets, (nsignals + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, p->s_comp);
@@ -2483,6 +2570,22 @@ int summarize_host_impl(mgx_plan* p, const float* samples, uint64_t num_samples,
       if (fq.r[i].per_frame && frame_offsets[nsignals] > frame_offsets[0])
         e = hipMemcpyAsync(fq.r[i].per_frame + frame_offsets[0], col[i] + frame_offsets[0],
                            (frame_offsets[nsignals] - frame_offsets[0]) * sizeof(float), hipMemcpyDeviceToHost, p->s_comp);
+    if (pick && rc == MGX_OK && e == hipSuccess) {
+      // the picker over the first request's column where it lies, once; the counts and the peaks alone cross back,
+      // the peaks when the counts are known (the stream is synchronised below either way)
+      mgx_peak_outputs po{};
+      po.struct_size = sizeof(po);
+      po.peak_offsets = reinterpret_cast<uint64_t*>(p->s_flux + pick_off);
+      po.peaks = pick_cap > 0 ? reinterpret_cast<uint64_t*>(p->s_flux + pick_peaks) : nullptr;
+      po.capacity = pick_cap;
+      e = mgx::launch_peaks(col[0], nframes, false, reinterpret_cast<const uint64_t*>(p->s_flux + fl.table), nsignals, *pick->params,
+                            po, p->s_flux + pick_ws, p->s_comp);
+      if (e == hipSuccess)
+        e = hipMemcpyAsync(pick->peak_offsets, po.peak_offsets, (nsignals + 1) * 8, hipMemcpyDeviceToHost, p->s_comp);
+      if (e == hipSuccess) e = hipStreamSynchronize(p->s_comp);
+      const uint64_t total = e == hipSuccess ? std::min(pick->peak_offsets[nsignals], pick_cap) : 0;
+      if (total > 0) e = hipMemcpyAsync(pick->peaks, po.peaks, total * 8, hipMemcpyDeviceToHost, p->s_comp);
+    }
   }
   const hipError_t es = hipStreamSynchronize(p->s_comp);
   if (rc) return rc;

@@ -31,6 +31,9 @@
 //   getSignalSummaries(features, signals, hopSize[, {deltaWidth, deltaOrder, flux}]) / getSignalSummariesAsync(...)
 //                                   getBatchSignals' signals pooled per signal on the device: per feature
 //                                   {mean, variance, min, max}, Float64Arrays of signals x width, plus frameOffsets
+//   getSignalOnsets(signals, hopSize, {feature, mode, lag, preMax, postMax, preAvg, postAvg, delta, wait, envelope})
+//   / getSignalOnsetsAsync(...)     the onsets of every signal: the peaks of a feature's spectral flux, picked on
+//                                   the device within each signal; {frameOffsets, onsetOffsets, onsets[, envelope]}
 //   Meyda.signalsFrameStarts(lengths, bufferSize, hopSize)
 //                                   {starts, frameOffsets} of signals stored one after another
 //   Meyda.readWav(wavBytes)         the header: {pcmFormat, channels, sampleRate, sampleFrames, ...}
@@ -477,6 +480,28 @@ class Meyda {
       .then((r) => summaryResult(names, r, c.frameOffsets));
   }
 
+  // The onsets of getBatchSignals' signals: the spectral flux of `feature` (one of getSignalSummaries' flux fields;
+  // mode and lag as there) is the onset envelope, and its peaks are picked on the device within each signal
+  // (include/meyda_gpu.h): buffer t is a candidate when no buffer of [t - preMax, t + postMax] is above it and it is
+  // at least delta above the mean of [t - preAvg, t + postAvg] (each reach 0..64, the signal's first and last
+  // buffers repeated beyond its ends), and the candidates are thinned so that two onsets are more than `wait`
+  // buffers apart. Returns {frameOffsets, onsetOffsets, onsets}: signal s's onsets are
+  // onsets[onsetOffsets[s] .. onsetOffsets[s + 1]), row numbers of the whole corpus (rows as in frameOffsets),
+  // ascending; with envelope: true also `envelope`, the flux per buffer (a Float32Array). Only the onsets (and the
+  // envelope when asked) cross back from the device.
+  getSignalOnsets(signals, hopSize, options) {
+    const o = onsetOptions(options);
+    const c = this._concatSignals(signals, hopSize);
+    return onsetResult(addon.onsetsGather(this._plan(), c.samples, c.starts, c.frameOffsets, o), c.frameOffsets);
+  }
+
+  getSignalOnsetsAsync(signals, hopSize, options) {
+    const o = onsetOptions(options);
+    const c = this._concatSignals(signals, hopSize);
+    return this._runAsync((plan) => addon.onsetsGatherAsync(plan, c.samples, c.starts, c.frameOffsets, o))
+      .then((r) => onsetResult(r, c.frameOffsets));
+  }
+
   _concatSignals(signals, hopSize) {
     const hop = this._checkHop(hopSize);
     if (!Array.isArray(signals)) throw new TypeError('signals must be an array of Float32Arrays');
@@ -742,6 +767,35 @@ function summaryOptions(options) {
     return { field: FLUX_FIELDS[f.feature], mode: FLUX_MODES[mode], lag, perFrame: !!f.perFrame };
   });
   return Object.assign({}, d || {}, { flux });
+}
+
+// getSignalOnsets' options as the addon takes them (the flux in the library's numbers)
+function onsetOptions(options) {
+  if (options === undefined || options === null || typeof options !== 'object') {
+    throw new TypeError('options must be an object: {feature, mode, lag, preMax, postMax, preAvg, postAvg, delta, wait, envelope}');
+  }
+  if (!Object.prototype.hasOwnProperty.call(FLUX_FIELDS, options.feature)) throw new TypeError("'" + options.feature + "' has no flux");
+  const mode = options.mode === undefined ? 'rectified' : options.mode;
+  if (!Object.prototype.hasOwnProperty.call(FLUX_MODES, mode)) throw new RangeError("flux mode must be 'rectified', 'l1' or 'l2'");
+  const lag = options.lag === undefined ? 1 : options.lag;
+  if (!Number.isInteger(lag) || lag < 1 || lag > 8) throw new RangeError('flux lag must be an integer from 1 to 8');
+  const o = { field: FLUX_FIELDS[options.feature], mode: FLUX_MODES[mode], lag, envelope: !!options.envelope };
+  for (const k of ['preMax', 'postMax', 'preAvg', 'postAvg']) {
+    o[k] = options[k] === undefined ? 0 : options[k];
+    if (!Number.isInteger(o[k]) || o[k] < 0 || o[k] > 64) throw new RangeError(k + ' must be an integer from 0 to 64');
+  }
+  o.wait = options.wait === undefined ? 0 : options.wait;
+  if (!Number.isInteger(o.wait) || o.wait < 0 || o.wait > 4294967295) throw new RangeError('wait must be an integer from 0 to 4294967295');
+  o.delta = options.delta === undefined ? 0 : options.delta;
+  if (typeof o.delta !== 'number') throw new TypeError('delta must be a number');
+  if (Number.isNaN(o.delta)) throw new RangeError('delta must not be NaN');
+  return o;
+}
+
+function onsetResult(raw, frameOffsets) {
+  const r = { frameOffsets, onsetOffsets: raw.onsetOffsets, onsets: raw.onsets };
+  if (raw.envelope) r.envelope = raw.envelope;
+  return r;
 }
 
 // getSignalSummaries' options as the addon takes them, or null when no deltas are asked for

@@ -58,7 +58,8 @@ def main():
     matched = set()
     for k in pm:
         name, args = ident(k)
-        nk = next((q for i, q in new_by.items() if i[0] == name and i[1][:len(args)] == args and not any(i[1][len(args):])), None)
+        # (the same mangled name first: the instances of a kernel this file's ident() does not tell apart)
+        nk = k if k in nm else next((q for i, q in new_by.items() if i[0] == name and i[1][:len(args)] == args and not any(i[1][len(args):])), None)
         if nk is None:
             print("%s | %s | (not in the new assembly)" % (show((name, args)), row(pm, po, k)))
             continue
