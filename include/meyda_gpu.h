@@ -37,6 +37,11 @@
  *   mgx_flux_device,     spectral flux: the distance of a row from   no counterpart in this snapshot (one
  *   mgx_summarize_flux_*  an earlier row of its clip, per frame     buffer per call); later Meyda's
  *                        (the onset envelope) and pooled per clip    spectralFlux, Dixon's rectified flux
+ *   mgx_peaks_device,    onsets: the peaks of a clip's envelope,     no counterpart: librosa.util.peak_pick
+ *   mgx_onsets_host      picked on the device                        in a host application
+ *   mgx_chroma_weights,  chroma: the pitch-class profile of every    no counterpart in this snapshot; later
+ *   mgx_chroma_device,   amplitude row (a dense C x N/2 filter       Meyda's chroma (createChromaFilterBank,
+ *   mgx_chroma_host      bank), per frame and pooled per clip        librosa.filters.chroma)
  *   mgx_group_*          several devices, RCCL gather of the        src/meyda.js:17-97 (one plan
  *                        per-frame records to the root device       per device), :69-91 (buffers
  *                                                                   are independent: shardable)
@@ -734,6 +739,99 @@ int mgx_onsets_host(mgx_plan* plan, const float* samples, uint64_t num_samples, 
                     uint64_t num_frames, const uint64_t* frame_offsets, uint64_t num_signals,
                     const mgx_flux_request* flux, const mgx_peak_params* params,
                     uint64_t* peak_offsets, uint64_t* peaks, uint64_t capacity);
+
+/* ---- Chroma: pitch-class profiles of a clip's spectra, per frame and pooled ------------------------
+ * Replaces, in a host application, the product of every buffer's amplitude spectrum with a chroma filter bank
+ * after the spectrum was copied back: later Meyda's `chroma` (src/extractors/chroma.js with
+ * createChromaFilterBank of src/utilities.js, a port of librosa.filters.chroma). The reference snapshot has no
+ * counterpart, so both halves are stated here in full. Chroma, like the statistics, the deltas, the flux and the
+ * peaks, is not a feature: MGX_NUM_FEATURES, the name table and every struct above are as they were.
+ *
+ * The filter bank (mgx_chroma_weights; host only, no device is touched). N = buffer_size, sr = sample_rate,
+ * C = num_chroma; everything in float64, rounded once to float32 at the end (positive stays positive, below). For k = 0 .. N/2:
+ *
+ *   fb(k)  = C log2((k sr / N) / (a440 / 16))  for k >= 1;   fb(0) = fb(1) - 1.5 C
+ *   bw(k)  = max(fb(k + 1) - fb(k), 1)         for k < N/2
+ *   h      = C / 2 rounded to the nearest integer, ties to even
+ *   d(c,k) = ((fb(k) - c + h) mod C) - h       the mod taken in [0, C)
+ *   w(c,k) = exp(-0.5 (2 d / bw(k))^2)
+ *
+ * then (1) every column k is divided by sqrt(sum_c w(c,k)^2); (2) if octave_width > 0 it is multiplied by
+ * exp(-0.5 ((fb(k) / C - center_octave) / octave_width)^2); (3) if base_c, row c of the result is row
+ * (c + 3 (C div 12)) mod C of the table so far (row 0 is C instead of A). Columns 0 .. N/2 - 1 are kept: the bins
+ * the amplitude spectrum has. The one rounding is to the nearest float32, except that a positive value below the
+ * smallest float32 (2^-149) becomes that value and not +0: from C = 15 on the far rows of a narrow bin (bw = 1,
+ * |d| above 7.2: exp(-2 d^2) down to exp(-648) at C = 36) are that small. So every entry is finite and > 0, as the
+ * table is in float64, and under it an overflowed amplitude is +Infinity in every output of its row, not 0 x Inf.
+ * MGX_E_INVALID_ARGUMENT: a NULL pointer, a bad struct_size, C outside 1 .. MGX_CHROMA_MAX_BINS, sample_rate, a440
+ * or octave_width not finite or not positive (octave_width may be 0: no octave weighting).
+ * MGX_E_NOT_POWER_OF_TWO: buffer_size is not a power of two, or is below 4. */
+#define MGX_CHROMA_MAX_BINS 36
+typedef struct mgx_chroma_params {
+  uint32_t struct_size;   /* = sizeof(mgx_chroma_params), 40; anything else: MGX_E_INVALID_ARGUMENT */
+  uint32_t num_chroma;    /* C, 1 .. MGX_CHROMA_MAX_BINS; 12 */
+  double a440;            /* 440 */
+  double center_octave;   /* 5 */
+  double octave_width;    /* 2; 0: no octave weighting */
+  uint32_t base_c;        /* 1: row 0 is C; 0: row 0 is A */
+  uint32_t reserved;
+} mgx_chroma_params;
+void mgx_chroma_params_init(mgx_chroma_params* params);
+int mgx_chroma_weights(uint32_t buffer_size, double sample_rate, const mgx_chroma_params* params,
+                       float* weights /* C x N/2, row-major */);
+
+/* The operator: chroma(t, c) of a row x(t, .) of `cols` float32 values under a bank w of C x cols float32 values.
+ * Values are taken as float64; a product w(c,k) x(k) of two float32 is exact there. Per output c the products are
+ * added in a fixed order: 64 partials P[l] start at +0; for k = 0, 64, 128, ... ascending, P[l] += w(c,k+l) x(k+l)
+ * for the columns that exist, each addition rounded; then P[l] += P[l + h] for l < h, with h = 32, 16, 8, 4, 2, 1;
+ * S(c) = P[0]. MGX_CHROMA_NORM_MAX is Meyda's v / max: m starts at -Infinity; for c ascending, m = S(c) if
+ * S(c) > m (an IEEE comparison: a NaN never becomes m); if m > 0 and m is finite, S(c) = S(c) / m, one correctly
+ * rounded float64 division per output; otherwise the row is left as it is (a silent buffer, a row whose sums are
+ * all <= 0 under a caller's signed bank, an infinite maximum). The result is rounded once to float32. Non-finite
+ * inputs follow IEEE: a NaN or an overflowed amplitude reaches the outputs of its own row only. A partial starts
+ * at +0, so no sum is -0. The bank is the caller's: it may be signed, and its rows need not be pitch classes
+ * (octave bands, a tonnetz projection). Rows are independent: no table of signals, no atomics, and the same bits
+ * from every call below, from a repeated call and from any grid. */
+typedef enum mgx_chroma_norm {
+  MGX_CHROMA_NORM_NONE = 0,
+  MGX_CHROMA_NORM_MAX = 1,
+  MGX_NUM_CHROMA_NORMS = 2
+} mgx_chroma_norm;
+
+/* The operator on device arrays; no plan: asynchronous on `stream`, no allocation, no host-side state,
+ * capturable. rows: num_frames x cols float32; weights: C x cols float32; chroma: num_frames x C float32.
+ * MGX_E_INVALID_ARGUMENT before any launch: cols = 0, C outside 1 .. MGX_CHROMA_MAX_BINS, norm >=
+ * MGX_NUM_CHROMA_NORMS, NULL weights or chroma, chroma equal to rows or to weights, NULL rows with
+ * num_frames > 0. num_frames = 0 returns MGX_OK and writes nothing. */
+int mgx_chroma_device(const float* rows, uint64_t num_frames, uint32_t cols, const float* weights /* device */,
+                      uint32_t num_chroma, uint32_t norm, float* chroma, void* stream);
+
+typedef struct mgx_chroma_request {
+  uint32_t struct_size;  /* = sizeof(mgx_chroma_request), 40; anything else: MGX_E_INVALID_ARGUMENT */
+  uint32_t num_chroma;   /* C */
+  uint32_t norm;         /* mgx_chroma_norm */
+  uint32_t reserved;
+  const float* weights;  /* host, C x N/2 */
+  float* per_frame;      /* num_frames x C, or NULL */
+  double* summary;       /* num_signals x MGX_NUM_STATS x C: mean, variance, min, max per clip, or NULL */
+} mgx_chroma_request;
+
+/* Host pointers throughout: mgx_extract_gather_host with the amplitude spectrum as a field that is laid out in
+ * the staging slot and does not cross back. Behind each chunk's extraction the operator runs over the chunk's
+ * amplitude rows where they lie and writes its rows of a plan-owned num_frames x C float32 array that lasts as
+ * long as the call (grown on demand, freed at mgx_plan_destroy); the weights are uploaded once per call. After the
+ * last chunk per_frame is copied back and, if summary is set, the summary kernels pool the array as one field of
+ * width C keyed by the table: every rule of the summaries holds (blocks of 256 rows from the signal's first row,
+ * NaN in all four for a signal without buffers, no atomics). Only C floats per buffer and the summaries cross
+ * back. The result equals mgx_chroma_device on the amplitude rows mgx_extract_gather_host returns, bit for bit,
+ * wherever the chunks end. The call goes through the staging slots whatever its size and ends a resident
+ * workgroup as any launch does.
+ * The table and the starts are checked as mgx_summarize_host checks them, before any copy; frame_offsets may be
+ * NULL with num_signals = 0 and per_frame alone. MGX_E_INVALID_ARGUMENT also for: summary with num_signals = 0,
+ * both outputs NULL, NULL weights, a bad struct_size, C or norm. */
+int mgx_chroma_host(mgx_plan* plan, const float* samples, uint64_t num_samples, const uint64_t* starts,
+                    uint64_t num_frames, const uint64_t* frame_offsets, uint64_t num_signals,
+                    const mgx_chroma_request* request);
 
 /* ---- Multi-device groups -------------------------------
  * Replaces nothing in the reference (single-threaded browser code); it exists because

@@ -25,6 +25,13 @@
  *                                        -> { onsetOffsets: Float64Array(S + 1), onsets: Float64Array(total)[, envelope:
  *                                           Float32Array(nframes)] }: the peaks of the field's flux within every
  *                                           signal, picked on the device (mgx_onsets_host)
+ *   chromaWeights(bufferSize, sampleRate[, {numChroma, a440, centerOctave, octaveWidth, baseC}])
+ *                                        -> Float32Array(numChroma x bufferSize / 2): the chroma filter bank
+ *                                           (mgx_chroma_weights; host only)
+ *   chromaGather(plan, samples, starts, frameOffsets | null, {weights, numChroma, norm, summary}) / chromaGatherAsync(...)
+ *                                        -> { chroma: Float32Array(nframes x numChroma), numChroma[, summary:
+ *                                           Float64Array(S x 4 x numChroma)] }: the chroma rows of every buffer,
+ *                                           computed on the device from spectra that stay there (mgx_chroma_host)
  *   wavParse(wavBytes)                   -> { pcmFormat, channels, sampleRate, bitsPerSample, ... }
  *   hostTables(opts)                     -> { hanning, hamming, window, barkScale, barkLimits, melBins, dct }
  *   isPowerOfTwo(n), deviceCount(), featureNames(), featureInfo(name), abiVersion()
@@ -301,6 +308,11 @@ typedef struct {
   mgx_peak_params peak;
   uint64_t* peak_offsets;
   uint64_t* peaks;
+  /* chromaGather: a gather job whose output is the chroma rows of every buffer under the caller's bank, and with
+   * the option summary their pooling per signal (mgx_chroma_host); nsignals 0 and no table: the rows alone */
+  int chroma;
+  mgx_chroma_request creq;
+  napi_ref crefs[3];  /* the bank (kept alive), the rows, the summaries */
   mgx_outputs out;
   mgx_aux_outputs aux;  /* melBands (SLOT_MEL): the job then makes the mgx_extract_*_ex call */
   /* The outputs are written straight into JS ArrayBuffers (napi_create_arraybuffer), held by
@@ -328,6 +340,11 @@ static void job_free_buffers(napi_env env, job* j) {
   j->peak_offsets = NULL;
   free(j->peaks);
   j->peaks = NULL;
+  for (int i = 0; i < 3; ++i)
+    if (j->crefs[i]) {
+      napi_delete_reference(env, j->crefs[i]);
+      j->crefs[i] = NULL;
+    }
   for (int i = 0; i < NSLOTS; ++i)
     if (j->refs[i]) {
       napi_delete_reference(env, j->refs[i]);
@@ -748,6 +765,107 @@ static int job_prepare_onsets(napi_env env, job* j, napi_value samples_v, napi_v
   return 1;
 }
 
+/* A property of the options object as a finite double; absent or undefined: *out as it stands. 0 with an error pending. */
+static int option_f64(napi_env env, napi_value obj, const char* name, double* out) {
+  napi_value v;
+  if (!option_given(env, obj, name, &v)) return 1;
+  napi_valuetype t = napi_undefined;
+  double d = 0;
+  napi_typeof(env, v, &t);
+  if (t == napi_number) napi_get_value_double(env, v, &d);
+  if (t != napi_number || d != d || d - d != 0) {
+    char msg[96];
+    snprintf(msg, sizeof msg, "%s must be a finite number", name);
+    napi_throw_range_error(env, NULL, msg);
+    return 0;
+  }
+  *out = d;
+  return 1;
+}
+
+/* chromaGather(plan, samples, starts, frameOffsets, options): extractGather's inputs, the table of the signals'
+ * buffers or null (no signals: the rows alone), and options: {weights: a Float32Array of numChroma x bufferSize / 2,
+ * numChroma, norm = 1 (0 none, 1 max), summary = false}. */
+static int job_prepare_chroma(napi_env env, job* j, napi_value samples_v, napi_value starts_v, napi_value offsets_v,
+                              napi_value options_v) {
+  napi_valuetype ot = napi_undefined;
+  napi_typeof(env, options_v, &ot);
+  if (ot != napi_object) {
+    napi_throw_type_error(env, NULL, "options must be an object: {weights, numChroma, norm, summary}");
+    return 0;
+  }
+  j->chroma = 1;
+  mgx_chroma_request* r = &j->creq;
+  r->struct_size = sizeof *r;
+  if (!option_u32(env, options_v, "numChroma", 1, MGX_CHROMA_MAX_BINS, 12, &r->num_chroma)) return 0;
+  if (!option_u32(env, options_v, "norm", 0, MGX_NUM_CHROMA_NORMS - 1, MGX_CHROMA_NORM_MAX, &r->norm)) return 0;
+  napi_value v, ab;
+  bool want_summary = false, is_ta = false;
+  if (option_given(env, options_v, "summary", &v)) napi_coerce_to_bool(env, v, &v), napi_get_value_bool(env, v, &want_summary);
+  napi_typedarray_type tt = napi_int8_array;
+  size_t len = 0, off = 0, count = 0;
+  void* data = NULL;
+  if (option_given(env, options_v, "weights", &v)) napi_is_typedarray(env, v, &is_ta);
+  if (is_ta) napi_get_typedarray_info(env, v, &tt, &len, &data, &ab, &off);
+  if (!is_ta || tt != napi_float32_array) {
+    napi_throw_type_error(env, NULL, "weights must be a Float32Array");
+    return 0;
+  }
+  if (len != (size_t)r->num_chroma * (j->box->desc.buffer_size / 2)) {
+    napi_throw_range_error(env, NULL, "weights.length must be numChroma x bufferSize / 2");
+    return 0;
+  }
+  if (napi_create_reference(env, v, 1, &j->crefs[0]) != napi_ok) return 0;
+  r->weights = (const float*)data;
+  napi_typeof(env, offsets_v, &ot);
+  if (ot != napi_undefined && ot != napi_null) {
+    j->frame_offsets = u64_of_f64(env, offsets_v, "frameOffsets", &count);
+    if (!j->frame_offsets) return 0;
+    if (count < 1) {
+      napi_throw_range_error(env, NULL, "frameOffsets holds one entry more than there are signals");
+      return 0;
+    }
+    j->nsignals = count - 1;
+  }
+  if (want_summary && j->nsignals == 0) {
+    napi_throw_range_error(env, NULL, "summary needs frameOffsets with a signal");
+    return 0;
+  }
+  is_ta = false;
+  napi_is_typedarray(env, samples_v, &is_ta);
+  if (is_ta) napi_get_typedarray_info(env, samples_v, &tt, &len, &data, &ab, &off);
+  if (!is_ta || tt != napi_float32_array) {
+    napi_throw_type_error(env, NULL, "samples must be a Float32Array");
+    return 0;
+  }
+  if (j->box->group) {
+    napi_throw_error(env, NULL, "starts are not supported on a plan created with `devices`: device groups take dense buffers only");
+    return 0;
+  }
+  j->starts = u64_of_f64(env, starts_v, "starts", &count);
+  if (!j->starts) return 0;
+  j->gather = 1;
+  j->frames = (const float*)data;
+  j->nsamples = len;
+  j->nframes = count;
+  const size_t row_bytes = (size_t)j->nframes * r->num_chroma * sizeof(float);
+  if (napi_create_arraybuffer(env, row_bytes, &data, &ab) != napi_ok || napi_create_reference(env, ab, 1, &j->crefs[1]) != napi_ok) {
+    napi_throw_error(env, NULL, "out of host memory");
+    return 0;
+  }
+  memset(data, 0, row_bytes);
+  r->per_frame = (float*)data;
+  if (want_summary) {
+    if (napi_create_arraybuffer(env, (size_t)j->nsignals * MGX_NUM_STATS * r->num_chroma * sizeof(double), &data, &ab) != napi_ok ||
+        napi_create_reference(env, ab, 1, &j->crefs[2]) != napi_ok) {
+      napi_throw_error(env, NULL, "out of host memory");
+      return 0;
+    }
+    r->summary = (double*)data;
+  }
+  return 1;
+}
+
 /* Field i of a summary (the complex spectrum has none) */
 static void set_summary_field(mgx_summary_outputs* s, int i, double* p) {
   double** const arrays[NSLOTS - SLOT_LOUD] = {&s->loudness_specific, &s->mfcc, &s->amplitude_spectrum, &s->power_spectrum,
@@ -868,7 +986,9 @@ static void job_run(job* j) {
     return;
   }
   const uint32_t n = j->box->desc.buffer_size;
-  if (j->onsets)
+  if (j->chroma)
+    j->rc = mgx_chroma_host(j->box->plan, j->frames, j->nsamples, j->starts, j->nframes, j->frame_offsets, j->nsignals, &j->creq);
+  else if (j->onsets)
     j->rc = mgx_onsets_host(j->box->plan, j->frames, j->nsamples, j->starts, j->nframes, j->frame_offsets, j->nsignals, &j->flux[0],
                             &j->peak, j->peak_offsets, j->nframes ? j->peaks : NULL, j->nframes);
   else if (j->summary && j->num_flux)
@@ -922,6 +1042,17 @@ static napi_value job_result(napi_env env, job* j) {
       "perceptualSharpness"};
   napi_value obj;
   if (napi_create_object(env, &obj) != napi_ok) return NULL;
+  if (j->chroma) {
+    napi_value nc;
+    const size_t C = j->creq.num_chroma;
+    napi_set_named_property(env, obj, "chroma", typed_of(env, j->crefs[1], (size_t)j->nframes * C * sizeof(float), napi_float32_array, 4));
+    if (napi_create_uint32(env, (uint32_t)C, &nc) != napi_ok) return NULL;
+    napi_set_named_property(env, obj, "numChroma", nc);
+    if (j->crefs[2])
+      napi_set_named_property(env, obj, "summary",
+                              typed_of(env, j->crefs[2], (size_t)j->nsignals * MGX_NUM_STATS * C * sizeof(double), napi_float64_array, 8));
+    return obj;
+  }
   if (j->onsets) {  /* the index arrays as signalsFrameStarts returns its own: Float64Arrays */
     const uint64_t total = j->peak_offsets[j->nsignals];
     const uint64_t* const src[2] = {j->peak_offsets, j->peaks};
@@ -988,7 +1119,7 @@ static napi_value job_result(napi_env env, job* j) {
 }
 
 /* kind: the input of an extraction job */
-enum { IN_FRAMES = 0, IN_WAV = 1, IN_SIGNAL = 2, IN_GATHER = 3, IN_SUMMARY = 4, IN_ONSETS = 5 };
+enum { IN_FRAMES = 0, IN_WAV = 1, IN_SIGNAL = 2, IN_GATHER = 3, IN_SUMMARY = 4, IN_ONSETS = 5, IN_CHROMA = 6 };
 
 static int job_prepare_kind(napi_env env, job* j, int kind, size_t argc, napi_value* argv) {
   if (kind == IN_WAV) return job_prepare_wav(env, j, argv[1], argv[2], argc > 3 ? argv[3] : NULL, argc > 4 ? argv[4] : NULL);
@@ -996,6 +1127,7 @@ static int job_prepare_kind(napi_env env, job* j, int kind, size_t argc, napi_va
   if (kind == IN_GATHER) return job_prepare_gather(env, j, argv[1], argv[2], argv[3]);
   if (kind == IN_SUMMARY) return job_prepare_summary(env, j, argv[1], argv[2], argv[3], argv[4], argc > 5 ? argv[5] : NULL);
   if (kind == IN_ONSETS) return job_prepare_onsets(env, j, argv[1], argv[2], argv[3], argv[4]);
+  if (kind == IN_CHROMA) return job_prepare_chroma(env, j, argv[1], argv[2], argv[3], argv[4]);
   return job_prepare(env, j, argv[1], argv[2]);
 }
 
@@ -1003,8 +1135,9 @@ static napi_value extract_common(napi_env env, napi_callback_info info, int kind
   size_t argc = 6;
   napi_value argv[6];
   CHECK(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
-  if (argc < (kind == IN_SUMMARY || kind == IN_ONSETS ? 5u : kind == IN_SIGNAL || kind == IN_GATHER ? 4u : 3u)) {
+  if (argc < (kind == IN_SUMMARY || kind == IN_ONSETS || kind == IN_CHROMA ? 5u : kind == IN_SIGNAL || kind == IN_GATHER ? 4u : 3u)) {
     napi_throw_type_error(env, NULL, kind == IN_WAV ? "extractWav(plan, wavBytes, features[, channel[, hop]])"
+                                   : kind == IN_CHROMA ? "chromaGather(plan, samples, starts, frameOffsets, {weights, numChroma, ...})"
                                    : kind == IN_ONSETS ? "onsetsGather(plan, samples, starts, frameOffsets, {field, ...})"
                                    : kind == IN_SUMMARY ? "summarizeGather(plan, samples, starts, frameOffsets, features[, {deltaWidth, deltaOrder}])"
                                    : kind == IN_GATHER ? "extractGather(plan, samples, starts, features)"
@@ -1129,6 +1262,7 @@ static napi_value extract_signal_sync(napi_env env, napi_callback_info info) { r
 static napi_value extract_gather_sync(napi_env env, napi_callback_info info) { return extract_common(env, info, IN_GATHER); }
 static napi_value summarize_gather_sync(napi_env env, napi_callback_info info) { return extract_common(env, info, IN_SUMMARY); }
 static napi_value onsets_gather_sync(napi_env env, napi_callback_info info) { return extract_common(env, info, IN_ONSETS); }
+static napi_value chroma_gather_sync(napi_env env, napi_callback_info info) { return extract_common(env, info, IN_CHROMA); }
 
 static void async_execute(napi_env env, void* data) {
   (void)env;
@@ -1159,8 +1293,9 @@ static napi_value extract_async_common(napi_env env, napi_callback_info info, in
   size_t argc = 6;
   napi_value argv[6];
   CHECK(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
-  if (argc < (kind == IN_SUMMARY || kind == IN_ONSETS ? 5u : kind == IN_SIGNAL || kind == IN_GATHER ? 4u : 3u)) {
+  if (argc < (kind == IN_SUMMARY || kind == IN_ONSETS || kind == IN_CHROMA ? 5u : kind == IN_SIGNAL || kind == IN_GATHER ? 4u : 3u)) {
     napi_throw_type_error(env, NULL, kind == IN_WAV ? "extractWavAsync(plan, wavBytes, features[, channel[, hop]])"
+                                   : kind == IN_CHROMA ? "chromaGatherAsync(plan, samples, starts, frameOffsets, {weights, numChroma, ...})"
                                    : kind == IN_ONSETS ? "onsetsGatherAsync(plan, samples, starts, frameOffsets, {field, ...})"
                                    : kind == IN_SUMMARY ? "summarizeGatherAsync(plan, samples, starts, frameOffsets, features[, {deltaWidth, deltaOrder}])"
                                    : kind == IN_GATHER ? "extractGatherAsync(plan, samples, starts, features)"
@@ -1198,6 +1333,54 @@ static napi_value extract_signal_async(napi_env env, napi_callback_info info) { 
 static napi_value extract_gather_async(napi_env env, napi_callback_info info) { return extract_async_common(env, info, IN_GATHER); }
 static napi_value summarize_gather_async(napi_env env, napi_callback_info info) { return extract_async_common(env, info, IN_SUMMARY); }
 static napi_value onsets_gather_async(napi_env env, napi_callback_info info) { return extract_async_common(env, info, IN_ONSETS); }
+static napi_value chroma_gather_async(napi_env env, napi_callback_info info) { return extract_async_common(env, info, IN_CHROMA); }
+
+/* chromaWeights(bufferSize, sampleRate[, {numChroma, a440, centerOctave, octaveWidth, baseC}]): the chroma filter
+ * bank (mgx_chroma_weights; host only), a Float32Array of numChroma x bufferSize / 2, row-major. */
+static napi_value chroma_weights(napi_env env, napi_callback_info info) {
+  size_t argc = 3;
+  napi_value argv[3];
+  CHECK(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  double n = 0, sr = 0;
+  napi_valuetype t0 = napi_undefined, t1 = napi_undefined, ot = napi_undefined;
+  if (argc >= 2) napi_typeof(env, argv[0], &t0), napi_typeof(env, argv[1], &t1);
+  if (t0 != napi_number || t1 != napi_number) {
+    napi_throw_type_error(env, NULL, "chromaWeights(bufferSize, sampleRate[, {numChroma, a440, centerOctave, octaveWidth, baseC}])");
+    return NULL;
+  }
+  napi_get_value_double(env, argv[0], &n);
+  napi_get_value_double(env, argv[1], &sr);
+  if (!(n >= 0) || n > 4294967295.0 || n != (double)(uint32_t)n) {
+    napi_throw_range_error(env, NULL, "bufferSize must be a non-negative integer");
+    return NULL;
+  }
+  mgx_chroma_params p;
+  mgx_chroma_params_init(&p);
+  if (argc > 2) napi_typeof(env, argv[2], &ot);
+  if (ot == napi_object) {
+    napi_value v;
+    bool b = true;
+    if (!option_u32(env, argv[2], "numChroma", 1, MGX_CHROMA_MAX_BINS, 12, &p.num_chroma)) return NULL;
+    if (!option_f64(env, argv[2], "a440", &p.a440) || !option_f64(env, argv[2], "centerOctave", &p.center_octave) ||
+        !option_f64(env, argv[2], "octaveWidth", &p.octave_width))
+      return NULL;
+    if (option_given(env, argv[2], "baseC", &v)) napi_coerce_to_bool(env, v, &v), napi_get_value_bool(env, v, &b);
+    p.base_c = b ? 1 : 0;
+  } else if (ot != napi_undefined && ot != napi_null) {
+    napi_throw_type_error(env, NULL, "options must be an object: {numChroma, a440, centerOctave, octaveWidth, baseC}");
+    return NULL;
+  }
+  /* (a size the library refuses may leave nothing to point at: it checks the size before it writes) */
+  const int pow2 = (uint32_t)n >= 4 && ((uint32_t)n & ((uint32_t)n - 1)) == 0;
+  const size_t count = pow2 ? (size_t)p.num_chroma * ((uint32_t)n / 2) : 1;
+  napi_value ab, ta;
+  void* data = NULL;
+  CHECK(napi_create_arraybuffer(env, count * sizeof(float), &data, &ab));
+  const int rc = mgx_chroma_weights((uint32_t)n, sr, &p, (float*)data);
+  if (rc) return throw_mgx(env, rc);
+  CHECK(napi_create_typedarray(env, napi_float32_array, count, ab, 0, &ta));
+  return ta;
+}
 
 /* signalsFrameStarts(lengths, bufferSize, hop): mgx_signals_frame_starts (host only) for signals stored one after
  * another; lengths: a Float64Array. Returns {starts, frameOffsets}, Float64Arrays. */
@@ -1430,6 +1613,9 @@ static napi_value init(napi_env env, napi_value exports) {
       {"summarizeGatherAsync", NULL, summarize_gather_async, NULL, NULL, NULL, napi_enumerable, NULL},
       {"onsetsGather", NULL, onsets_gather_sync, NULL, NULL, NULL, napi_enumerable, NULL},
       {"onsetsGatherAsync", NULL, onsets_gather_async, NULL, NULL, NULL, napi_enumerable, NULL},
+      {"chromaGather", NULL, chroma_gather_sync, NULL, NULL, NULL, napi_enumerable, NULL},
+      {"chromaGatherAsync", NULL, chroma_gather_async, NULL, NULL, NULL, napi_enumerable, NULL},
+      {"chromaWeights", NULL, chroma_weights, NULL, NULL, NULL, napi_enumerable, NULL},
       {"signalsFrameStarts", NULL, signals_frame_starts, NULL, NULL, NULL, napi_enumerable, NULL},
       {"wavParse", NULL, wav_parse, NULL, NULL, NULL, napi_enumerable, NULL},
       {"hostTables", NULL, host_tables, NULL, NULL, NULL, napi_enumerable, NULL},

@@ -43,6 +43,7 @@ EXPORTS = ["mgx_plan_desc_init", "mgx_plan_create", "mgx_plan_destroy", "mgx_pla
            "mgx_summarize_deltas_host",
            "mgx_flux_device", "mgx_summarize_flux_workspace_bytes", "mgx_summarize_flux_device", "mgx_summarize_flux_host",
            "mgx_peaks_workspace_bytes", "mgx_peaks_device", "mgx_onsets_host",
+           "mgx_chroma_params_init", "mgx_chroma_weights", "mgx_chroma_device", "mgx_chroma_host",
            "mgx_shard_range", "mgx_packed_layout", "mgx_comm_unique_id", "mgx_group_create",
            "mgx_group_create_rank", "mgx_group_create_loopback", "mgx_group_create_loopback_rccl", "mgx_group_destroy",
            "mgx_group_info", "mgx_group_comm_info", "mgx_group_extract_device", "mgx_group_extract_host"]
@@ -167,6 +168,46 @@ def peak_params(pre_max=0, post_max=0, pre_avg=0, post_avg=0, delta=0.0, wait=0)
     return p
 
 
+CHROMA_MAX_BINS = 36  # MGX_CHROMA_MAX_BINS
+CHROMA_NORMS = {"none": 0, "max": 1}  # mgx_chroma_norm
+CHROMA_PARAMS = ("num_chroma", "a440", "center_octave", "octave_width", "base_c")
+
+
+class ChromaParams(ctypes.Structure):
+    """mgx_chroma_params: the construction of the chroma filter bank (mgx_chroma_weights)."""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("num_chroma", ctypes.c_uint32), ("a440", ctypes.c_double),
+                ("center_octave", ctypes.c_double), ("octave_width", ctypes.c_double), ("base_c", ctypes.c_uint32),
+                ("reserved", ctypes.c_uint32)]
+
+
+class ChromaRequest(ctypes.Structure):
+    """mgx_chroma_request: what mgx_chroma_host computes and where it goes (host pointers)."""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("num_chroma", ctypes.c_uint32), ("norm", ctypes.c_uint32),
+                ("reserved", ctypes.c_uint32), ("weights", ctypes.c_void_p), ("per_frame", ctypes.c_void_p),
+                ("summary", ctypes.c_void_p)]
+
+
+def chroma_params(**params):
+    """A ChromaParams with the library's defaults (mgx_chroma_params_init) and `params` over them; numbers out of
+    range pass through: the library refuses them with its message."""
+    for k in params:
+        if k not in CHROMA_PARAMS:
+            raise TypeError("chroma parameter %r: one of %s" % (k, ", ".join(CHROMA_PARAMS)))
+    p = ChromaParams()
+    lib().mgx_chroma_params_init(ctypes.byref(p))
+    for k, v in params.items():
+        setattr(p, k, int(v) if k in ("num_chroma", "base_c") else float(v))
+    return p
+
+
+def _chroma_norm(norm):
+    if isinstance(norm, str):
+        if norm not in CHROMA_NORMS:
+            raise ValueError("chroma norm %r: one of %s" % (norm, sorted(CHROMA_NORMS)))
+        return CHROMA_NORMS[norm]
+    return int(norm)
+
+
 class HostTables(ctypes.Structure):
     _fields_ = [("window", ctypes.c_void_p), ("hanning", ctypes.c_void_p),
                 ("hamming", ctypes.c_void_p), ("bark_scale", ctypes.c_void_p),
@@ -288,6 +329,13 @@ def lib():
         L.mgx_onsets_host.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64,
                                       ctypes.c_void_p, ctypes.c_uint64, freq, ctypes.POINTER(PeakParams), ctypes.c_void_p,
                                       ctypes.c_void_p, ctypes.c_uint64]
+        L.mgx_chroma_params_init.argtypes = [ctypes.POINTER(ChromaParams)]
+        L.mgx_chroma_params_init.restype = None
+        L.mgx_chroma_weights.argtypes = [ctypes.c_uint32, ctypes.c_double, ctypes.POINTER(ChromaParams), ctypes.c_void_p]
+        L.mgx_chroma_device.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint32,
+                                        ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p]
+        L.mgx_chroma_host.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64,
+                                      ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(ChromaRequest)]
         L.mgx_shard_range.argtypes = [ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, u64p, u64p]
         L.mgx_packed_layout.argtypes = [ctypes.POINTER(PlanDesc), ctypes.c_uint32, ctypes.c_uint64, u64p]
         L.mgx_packed_layout.restype = ctypes.c_uint64
@@ -772,6 +820,51 @@ class Plan:
             res["summary"] = fres[0]["summary"]
         return res
 
+    def chroma(self, samples, starts, frame_offsets=None, weights=None, norm="max", per_frame=True, summary=False, **params):
+        """Host numpy in / numpy out (mgx_chroma_host): the chroma rows of the buffers at `starts` under `weights`
+        (a (C, N/2) float32 bank; None: chroma_weights of the plan's size and sample rate with `params`), computed
+        on the device from amplitude rows that never cross back. Returns a dict: "chroma" ((F, C) float32) with
+        per_frame, "summary" ((S, 4, C) float64: mean, variance, min, max per signal) with summary, which needs
+        frame_offsets, and "weights"."""
+        samples = np.ascontiguousarray(samples, dtype=np.float32)
+        starts = np.ascontiguousarray(starts, dtype=np.uint64)
+        assert samples.ndim == 1 and starts.ndim == 1
+        S = 0
+        if frame_offsets is not None:
+            frame_offsets = np.ascontiguousarray(frame_offsets, dtype=np.uint64)
+            assert frame_offsets.ndim == 1 and frame_offsets.size >= 1
+            S = frame_offsets.size - 1
+        if weights is None:
+            weights = chroma_weights(self.n, self.desc.sample_rate, **params)
+        elif params:
+            raise TypeError("chroma parameters are given with weights=None")
+        weights = np.ascontiguousarray(weights, dtype=np.float32)
+        assert weights.ndim == 2 and weights.shape[1] == self.n // 2
+        C = weights.shape[0]
+        req = ChromaRequest()
+        req.struct_size = ctypes.sizeof(ChromaRequest)
+        req.num_chroma, req.norm, req.weights = C, _chroma_norm(norm), weights.ctypes.data
+        res = {"weights": weights}
+        if per_frame:
+            res["chroma"] = np.zeros((starts.size, C), np.float32)
+            req.per_frame = res["chroma"].ctypes.data
+        if summary:
+            res["summary"] = np.empty((S, len(STATS), C), np.float64)
+            req.summary = res["summary"].ctypes.data
+        check(lib().mgx_chroma_host(self._h, samples.ctypes.data, samples.size, starts.ctypes.data, starts.size,
+                                    None if frame_offsets is None else frame_offsets.ctypes.data, S, ctypes.byref(req)))
+        return res
+
+    def chroma_signals(self, signals, hop, **kw):
+        """A list of 1-D host signals in one call (Plan.chroma over signals_frame_starts of their lengths): the
+        dict Plan.chroma returns, with "frame_offsets"."""
+        signals = [np.ascontiguousarray(x, dtype=np.float32).ravel() for x in signals]
+        starts, frame_offsets = signals_frame_starts([x.size for x in signals], self.n, hop)
+        samples = np.concatenate(signals) if signals else np.empty(0, np.float32)
+        res = self.chroma(samples, starts, frame_offsets, **kw)
+        res["frame_offsets"] = frame_offsets
+        return res
+
     def summarize_signals(self, signals, hop, features, per_frame=(), deltas=None, flux=None):
         """A list of 1-D host signals in one call, pooled per signal: returns (summaries, frame_offsets), summaries
         being {name: ndarray (S, 4, width)} of mean, variance, min, max (STATS) over each signal's buffers; with
@@ -1149,3 +1242,41 @@ def peaks_torch(envelope, frame_offsets=None, capacity=None, starts=None, stream
     peaks_device(envelope.data_ptr(), F, envelope.dtype == torch.float64, None if frame_offsets is None else frame_offsets.data_ptr(),
                  S, peak_params(**params), o, ws.data_ptr(), nbytes, stream)
     return (mask, offsets, peaks) if starts is None else (mask, offsets, peaks, peak_starts)
+
+
+def chroma_weights(n, sample_rate, **params):
+    """mgx_chroma_weights (host only): the (C, n/2) float32 chroma filter bank of librosa.filters.chroma for buffers
+    of n samples; params: num_chroma (12), a440 (440), center_octave (5), octave_width (2; 0: none), base_c (True)."""
+    p = chroma_params(**params)
+    w = np.zeros((max(int(p.num_chroma), 0), max(int(n) // 2, 0)), np.float32)
+    # (a refused size or C may leave nothing to point at: the library checks them before it writes)
+    buf = w if w.size else np.zeros(1, np.float32)
+    check(lib().mgx_chroma_weights(int(n), float(sample_rate), ctypes.byref(p), buf.ctypes.data))
+    return w
+
+
+def chroma_device(rows_ptr, num_frames, cols, weights_ptr, num_chroma, norm, chroma_ptr, stream=None):
+    """mgx_chroma_device on device pointers (async on `stream`); a pointer may be None."""
+    check(lib().mgx_chroma_device(ctypes.c_void_p(rows_ptr or 0), num_frames, cols, ctypes.c_void_p(weights_ptr or 0),
+                                  num_chroma, norm, ctypes.c_void_p(chroma_ptr or 0), ctypes.c_void_p(stream or 0)))
+
+
+def chroma_torch(rows, weights, norm="max", stream=None, out=None):
+    """The chroma rows of `rows`, a (F, cols) float32 CUDA tensor, under `weights`, a (C, cols) float32 CUDA tensor
+    (or anything numpy turns into one): the products added in the fixed order of include/meyda_gpu.h, then divided
+    by the row's maximum (norm "max") or left as they are ("none"). Returns a (F, C) float32 tensor (`out` when given)."""
+    import torch
+    assert rows.is_cuda and rows.is_contiguous() and rows.dim() == 2 and rows.dtype == torch.float32
+    if not torch.is_tensor(weights):
+        weights = torch.from_numpy(np.ascontiguousarray(weights, dtype=np.float32)).to(rows.device)
+    assert weights.is_cuda and weights.is_contiguous() and weights.dim() == 2 and weights.dtype == torch.float32
+    F, cols = rows.shape
+    C = weights.shape[0]
+    assert weights.shape[1] == cols
+    if out is None:
+        out = torch.zeros((F, C), dtype=torch.float32, device=rows.device)
+    assert out.is_cuda and out.is_contiguous() and out.dtype == torch.float32 and out.shape == (F, C)
+    if stream is None:
+        stream = torch.cuda.current_stream(rows.device).cuda_stream
+    chroma_device(rows.data_ptr(), F, cols, weights.data_ptr(), C, _chroma_norm(norm), out.data_ptr(), stream)
+    return out

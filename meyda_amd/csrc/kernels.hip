@@ -3849,6 +3849,158 @@ hipError_t launch_peaks(const void* env, uint64_t num_frames, bool f64, const ui
   return hipGetLastError();
 }
 
+// ---- Chroma (mgx_chroma_device, mgx_chroma_host): a dense C x cols bank applied to every row ----
+// A wave takes R consecutive rows at a time (4 for C <= 16, else 2) and lane l owns the partials P[l] of the
+// definition (include/meyda_gpu.h) of all R x C sums: per 64 columns one 256-byte load per row and one value of
+// each of the C bank rows, shared by the R rows, then R x C float64 FMAs (the product of two float32 is exact in
+// float64, so the FMA rounds exactly what the definition's addition rounds). The bank is staged in LDS once per
+// workgroup when it fits kChromaLdsBytes (12 x 512: 24 KB) and read from there by every wave for every row; a
+// larger one (36 x 2048: 288 KB) is read through L1 / L2 instead. The definition's halvings run over all C
+// partial vectors together (ChromaFold): at distance h a pair of vectors (a, b) becomes one, lanes without bit
+// h keeping a and lanes with it b, each adding what the lane at distance h holds of the same vector -- the sums
+// P[l] + P[l + h] of both, one cross-lane move per pair instead of two; an odd vector out is folded alone. After
+// the six distances one register holds every S(c), c a function of the lane alone (found once per kernel by
+// folding the indices the same way), so C vectors cost about C + 6 moves instead of 6 C. IEEE addition is
+// commutative, so the lane that adds P[l + h] + P[l] gets the bits of P[l] + P[l + h]. The maximum of
+// MGX_CHROMA_NORM_MAX is a wave maximum with NaN taken as -Infinity: the value the definition's ascending scan
+// ends with; the division is the compiler's correctly rounded float64 one. No atomics; one writer per output;
+// nothing depends on the grid.
+namespace {
+
+constexpr uint32_t kChromaLdsBytes = 64 * 1024;
+constexpr uint32_t kChromaBlocks = 2048;  // at most: 8 workgroups a CU, each staging the bank once
+
+struct ChromaArgs {
+  const float* rows;
+  const float* weights;
+  float* out;
+  uint64_t num_frames, ngroups;
+  uint32_t cols, norm, lds;
+};
+
+template <int C>
+constexpr int chroma_rows() { return C <= 16 ? 4 : 2; }
+
+template <int N, int H>
+struct ChromaFold {
+  template <typename T, typename Pair, typename Alone>
+  static __device__ __forceinline__ T run(const T (&v)[N], uint32_t lane, Pair pair, Alone alone) {
+    constexpr int M = (N + 1) / 2;
+    T u[M];
+    const bool hi = (lane & H) != 0;
+#pragma unroll
+    for (int i = 0; i < N / 2; ++i) u[i] = pair(v[2 * i], v[2 * i + 1], hi, H);
+    if (N & 1) u[M - 1] = alone(v[N - 1], hi, H);
+    return ChromaFold<M, H / 2>::run(u, lane, pair, alone);
+  }
+};
+template <int N>
+struct ChromaFold<N, 0> {
+  static_assert(N == 1, "six halvings fold at most 64 vectors into one");
+  template <typename T, typename Pair, typename Alone>
+  static __device__ __forceinline__ T run(const T (&v)[N], uint32_t, Pair, Alone) { return v[0]; }
+};
+
+constexpr int kChromaCopy = 0x100;  // on a lane's index: another lane writes this output
+
+template <int C>
+__global__ __launch_bounds__(256) void chroma_kernel(ChromaArgs g) {
+  extern __shared__ float chroma_bank[];
+  constexpr int R = chroma_rows<C>();
+  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6, cols = g.cols;
+  if (g.lds) {
+    for (uint32_t i = threadIdx.x; i < (uint32_t)C * cols; i += 256) chroma_bank[i] = g.weights[i];
+    __syncthreads();
+  }
+  // which output this lane holds after the fold, and whether it is the lane that writes it
+  int idx[C];
+#pragma unroll
+  for (int c = 0; c < C; ++c) idx[c] = c;
+  const int mine = ChromaFold<C, 32>::run(
+      idx, lane, [](int a, int b, bool hi, int) { return hi ? b : a; },
+      [](int a, bool hi, int) { return hi ? a | kChromaCopy : a; });
+  const bool writer = !(mine & kChromaCopy);
+  const uint32_t my_c = (uint32_t)(mine & (kChromaCopy - 1));
+  for (uint64_t grp = (uint64_t)blockIdx.x * 4 + wave; grp < g.ngroups; grp += (uint64_t)gridDim.x * 4) {
+    const uint64_t r0 = grp * R;
+    const float* __restrict__ x[R];
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      // (a row past the last repeats it and is not written)
+      const uint64_t row = r0 + r < g.num_frames ? r0 + r : g.num_frames - 1;
+      x[r] = g.rows + row * cols;
+    }
+    double acc[R][C];
+#pragma unroll
+    for (int r = 0; r < R; ++r)
+#pragma unroll
+      for (int c = 0; c < C; ++c) acc[r][c] = 0.0;
+    auto sweep = [&](const float* __restrict__ w) {
+      for (uint64_t k = lane; k < cols; k += 64) {
+        double xv[R];
+#pragma unroll
+        for (int r = 0; r < R; ++r) xv[r] = (double)x[r][k];
+#pragma unroll
+        for (int c = 0; c < C; ++c) {
+          const double wv = (double)w[(uint64_t)c * cols + k];
+#pragma unroll
+          for (int r = 0; r < R; ++r) acc[r][c] = __builtin_fma(wv, xv[r], acc[r][c]);
+        }
+      }
+    };
+    if (g.lds) sweep(chroma_bank);
+    else sweep(g.weights);
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      double s = ChromaFold<C, 32>::run(
+          acc[r], lane,
+          [](double a, double b, bool hi, int h) {
+            const double keep = hi ? b : a, send = hi ? a : b;
+            return keep + __shfl_xor(send, h);
+          },
+          [](double a, bool, int h) { return a + __shfl_xor(a, h); });
+      if (g.norm == MGX_CHROMA_NORM_MAX) {
+        double m = s == s ? s : -HUGE_VAL;
+#pragma unroll
+        for (int h = 32; h >= 1; h >>= 1) m = fmax(m, __shfl_xor(m, h));
+        if (m > 0.0 && m < HUGE_VAL) s = s / m;
+      }
+      if (writer && r0 + r < g.num_frames) g.out[(r0 + r) * C + my_c] = (float)s;
+    }
+  }
+}
+
+template <int C>
+hipError_t launch_chroma_c(const ChromaArgs& g, unsigned grid, size_t lds, hipStream_t stream, uint32_t num_chroma) {
+  if (num_chroma != (uint32_t)C) return launch_chroma_c<C - 1>(g, grid, lds, stream, num_chroma);
+  ChromaArgs a = g;
+  a.ngroups = (g.num_frames + chroma_rows<C>() - 1) / chroma_rows<C>();
+  const uint64_t blocks = (a.ngroups + 3) / 4;
+  hipLaunchKernelGGL((chroma_kernel<C>), dim3((unsigned)(blocks < grid ? blocks : grid)), dim3(256), lds, stream, a);
+  return hipGetLastError();
+}
+template <>
+hipError_t launch_chroma_c<0>(const ChromaArgs&, unsigned, size_t, hipStream_t, uint32_t) { return hipErrorInvalidValue; }
+
+}  // namespace
+
+hipError_t launch_chroma(const float* rows, uint64_t num_frames, uint32_t cols, const float* weights, uint32_t num_chroma,
+                         uint32_t norm, float* out, hipStream_t stream) {
+  if (num_frames == 0) return hipSuccess;
+  if (cols == 0 || num_chroma == 0 || num_chroma > MGX_CHROMA_MAX_BINS || norm >= MGX_NUM_CHROMA_NORMS || !rows || !weights || !out)
+    return hipErrorInvalidValue;
+  ChromaArgs g{};
+  g.rows = rows;
+  g.weights = weights;
+  g.out = out;
+  g.num_frames = num_frames;
+  g.cols = cols;
+  g.norm = norm;
+  const uint64_t bank = (uint64_t)num_chroma * cols * sizeof(float);
+  g.lds = bank <= kChromaLdsBytes;
+  return launch_chroma_c<MGX_CHROMA_MAX_BINS>(g, kChromaBlocks, g.lds ? (size_t)bank : 0, stream, num_chroma);
+}
+
 }  // namespace mgx
 
 #if MGX_WAVE_TIMES

@@ -250,6 +250,11 @@ struct PeakLayout {
 uint64_t peaks_workspace_bytes(uint64_t num_frames, PeakLayout* l = nullptr);
 hipError_t launch_peaks(const void* env, uint64_t num_frames, bool f64, const uint64_t* table, uint64_t num_signals,
                         const mgx_peak_params& p, const mgx_peak_outputs& o, void* workspace, hipStream_t stream);
+// Chroma (mgx_chroma_device, mgx_chroma_host; kernels.hip chroma_kernel): out[t * num_chroma + c] = the sum over
+// the cols columns of weights[c * cols + k] * rows[t * cols + k] in the definition's order, divided by the row's
+// maximum under MGX_CHROMA_NORM_MAX. All three are float32 arrays in device memory. One launch, asynchronous.
+hipError_t launch_chroma(const float* rows, uint64_t num_frames, uint32_t cols, const float* weights, uint32_t num_chroma,
+                         uint32_t norm, float* out, hipStream_t stream);
 size_t extract_lds_bytes(int n, int ncoef, int nfilt, bool chain);
 size_t lds_image_bytes(int n, int ncoef, int nfilt);  // DevTables::lds_image, a multiple of 16
 hipError_t launch_lds_image(int n, int precision, int mode, const KernelArgs& a, void* image, hipStream_t stream);

@@ -17,6 +17,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <functional>
+#include <limits>
 #include <string>
 #include <vector>
 
@@ -501,6 +502,10 @@ struct mgx_plan {
   // them the picker's workspace, its offsets and the peaks the caller has room for
   unsigned char* s_flux = nullptr;
   size_t s_flux_bytes = 0;
+  // mgx_chroma_host: the bank, the chroma rows of the whole call, then a table, shifts, partials and summaries (one
+  // allocation, grown when a call needs more)
+  unsigned char* s_chroma = nullptr;
+  size_t s_chroma_bytes = 0;
   hipStream_t s_copy = nullptr, s_comp = nullptr;
   hipEvent_t ev_loaded[2] = {nullptr, nullptr}, ev_done[2] = {nullptr, nullptr}, ev_back[2] = {nullptr, nullptr};
   // small host batches (kSmallBatchFrames): pinned, device-mapped, coherent host buffers
@@ -853,6 +858,7 @@ int mgx_plan_destroy(mgx_plan* p) {
   if (p->s_sum) (void)hipFree(p->s_sum);
   if (p->s_delta) (void)hipFree(p->s_delta);
   if (p->s_flux) (void)hipFree(p->s_flux);
+  if (p->s_chroma) (void)hipFree(p->s_chroma);
   if (p->s_copy) (void)hipStreamDestroy(p->s_copy);
   if (p->s_comp) (void)hipStreamDestroy(p->s_comp);
   if (p->s_res) (void)hipStreamDestroy(p->s_res);
@@ -2597,6 +2603,186 @@ int summarize_host_impl(mgx_plan* p, const float* samples, uint64_t num_samples,
 
 extern "C" {
 
+void mgx_chroma_params_init(mgx_chroma_params* c) {
+  if (!c) return;
+  memset(c, 0, sizeof *c);
+  c->struct_size = sizeof *c;
+  c->num_chroma = 12;
+  c->a440 = 440.0;
+  c->center_octave = 5.0;
+  c->octave_width = 2.0;
+  c->base_c = 1;
+}
+
+// The construction of librosa.filters.chroma as include/meyda_gpu.h states it: float64 throughout, one rounding
+int mgx_chroma_weights(uint32_t buffer_size, double sample_rate, const mgx_chroma_params* c, float* weights) {
+  if (!c) return fail(MGX_E_INVALID_ARGUMENT, "params is NULL");
+  if (c->struct_size != sizeof(mgx_chroma_params))
+    return fail(MGX_E_INVALID_ARGUMENT, "mgx_chroma_params.struct_size is %u, expected %zu", c->struct_size, sizeof(mgx_chroma_params));
+  if (!weights) return fail(MGX_E_INVALID_ARGUMENT, "weights is NULL");
+  if (c->num_chroma < 1 || c->num_chroma > MGX_CHROMA_MAX_BINS)
+    return fail(MGX_E_INVALID_ARGUMENT, "mgx_chroma_params.num_chroma is %u, expected 1..%d", c->num_chroma, MGX_CHROMA_MAX_BINS);
+  if (!(std::isfinite(sample_rate) && sample_rate > 0)) return fail(MGX_E_INVALID_ARGUMENT, "sample_rate must be finite and positive");
+  if (!(std::isfinite(c->a440) && c->a440 > 0)) return fail(MGX_E_INVALID_ARGUMENT, "mgx_chroma_params.a440 must be finite and positive");
+  if (!(std::isfinite(c->octave_width) && c->octave_width >= 0))
+    return fail(MGX_E_INVALID_ARGUMENT, "mgx_chroma_params.octave_width must be finite and not negative");
+  if (!std::isfinite(c->center_octave)) return fail(MGX_E_INVALID_ARGUMENT, "mgx_chroma_params.center_octave must be finite");
+  if (buffer_size < 4 || (buffer_size & (buffer_size - 1)) != 0)
+    return fail(MGX_E_NOT_POWER_OF_TWO, "Buffer size is not a power of two of at least 4: %u", buffer_size);
+  const uint32_t C = c->num_chroma, K = buffer_size / 2;
+  const double Cd = (double)C, n = (double)buffer_size;
+  std::vector<double> fb((size_t)K + 1);
+  for (uint32_t k = 1; k <= K; ++k) fb[k] = Cd * std::log2(((double)k * sample_rate / n) / (c->a440 / 16.0));
+  fb[0] = fb[1] - 1.5 * Cd;
+  const double h = std::nearbyint(Cd / 2.0);  // (the default rounding mode: ties to even)
+  const uint32_t roll = c->base_c ? 3 * (C / 12) : 0;
+  std::vector<double> col(C);
+  for (uint32_t k = 0; k < K; ++k) {
+    const double bw = std::max(fb[k + 1] - fb[k], 1.0);
+    double ss = 0.0;
+    for (uint32_t i = 0; i < C; ++i) {
+      double m = std::fmod(fb[k] - (double)i + h, Cd);  // exact; the sign of the dividend
+      if (m < 0) m += Cd;
+      const double d = m - h, t = 2.0 * d / bw;
+      col[i] = std::exp(-0.5 * (t * t));
+      ss += col[i] * col[i];
+    }
+    const double norm = std::sqrt(ss);
+    double oct = 1.0;
+    if (c->octave_width > 0) {
+      const double u = (fb[k] / Cd - c->center_octave) / c->octave_width;
+      oct = std::exp(-0.5 * (u * u));
+    }
+    for (uint32_t i = 0; i < C; ++i) {
+      double v = col[(i + roll) % C] / norm;
+      if (c->octave_width > 0) v *= oct;
+      // the one rounding; a positive value below the smallest float32 takes that value instead of +0, so the table
+      // stays strictly positive as it is in float64 (a zero weight would turn an overflowed amplitude into NaN)
+      const float f = (float)v;
+      weights[(size_t)i * K + k] = v > 0.0 && f == 0.0f ? std::numeric_limits<float>::denorm_min() : f;
+    }
+  }
+  return MGX_OK;
+}
+
+int mgx_chroma_device(const float* rows, uint64_t num_frames, uint32_t cols, const float* weights, uint32_t num_chroma, uint32_t norm,
+                      float* chroma, void* stream) {
+  if (cols == 0) return fail(MGX_E_INVALID_ARGUMENT, "cols is 0");
+  if (num_chroma < 1 || num_chroma > MGX_CHROMA_MAX_BINS)
+    return fail(MGX_E_INVALID_ARGUMENT, "num_chroma is %u, expected 1..%d", num_chroma, MGX_CHROMA_MAX_BINS);
+  if (norm >= MGX_NUM_CHROMA_NORMS) return fail(MGX_E_INVALID_ARGUMENT, "norm is %u, expected 0..%d", norm, MGX_NUM_CHROMA_NORMS - 1);
+  if (!weights) return fail(MGX_E_INVALID_ARGUMENT, "weights is NULL");
+  if (!chroma) return fail(MGX_E_INVALID_ARGUMENT, "chroma is NULL");
+  if (chroma == rows || chroma == weights) return fail(MGX_E_INVALID_ARGUMENT, "chroma is the same array as %s", chroma == rows ? "rows" : "weights");
+  if (num_frames > 0 && !rows) return fail(MGX_E_INVALID_ARGUMENT, "rows is NULL");
+  if (num_frames == 0) return MGX_OK;
+  const hipError_t e = mgx::launch_chroma(rows, num_frames, cols, weights, num_chroma, norm, chroma, (hipStream_t)stream);
+  return e == hipSuccess ? MGX_OK : hip_fail(e, "chroma kernel launch");
+}
+
+int mgx_chroma_host(mgx_plan* p, const float* samples, uint64_t num_samples, const uint64_t* starts, uint64_t nframes,
+                    const uint64_t* frame_offsets, uint64_t nsignals, const mgx_chroma_request* req) {
+  if (!req) return fail(MGX_E_INVALID_ARGUMENT, "request is NULL");
+  if (req->struct_size != sizeof(mgx_chroma_request))
+    return fail(MGX_E_INVALID_ARGUMENT, "mgx_chroma_request.struct_size is %u, expected %zu", req->struct_size, sizeof(mgx_chroma_request));
+  if (req->num_chroma < 1 || req->num_chroma > MGX_CHROMA_MAX_BINS)
+    return fail(MGX_E_INVALID_ARGUMENT, "mgx_chroma_request.num_chroma is %u, expected 1..%d", req->num_chroma, MGX_CHROMA_MAX_BINS);
+  if (req->norm >= MGX_NUM_CHROMA_NORMS)
+    return fail(MGX_E_INVALID_ARGUMENT, "mgx_chroma_request.norm is %u, expected 0..%d", req->norm, MGX_NUM_CHROMA_NORMS - 1);
+  if (!req->weights) return fail(MGX_E_INVALID_ARGUMENT, "mgx_chroma_request.weights is NULL");
+  if (!req->per_frame && !req->summary) return fail(MGX_E_INVALID_ARGUMENT, "mgx_chroma_request.per_frame and .summary are both NULL");
+  if (req->summary && nsignals == 0) return fail(MGX_E_INVALID_ARGUMENT, "mgx_chroma_request.summary is set with num_signals = 0");
+  if (!p) return fail(MGX_E_INVALID_ARGUMENT, "plan is NULL");
+  int rc = summary_inputs(p, samples, num_samples, starts, nframes, frame_offsets, nsignals);
+  if (rc) return rc;
+  // (the host sees both tables: they are checked here, before any copy, as mgx_summarize_host checks them)
+  const uint64_t n = (uint64_t)p->n;
+  for (uint64_t f = 0; f < nframes; ++f)
+    if (starts[f] > num_samples - n)
+      return fail(MGX_E_INVALID_ARGUMENT, "starts[%llu] = %llu: a buffer of %d leaves the %llu samples", (unsigned long long)f,
+                  (unsigned long long)starts[f], p->n, (unsigned long long)num_samples);
+  for (uint64_t s = 0; s < nsignals; ++s)
+    if (frame_offsets[s + 1] < frame_offsets[s])
+      return fail(MGX_E_INVALID_ARGUMENT, "frame_offsets[%llu] = %llu is below frame_offsets[%llu] = %llu", (unsigned long long)(s + 1),
+                  (unsigned long long)frame_offsets[s + 1], (unsigned long long)s, (unsigned long long)frame_offsets[s]);
+  if (nsignals > 0 && frame_offsets[nsignals] > nframes)
+    return fail(MGX_E_INVALID_ARGUMENT, "frame_offsets[%llu] = %llu is above the %llu buffers", (unsigned long long)nsignals,
+                (unsigned long long)frame_offsets[nsignals], (unsigned long long)nframes);
+  const mgx_outputs none{};
+  mgx::Outputs x;  // (no per-frame field crosses back)
+  if ((rc = make_outputs(p, &none, nullptr, &x))) return rc;
+  resident_stop(p);
+  const uint32_t C = req->num_chroma, cols = (uint32_t)(n / 2);
+  const uint64_t stats = nsignals * MGX_NUM_STATS * C;
+  if (nframes == 0) {
+    // no buffers: every signal is empty, NaN in all four (nothing for the device to do)
+    if (req->summary) std::fill_n(req->summary, stats, std::nan(""));
+    return MGX_OK;
+  }
+  // the call's buffer: the bank, the chroma rows, and for the pooling a table, the shifts, the partials and the summaries
+  const bool pool = req->summary != nullptr;
+  uint64_t total = 0;
+  auto take = [&total](uint64_t bytes) {
+    const uint64_t at = total;
+    total += (bytes + 255) / 256 * 256;
+    return at;
+  };
+  const uint64_t at_bank = take((uint64_t)C * cols * sizeof(float)), at_rows = take(nframes * C * sizeof(float));
+  const uint64_t at_table = pool ? take((nsignals + 1) * sizeof(uint64_t)) : 0, at_shift = pool ? take(nsignals * C * sizeof(double)) : 0;
+  const uint64_t at_part = pool ? take((nframes / mgx::kSummaryBlock + nsignals + 1) * mgx::kSummaryWords * C * sizeof(double)) : 0;
+  const uint64_t at_result = pool ? take(stats * sizeof(double)) : 0;
+  hipError_t e = hipSetDevice(p->d.device);
+  if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
+  // the staging streams first: the bank's copy and the last kernels go on the compute stream
+  if ((rc = ensure_host_staging(p, 1, mgx::kOutLayoutSlack))) return rc;
+  if (p->s_chroma_bytes < total) {
+    if (p->s_chroma) (void)hipFree(p->s_chroma);
+    p->s_chroma = nullptr;
+    p->s_chroma_bytes = 0;
+    e = hipMalloc(reinterpret_cast<void**>(&p->s_chroma), total);
+    if (e != hipSuccess) { p->s_chroma = nullptr; return hip_fail(e, "hipMalloc(chroma rows)"); }
+    p->s_chroma_bytes = total;
+  }
+  const float* const bank = reinterpret_cast<const float*>(p->s_chroma + at_bank);
+  float* const out = reinterpret_cast<float*>(p->s_chroma + at_rows);
+  e = hipMemcpyAsync(p->s_chroma + at_bank, req->weights, (uint64_t)C * cols * sizeof(float), hipMemcpyHostToDevice, p->s_comp);
+  if (e == hipSuccess && pool)
+    e = hipMemcpyAsync(p->s_chroma + at_table, frame_offsets, (nsignals + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, p->s_comp);
+  if (e != hipSuccess) {
+    (void)hipStreamSynchronize(p->s_comp);
+    return hip_fail(e, "hipMemcpyAsync(weights, frame_offsets)");
+  }
+  ChunkHook hook;
+  hook.pooled = MGX_OUT_AMPLITUDE_SPECTRUM;
+  hook.after = [&](uint64_t f0, uint64_t cnt, const mgx::Outputs& d) {
+    const hipError_t ke = mgx::launch_chroma(d.amplitude_spectrum, cnt, cols, bank, C, req->norm, out + f0 * C, p->s_comp);
+    return ke == hipSuccess ? (int)MGX_OK : hip_fail(ke, "chroma kernel launch");
+  };
+  if ((rc = gather_host_chunked(p, samples, starts, nframes, &x, &hook))) return rc;
+  if (req->per_frame) e = hipMemcpyAsync(req->per_frame, out, nframes * C * sizeof(float), hipMemcpyDeviceToHost, p->s_comp);
+  if (pool && e == hipSuccess) {
+    // the summary kernels over the whole call's chroma rows: one field of width C, keyed by the table
+    mgx::SummaryArgs a{};
+    a.nfields = 1;
+    a.cols = C;
+    a.f[0].src = out;
+    a.f[0].dst = reinterpret_cast<double*>(p->s_chroma + at_result);
+    a.f[0].width = C;
+    a.table = reinterpret_cast<const uint64_t*>(p->s_chroma + at_table);
+    a.num_signals = nsignals;
+    a.num_frames = nframes;
+    a.rows = nframes;
+    a.nslots = nframes / mgx::kSummaryBlock + nsignals;
+    a.shift = reinterpret_cast<double*>(p->s_chroma + at_shift);
+    a.part = reinterpret_cast<double*>(p->s_chroma + at_part);
+    e = mgx::launch_summary_partial(a, p->s_comp);
+    if (e == hipSuccess) e = mgx::launch_summary_final(a, p->s_comp);
+    if (e == hipSuccess) e = hipMemcpyAsync(req->summary, a.f[0].dst, stats * sizeof(double), hipMemcpyDeviceToHost, p->s_comp);
+  }
+  const hipError_t es = hipStreamSynchronize(p->s_comp);
+  if (e == hipSuccess) e = es;
+  return e == hipSuccess ? MGX_OK : hip_fail(e, "chroma and summary kernels and copies");
+}
 
 int mgx_wav_parse(const void* bytes, uint64_t len, mgx_wav_info* info) {
   if (!bytes || !info) return fail(MGX_E_INVALID_ARGUMENT, "NULL argument");

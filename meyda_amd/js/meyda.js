@@ -34,6 +34,12 @@
 //   getSignalOnsets(signals, hopSize, {feature, mode, lag, preMax, postMax, preAvg, postAvg, delta, wait, envelope})
 //   / getSignalOnsetsAsync(...)     the onsets of every signal: the peaks of a feature's spectral flux, picked on
 //                                   the device within each signal; {frameOffsets, onsetOffsets, onsets[, envelope]}
+//   getSignalChroma(signals, hopSize[, {weights, numChroma, a440, centerOctave, octaveWidth, baseC, norm, summary}])
+//   / getSignalChromaAsync(...)     the pitch-class profile of every buffer of every signal (later Meyda's chroma),
+//                                   computed on the device from spectra that stay there; {chroma, numChroma,
+//                                   frameOffsets[, summaries]}
+//   Meyda.chromaFilterBank(bufferSize, sampleRate[, options])
+//                                   the numChroma x bufferSize / 2 chroma filter bank (host only)
 //   Meyda.signalsFrameStarts(lengths, bufferSize, hopSize)
 //                                   {starts, frameOffsets} of signals stored one after another
 //   Meyda.readWav(wavBytes)         the header: {pcmFormat, channels, sampleRate, sampleFrames, ...}
@@ -502,6 +508,40 @@ class Meyda {
       .then((r) => onsetResult(r, c.frameOffsets));
   }
 
+  // The chroma of getBatchSignals' signals (later Meyda's `chroma`): every buffer's amplitude spectrum times a
+  // numChroma x bufferSize / 2 filter bank, each product sum added in the fixed order of include/meyda_gpu.h, then
+  // divided by the buffer's largest value (norm 'max', Meyda's; 'none': the sums). The bank is options.weights (a
+  // Float32Array, numChroma rows: the caller's own, which may be signed) or Meyda.chromaFilterBank of this
+  // instance's bufferSize and sample rate with {numChroma, a440, centerOctave, octaveWidth, baseC}. Returns {chroma,
+  // numChroma, frameOffsets}: chroma is a Float32Array, buffer t's profile at [t numChroma, (t + 1) numChroma), rows
+  // as in frameOffsets; with summary: true also `summaries`: {mean, variance, min, max}, Float64Arrays of
+  // signals.length x numChroma as getSignalSummaries gives them. Only the profiles and the summaries cross back.
+  getSignalChroma(signals, hopSize, options) {
+    const o = chromaOptions(options, this.bufferSize, this.sampleRate);
+    const c = this._concatSignals(signals, hopSize);
+    return chromaResult(addon.chromaGather(this._plan(), c.samples, c.starts, c.frameOffsets, o), c.frameOffsets);
+  }
+
+  getSignalChromaAsync(signals, hopSize, options) {
+    const o = chromaOptions(options, this.bufferSize, this.sampleRate);
+    const c = this._concatSignals(signals, hopSize);
+    return this._runAsync((plan) => addon.chromaGatherAsync(plan, c.samples, c.starts, c.frameOffsets, o))
+      .then((r) => chromaResult(r, c.frameOffsets));
+  }
+
+  // The chroma filter bank of librosa.filters.chroma (later Meyda's createChromaFilterBank) as include/meyda_gpu.h
+  // states it: a Float32Array of numChroma x bufferSize / 2, row-major; options {numChroma: 12, a440: 440,
+  // centerOctave: 5, octaveWidth: 2 (0: no octave weighting), baseC: true (row 0 is C; false: A)}. Host only.
+  static chromaFilterBank(bufferSize, sampleRate, options) {
+    if (typeof bufferSize !== 'number' || !isPowerOfTwo(bufferSize) || bufferSize < 4) {
+      throw new Error('Buffer size is not a power of two: Meyda will not run.');
+    }
+    if (typeof sampleRate !== 'number' || !(sampleRate > 0) || !Number.isFinite(sampleRate)) {
+      throw new RangeError('sampleRate must be a positive finite number');
+    }
+    return addon.chromaWeights(bufferSize, sampleRate, chromaBankOptions(options));
+  }
+
   _concatSignals(signals, hopSize) {
     const hop = this._checkHop(hopSize);
     if (!Array.isArray(signals)) throw new TypeError('signals must be an array of Float32Arrays');
@@ -790,6 +830,63 @@ function onsetOptions(options) {
   if (typeof o.delta !== 'number') throw new TypeError('delta must be a number');
   if (Number.isNaN(o.delta)) throw new RangeError('delta must not be NaN');
   return o;
+}
+
+// Meyda.chromaFilterBank's options as the addon takes them
+const CHROMA_NORMS = { none: 0, max: 1 };
+function chromaBankOptions(options) {
+  if (options === undefined || options === null) options = {};
+  if (typeof options !== 'object') throw new TypeError('options must be an object: {numChroma, a440, centerOctave, octaveWidth, baseC}');
+  const o = { numChroma: options.numChroma === undefined ? 12 : options.numChroma,
+    a440: options.a440 === undefined ? 440 : options.a440,
+    centerOctave: options.centerOctave === undefined ? 5 : options.centerOctave,
+    octaveWidth: options.octaveWidth === undefined ? 2 : options.octaveWidth,
+    baseC: options.baseC === undefined ? true : !!options.baseC };
+  if (!Number.isInteger(o.numChroma) || o.numChroma < 1 || o.numChroma > 36) throw new RangeError('numChroma must be an integer from 1 to 36');
+  if (typeof o.a440 !== 'number' || !Number.isFinite(o.a440) || !(o.a440 > 0)) throw new RangeError('a440 must be a positive finite number');
+  if (typeof o.centerOctave !== 'number' || !Number.isFinite(o.centerOctave)) throw new RangeError('centerOctave must be a finite number');
+  if (typeof o.octaveWidth !== 'number' || !Number.isFinite(o.octaveWidth) || o.octaveWidth < 0) {
+    throw new RangeError('octaveWidth must be a finite number, 0 or above');
+  }
+  return o;
+}
+
+// getSignalChroma's options as the addon takes them: the bank (the caller's, or the library's), its rows, the norm
+function chromaOptions(options, bufferSize, sampleRate) {
+  if (options === undefined || options === null) options = {};
+  if (typeof options !== 'object') {
+    throw new TypeError('options must be an object: {weights, numChroma, a440, centerOctave, octaveWidth, baseC, norm, summary}');
+  }
+  const norm = options.norm === undefined ? 'max' : options.norm;
+  if (!Object.prototype.hasOwnProperty.call(CHROMA_NORMS, norm)) throw new RangeError("chroma norm must be 'max' or 'none'");
+  const o = { norm: CHROMA_NORMS[norm], summary: !!options.summary };
+  if (options.weights !== undefined && options.weights !== null) {
+    if (!(options.weights instanceof Float32Array)) throw new TypeError('weights must be a Float32Array');
+    const cols = bufferSize / 2;
+    o.numChroma = options.numChroma === undefined ? options.weights.length / cols : options.numChroma;
+    if (!Number.isInteger(o.numChroma) || o.numChroma < 1 || o.numChroma > 36 || o.numChroma * cols !== options.weights.length) {
+      throw new RangeError('weights must hold numChroma (1 to 36) rows of bufferSize / 2 values');
+    }
+    o.weights = options.weights;
+  } else {
+    const b = chromaBankOptions(options);
+    o.numChroma = b.numChroma;
+    o.weights = addon.chromaWeights(bufferSize, sampleRate, b);
+  }
+  return o;
+}
+
+function chromaResult(raw, frameOffsets) {
+  const r = { chroma: raw.chroma, numChroma: raw.numChroma, frameOffsets };
+  if (raw.summary) {
+    const S = frameOffsets.length - 1, w = raw.numChroma;
+    r.summaries = {};
+    STATS.forEach((k, j) => {
+      r.summaries[k] = new Float64Array(S * w);
+      for (let s = 0; s < S; ++s) r.summaries[k].set(raw.summary.subarray((s * STATS.length + j) * w, (s * STATS.length + j + 1) * w), s * w);
+    });
+  }
+  return r;
 }
 
 function onsetResult(raw, frameOffsets) {
