@@ -42,6 +42,9 @@
  *   mgx_chroma_weights,  chroma: the pitch-class profile of every    no counterpart in this snapshot; later
  *   mgx_chroma_device,   amplitude row (a dense C x N/2 filter       Meyda's chroma (createChromaFilterBank,
  *   mgx_chroma_host      bank), per frame and pooled per clip        librosa.filters.chroma)
+ *   mgx_tempogram_device, tempo: the local autocorrelation of a       no counterpart: librosa.feature.tempogram
+ *   mgx_tempo_device,    clip's envelope per frame, pooled per clip,  and librosa.feature.tempo in a host
+ *   mgx_tempo_host       and the lag a tempo prior picks              application
  *   mgx_group_*          several devices, RCCL gather of the        src/meyda.js:17-97 (one plan
  *                        per-frame records to the root device       per device), :69-91 (buffers
  *                                                                   are independent: shardable)
@@ -832,6 +835,118 @@ typedef struct mgx_chroma_request {
 int mgx_chroma_host(mgx_plan* plan, const float* samples, uint64_t num_samples, const uint64_t* starts,
                     uint64_t num_frames, const uint64_t* frame_offsets, uint64_t num_signals,
                     const mgx_chroma_request* request);
+
+/* ---- Tempo: a clip's autocorrelation tempogram and tempo on the device ---------------------------
+ * Replaces, in a host application, the local autocorrelation of the onset envelope after it was copied back, its
+ * average over the clip and the weighing of the lags with a tempo prior (librosa.feature.tempogram and
+ * librosa.feature.tempo). The reference snapshot has no counterpart, so the definitions are stated here in full.
+ * Like the statistics, the deltas, the flux, the peaks and the chroma it is no feature: MGX_NUM_FEATURES, the name
+ * table and every struct above are as they were.
+ *
+ * The tempogram. A signal owns rows [a, b) of a one-column envelope x of num_frames values, float32 or float64;
+ * values are taken as float64. Outside the signal the envelope is +0, not an edge repeat: x~(u) = x(u) for
+ * a <= u < b, else +0. The parameters are the window length W (2 .. MGX_TEMPOGRAM_MAX_WIN), the number of lags L
+ * (1 .. W), a window h of W float32 values (the caller's, as chroma's bank is) and a normalisation. For row t of
+ * [a, b):
+ *
+ *   1. y(j) = h(j) x~(t - floor(W / 2) + j), j = 0 .. W - 1, formed in float64 and rounded once to float32
+ *      (denormal results are kept).
+ *   2. For l = 0 .. L - 1: S(l) starts at +0; S(l) += y(j) y(j + l) for j = 0, 1, .., W - 1 - l ascending. The
+ *      product of two float32 values is exact in float64; each addition is rounded once (an FMA rounds what the
+ *      definition rounds). The order is plainly sequential on purpose: a lane can own a lag.
+ *   3. MGX_TEMPOGRAM_NORM_NONE leaves S as it is.
+ *   4. MGX_TEMPOGRAM_NORM_LAG0: if S(0) > 0 and S(0) is finite, S(l) = S(l) / S(0), one correctly rounded float64
+ *      division per output (lag 0 becomes exactly 1); otherwise the row is left as it is (a silent window, a NaN,
+ *      an overflow).
+ *   5. The result is rounded once to float32.
+ *
+ * Non-finite inputs follow IEEE: a NaN or an infinite envelope value reaches the rows whose window holds it, in
+ * its own signal, and no other row. Rows that belong to no signal are not written; an empty signal has no rows.
+ * No atomics: the same bits from every call below, a repeated call, a graph replay and any grid.
+ *
+ * The window (mgx_tempogram_window; host only): the periodic Hann window h(j) = 0.5 - 0.5 cos(2 pi j / W), formed
+ * in float64 and rounded once to float32. MGX_E_INVALID_ARGUMENT: W outside 2 .. MGX_TEMPOGRAM_MAX_WIN, NULL h.
+ *
+ * The prior (mgx_tempo_prior; host only): p(0) = 0; for l >= 1 with bpm(l) = 60 frame_rate / l: p(l) = 0 if
+ * max_bpm > 0 and bpm(l) > max_bpm, otherwise p(l) = exp(-0.5 ((log2 bpm(l) - log2 start_bpm) / std_octaves)^2):
+ * librosa's log-normal prior without its constant factor (its defaults: 120, 1.0, 320). All float64.
+ * MGX_E_INVALID_ARGUMENT: frame_rate, start_bpm or std_octaves not finite or not positive, max_bpm NaN or
+ * negative, L = 0, NULL p.
+ *
+ * The pick takes a mean row m(.) of L doubles, the weights p and a gain g (1e6 in librosa; finite and >= 0):
+ * s(l) = (1 + g m(l)) p(l), three float64 roundings and no contraction. The lag is the lowest l whose s(l) is
+ * greater than every s before it, starting from a best of +0: a NaN never wins, and no positive score gives lag
+ * 0, "none". This is the argmax of librosa's log1p(g m) + log p with the monotone exponential applied, so the
+ * device evaluates no transcendental. The output is a uint32 per signal; bpm = 60 frame_rate / lag is the
+ * binding's arithmetic. */
+#define MGX_TEMPOGRAM_MAX_WIN 1024
+typedef enum mgx_tempogram_norm {
+  MGX_TEMPOGRAM_NORM_NONE = 0,
+  MGX_TEMPOGRAM_NORM_LAG0 = 1,
+  MGX_NUM_TEMPOGRAM_NORMS = 2
+} mgx_tempogram_norm;
+typedef struct mgx_tempo_params {
+  uint32_t struct_size;  /* = sizeof(mgx_tempo_params), 24; anything else: MGX_E_INVALID_ARGUMENT */
+  uint32_t win_length;   /* W, 2 .. MGX_TEMPOGRAM_MAX_WIN; 384 */
+  uint32_t num_lags;     /* L, 1 .. W; 384 */
+  uint32_t norm;         /* mgx_tempogram_norm; MGX_TEMPOGRAM_NORM_LAG0 */
+  double gain;           /* g of the pick, finite and >= 0; 1e6 */
+} mgx_tempo_params;
+void mgx_tempo_params_init(mgx_tempo_params* params);
+int mgx_tempogram_window(uint32_t win_length, float* window /* W */);
+int mgx_tempo_prior(double frame_rate, double start_bpm, double std_octaves, double max_bpm, uint32_t num_lags,
+                    double* prior /* L */);
+
+/* The tempogram on device arrays; no plan: asynchronous on `stream`, no allocation, no host-side state, capturable.
+ * Every pointer is a device pointer. envelope_f64: 0 float32, 1 float64. frame_offsets NULL with num_signals 0:
+ * one signal [0, num_frames). The table is read as mgx_delta_device reads it, every entry limited to num_frames:
+ * a non-decreasing one gives the definition above, any other gives unspecified values in the rows it is wrong
+ * about, and no access is made outside the arrays. tempogram: num_frames x L float32. num_frames = 0 returns
+ * MGX_OK and writes nothing.
+ * MGX_E_INVALID_ARGUMENT before any launch: envelope_f64 > 1, W outside 2 .. MGX_TEMPOGRAM_MAX_WIN, L outside
+ * 1 .. W, norm >= MGX_NUM_TEMPOGRAM_NORMS, NULL window or tempogram, tempogram equal to envelope or to window,
+ * num_signals > 0 with NULL frame_offsets, NULL envelope with num_frames > 0. */
+int mgx_tempogram_device(const void* envelope, uint64_t num_frames, uint32_t envelope_f64,
+                         const uint64_t* frame_offsets, uint64_t num_signals, const float* window /* device */,
+                         uint32_t win_length, uint32_t num_lags, uint32_t norm, float* tempogram, void* stream);
+
+/* Tempogram -> per-clip pooling -> pick, on device arrays; no plan, no allocation, capturable. Outputs, each
+ * optional but not all NULL: tempogram (num_frames x L float32), summary (S x MGX_NUM_STATS x L doubles: the
+ * tempogram rows pooled per clip by the summary kernels as one field of width L, every rule of the summaries
+ * holding: blocks of 256 rows from the signal's first row, NaN in all four for an empty signal), lag (S uint32:
+ * the pick over the mean row under `prior`, L doubles on the device, required with lag). S is num_signals, or 1
+ * when frame_offsets is NULL and num_signals is 0. The table is made non-decreasing and limited to num_frames as
+ * mgx_summarize_device makes it.
+ * With a tempogram output the rows are written there and pooled in one pass. Without one they are produced
+ * MGX_TEMPO_CHUNK_ROWS rows at a time into the workspace and each pass is pooled by a partial launch over its
+ * rows, so the workspace does not grow with num_frames x L; both routes give the same bits.
+ * mgx_tempo_workspace_bytes (host only; keep_rows: 1 when the call has a tempogram output): a multiple of 256,
+ *   256 ceil((S + 1) 8 / 256) + 256 ceil(S L 8 / 256) + 256 ceil((floor(F / 256) + S + 1) 5 L 8 / 256)
+ *   + 256 ceil(S 4 L 8 / 256) + (keep_rows ? 0 : 256 ceil(min(F, MGX_TEMPO_CHUNK_ROWS) L 4 / 256))
+ * -- the table, the shifts, the partials, the summaries and a pass of rows (100,663,296 bytes at L = 384).
+ * MGX_E_INVALID_ARGUMENT before any launch: what mgx_tempogram_device refuses, a bad struct_size, a gain that is
+ * not finite or is negative, all three outputs NULL, lag without prior, a workspace smaller than
+ * mgx_tempo_workspace_bytes or not 256-byte aligned. */
+#define MGX_TEMPO_CHUNK_ROWS 65536
+int mgx_tempo_workspace_bytes(uint64_t num_frames, uint64_t num_signals, const mgx_tempo_params* params,
+                              uint32_t keep_rows, uint64_t* bytes);
+int mgx_tempo_device(const void* envelope, uint64_t num_frames, uint32_t envelope_f64, const uint64_t* frame_offsets,
+                     uint64_t num_signals, const mgx_tempo_params* params, const float* window /* device */,
+                     const double* prior /* device */, float* tempogram, double* summary, uint32_t* lag,
+                     void* workspace, uint64_t workspace_bytes, void* stream);
+
+/* Host pointers throughout: mgx_summarize_flux_host with exactly the one request `flux` (no other output, summary
+ * or delta), followed by mgx_tempo_device without a tempogram output over the plan-owned flux column that call
+ * keeps on the device -- as mgx_onsets_host runs the picker. flux->per_frame and flux->summary are honoured when
+ * set and written bit for bit as that call writes them; both may be NULL. window (W floats) and prior (L doubles,
+ * required with lag) are uploaded once per call. Only lag (S uint32), summary (S x MGX_NUM_STATS x L doubles) and
+ * what the request names cross back; summary or lag may be NULL, not both. The result equals mgx_tempo_device on
+ * the column mgx_summarize_flux_host returns, wherever the chunks end. num_signals = 0 is
+ * MGX_E_INVALID_ARGUMENT: a tempo is a clip's. Every other refusal is that of the two calls it is made of. */
+int mgx_tempo_host(mgx_plan* plan, const float* samples, uint64_t num_samples, const uint64_t* starts,
+                   uint64_t num_frames, const uint64_t* frame_offsets, uint64_t num_signals,
+                   const mgx_flux_request* flux, const mgx_tempo_params* params, const float* window,
+                   const double* prior, double* summary, uint32_t* lag);
 
 /* ---- Multi-device groups -------------------------------
  * Replaces nothing in the reference (single-threaded browser code); it exists because

@@ -32,6 +32,14 @@
  *                                        -> { chroma: Float32Array(nframes x numChroma), numChroma[, summary:
  *                                           Float64Array(S x 4 x numChroma)] }: the chroma rows of every buffer,
  *                                           computed on the device from spectra that stay there (mgx_chroma_host)
+ *   tempogramWindow(winLength)           -> Float32Array(winLength): the periodic Hann window (mgx_tempogram_window; host only)
+ *   tempoPrior(frameRate, numLags[, {startBpm, stdOctaves, maxBpm}])
+ *                                        -> Float64Array(numLags): the log-normal tempo prior (mgx_tempo_prior; host only)
+ *   tempoGather(plan, samples, starts, frameOffsets, {field, mode, lag, winLength, numLags, norm, gain, window, prior,
+ *               mean, envelope}) / tempoGatherAsync(...)
+ *                                        -> { lag: Uint32Array(S), numLags[, summary: Float64Array(S x 4 x numLags)][,
+ *                                           envelope: Float32Array(nframes)] }: the lag the prior picks from every
+ *                                           signal's mean tempogram row, on the device (mgx_tempo_host)
  *   wavParse(wavBytes)                   -> { pcmFormat, channels, sampleRate, bitsPerSample, ... }
  *   hostTables(opts)                     -> { hanning, hamming, window, barkScale, barkLimits, melBins, dct }
  *   isPowerOfTwo(n), deviceCount(), featureNames(), featureInfo(name), abiVersion()
@@ -313,6 +321,15 @@ typedef struct {
   int chroma;
   mgx_chroma_request creq;
   napi_ref crefs[3];  /* the bank (kept alive), the rows, the summaries */
+  /* tempoGather: a gather job whose outputs are the lag a tempo prior picks from the mean tempogram row of flux[0]'s
+   * column within every signal, and with the option mean the pooled tempogram rows (mgx_tempo_host) */
+  int tempo;
+  mgx_tempo_params tpar;
+  const float* twindow;
+  const double* tprior;
+  double* tsummary;
+  uint32_t* tlag;
+  napi_ref trefs[4];  /* the window and the prior (kept alive), the lags, the summaries */
   mgx_outputs out;
   mgx_aux_outputs aux;  /* melBands (SLOT_MEL): the job then makes the mgx_extract_*_ex call */
   /* The outputs are written straight into JS ArrayBuffers (napi_create_arraybuffer), held by
@@ -344,6 +361,11 @@ static void job_free_buffers(napi_env env, job* j) {
     if (j->crefs[i]) {
       napi_delete_reference(env, j->crefs[i]);
       j->crefs[i] = NULL;
+    }
+  for (int i = 0; i < 4; ++i)
+    if (j->trefs[i]) {
+      napi_delete_reference(env, j->trefs[i]);
+      j->trefs[i] = NULL;
     }
   for (int i = 0; i < NSLOTS; ++i)
     if (j->refs[i]) {
@@ -866,6 +888,126 @@ static int job_prepare_chroma(napi_env env, job* j, napi_value samples_v, napi_v
   return 1;
 }
 
+/* A typed-array property of the options object of the given type and length, kept alive by *ref. 0 with an error pending. */
+static int option_typed(napi_env env, napi_value obj, const char* name, napi_typedarray_type want, size_t count, napi_ref* ref,
+                        void** out) {
+  napi_value v, ab;
+  bool is_ta = false;
+  napi_typedarray_type tt = napi_int8_array;
+  size_t len = 0, off = 0;
+  void* data = NULL;
+  char msg[96];
+  if (option_given(env, obj, name, &v)) napi_is_typedarray(env, v, &is_ta);
+  if (is_ta) napi_get_typedarray_info(env, v, &tt, &len, &data, &ab, &off);
+  if (!is_ta || tt != want) {
+    snprintf(msg, sizeof msg, "%s must be a %s", name, want == napi_float32_array ? "Float32Array" : "Float64Array");
+    napi_throw_type_error(env, NULL, msg);
+    return 0;
+  }
+  if (len != count) {
+    snprintf(msg, sizeof msg, "%s.length must be %zu", name, count);
+    napi_throw_range_error(env, NULL, msg);
+    return 0;
+  }
+  if (napi_create_reference(env, v, 1, ref) != napi_ok) return 0;
+  *out = data;
+  return 1;
+}
+
+/* tempoGather(plan, samples, starts, frameOffsets, options): summarizeGather's inputs; options: {field, mode = 0,
+ * lag = 1, winLength = 384, numLags = winLength, norm = 1 (0 none, 1 lag0), gain = 1e6, window: a Float32Array of
+ * winLength, prior: a Float64Array of numLags, mean = false, envelope = false}. */
+static int job_prepare_tempo(napi_env env, job* j, napi_value samples_v, napi_value starts_v, napi_value offsets_v,
+                             napi_value options_v) {
+  napi_valuetype ot = napi_undefined;
+  napi_typeof(env, options_v, &ot);
+  if (ot != napi_object) {
+    napi_throw_type_error(env, NULL, "options must be an object: {field, mode, lag, winLength, numLags, norm, gain, window, prior, mean, envelope}");
+    return 0;
+  }
+  j->tempo = 1;
+  mgx_flux_request* r = &j->flux[0];
+  r->struct_size = sizeof *r;
+  if (!option_u32(env, options_v, "field", 0, MGX_NUM_FEATURES - 1, MGX_NUM_FEATURES, &r->field)) return 0;
+  if (r->field == MGX_NUM_FEATURES) {
+    napi_throw_type_error(env, NULL, "the tempo's flux names its field");
+    return 0;
+  }
+  if (!option_u32(env, options_v, "mode", 0, MGX_NUM_FLUX_MODES - 1, MGX_FLUX_RECTIFIED, &r->mode)) return 0;
+  if (!option_u32(env, options_v, "lag", 1, MGX_FLUX_MAX_LAG, 1, &r->lag)) return 0;
+  mgx_tempo_params* tp = &j->tpar;
+  mgx_tempo_params_init(tp);
+  if (!option_u32(env, options_v, "winLength", 2, MGX_TEMPOGRAM_MAX_WIN, tp->win_length, &tp->win_length)) return 0;
+  if (!option_u32(env, options_v, "numLags", 1, tp->win_length, tp->win_length, &tp->num_lags)) return 0;
+  if (!option_u32(env, options_v, "norm", 0, MGX_NUM_TEMPOGRAM_NORMS - 1, MGX_TEMPOGRAM_NORM_LAG0, &tp->norm)) return 0;
+  if (!option_f64(env, options_v, "gain", &tp->gain)) return 0;
+  if (tp->gain < 0) {
+    napi_throw_range_error(env, NULL, "gain must not be negative");
+    return 0;
+  }
+  void* data = NULL;
+  if (!option_typed(env, options_v, "window", napi_float32_array, tp->win_length, &j->trefs[0], &data)) return 0;
+  j->twindow = (const float*)data;
+  if (!option_typed(env, options_v, "prior", napi_float64_array, tp->num_lags, &j->trefs[1], &data)) return 0;
+  j->tprior = (const double*)data;
+  napi_value v, ab;
+  bool want_mean = false, b = false;
+  if (option_given(env, options_v, "mean", &v)) napi_coerce_to_bool(env, v, &v), napi_get_value_bool(env, v, &want_mean);
+  if (option_given(env, options_v, "envelope", &v)) napi_coerce_to_bool(env, v, &v), napi_get_value_bool(env, v, &b);
+  j->flux_per_frame[0] = b ? 1 : 0;
+  size_t count = 0, len = 0, off = 0;
+  j->frame_offsets = u64_of_f64(env, offsets_v, "frameOffsets", &count);
+  if (!j->frame_offsets) return 0;
+  if (count < 2) {
+    napi_throw_range_error(env, NULL, "frameOffsets holds one entry more than there are signals, and a tempo needs a signal");
+    return 0;
+  }
+  j->nsignals = count - 1;
+  bool is_ta = false;
+  napi_typedarray_type tt = napi_int8_array;
+  napi_is_typedarray(env, samples_v, &is_ta);
+  if (is_ta) napi_get_typedarray_info(env, samples_v, &tt, &len, &data, &ab, &off);
+  if (!is_ta || tt != napi_float32_array) {
+    napi_throw_type_error(env, NULL, "samples must be a Float32Array");
+    return 0;
+  }
+  if (j->box->group) {
+    napi_throw_error(env, NULL, "starts are not supported on a plan created with `devices`: device groups take dense buffers only");
+    return 0;
+  }
+  j->starts = u64_of_f64(env, starts_v, "starts", &count);
+  if (!j->starts) return 0;
+  j->gather = 1;
+  j->frames = (const float*)data;
+  j->nsamples = len;
+  j->nframes = count;
+  if (napi_create_arraybuffer(env, (size_t)j->nsignals * sizeof(uint32_t), &data, &ab) != napi_ok ||
+      napi_create_reference(env, ab, 1, &j->trefs[2]) != napi_ok) {
+    napi_throw_error(env, NULL, "out of host memory");
+    return 0;
+  }
+  memset(data, 0, (size_t)j->nsignals * sizeof(uint32_t));
+  j->tlag = (uint32_t*)data;
+  if (want_mean) {
+    if (napi_create_arraybuffer(env, (size_t)j->nsignals * MGX_NUM_STATS * tp->num_lags * sizeof(double), &data, &ab) != napi_ok ||
+        napi_create_reference(env, ab, 1, &j->trefs[3]) != napi_ok) {
+      napi_throw_error(env, NULL, "out of host memory");
+      return 0;
+    }
+    j->tsummary = (double*)data;
+  }
+  if (j->flux_per_frame[0]) {
+    if (napi_create_arraybuffer(env, (size_t)j->nframes * sizeof(float), &data, &ab) != napi_ok ||
+        napi_create_reference(env, ab, 1, &j->frefs[1][0]) != napi_ok) {
+      napi_throw_error(env, NULL, "out of host memory");
+      return 0;
+    }
+    memset(data, 0, (size_t)j->nframes * sizeof(float));
+    r->per_frame = (float*)data;
+  }
+  return 1;
+}
+
 /* Field i of a summary (the complex spectrum has none) */
 static void set_summary_field(mgx_summary_outputs* s, int i, double* p) {
   double** const arrays[NSLOTS - SLOT_LOUD] = {&s->loudness_specific, &s->mfcc, &s->amplitude_spectrum, &s->power_spectrum,
@@ -988,6 +1130,9 @@ static void job_run(job* j) {
   const uint32_t n = j->box->desc.buffer_size;
   if (j->chroma)
     j->rc = mgx_chroma_host(j->box->plan, j->frames, j->nsamples, j->starts, j->nframes, j->frame_offsets, j->nsignals, &j->creq);
+  else if (j->tempo)
+    j->rc = mgx_tempo_host(j->box->plan, j->frames, j->nsamples, j->starts, j->nframes, j->frame_offsets, j->nsignals, &j->flux[0],
+                           &j->tpar, j->twindow, j->tprior, j->tsummary, j->tlag);
   else if (j->onsets)
     j->rc = mgx_onsets_host(j->box->plan, j->frames, j->nsamples, j->starts, j->nframes, j->frame_offsets, j->nsignals, &j->flux[0],
                             &j->peak, j->peak_offsets, j->nframes ? j->peaks : NULL, j->nframes);
@@ -1051,6 +1196,19 @@ static napi_value job_result(napi_env env, job* j) {
     if (j->crefs[2])
       napi_set_named_property(env, obj, "summary",
                               typed_of(env, j->crefs[2], (size_t)j->nsignals * MGX_NUM_STATS * C * sizeof(double), napi_float64_array, 8));
+    return obj;
+  }
+  if (j->tempo) {
+    napi_value nl;
+    const size_t L = j->tpar.num_lags;
+    napi_set_named_property(env, obj, "lag", typed_of(env, j->trefs[2], (size_t)j->nsignals * sizeof(uint32_t), napi_uint32_array, 4));
+    if (napi_create_uint32(env, (uint32_t)L, &nl) != napi_ok) return NULL;
+    napi_set_named_property(env, obj, "numLags", nl);
+    if (j->trefs[3])
+      napi_set_named_property(env, obj, "summary",
+                              typed_of(env, j->trefs[3], (size_t)j->nsignals * MGX_NUM_STATS * L * sizeof(double), napi_float64_array, 8));
+    if (j->frefs[1][0])
+      napi_set_named_property(env, obj, "envelope", typed_of(env, j->frefs[1][0], (size_t)j->nframes * sizeof(float), napi_float32_array, 4));
     return obj;
   }
   if (j->onsets) {  /* the index arrays as signalsFrameStarts returns its own: Float64Arrays */
@@ -1119,7 +1277,7 @@ static napi_value job_result(napi_env env, job* j) {
 }
 
 /* kind: the input of an extraction job */
-enum { IN_FRAMES = 0, IN_WAV = 1, IN_SIGNAL = 2, IN_GATHER = 3, IN_SUMMARY = 4, IN_ONSETS = 5, IN_CHROMA = 6 };
+enum { IN_FRAMES = 0, IN_WAV = 1, IN_SIGNAL = 2, IN_GATHER = 3, IN_SUMMARY = 4, IN_ONSETS = 5, IN_CHROMA = 6, IN_TEMPO = 7 };
 
 static int job_prepare_kind(napi_env env, job* j, int kind, size_t argc, napi_value* argv) {
   if (kind == IN_WAV) return job_prepare_wav(env, j, argv[1], argv[2], argc > 3 ? argv[3] : NULL, argc > 4 ? argv[4] : NULL);
@@ -1128,6 +1286,7 @@ static int job_prepare_kind(napi_env env, job* j, int kind, size_t argc, napi_va
   if (kind == IN_SUMMARY) return job_prepare_summary(env, j, argv[1], argv[2], argv[3], argv[4], argc > 5 ? argv[5] : NULL);
   if (kind == IN_ONSETS) return job_prepare_onsets(env, j, argv[1], argv[2], argv[3], argv[4]);
   if (kind == IN_CHROMA) return job_prepare_chroma(env, j, argv[1], argv[2], argv[3], argv[4]);
+  if (kind == IN_TEMPO) return job_prepare_tempo(env, j, argv[1], argv[2], argv[3], argv[4]);
   return job_prepare(env, j, argv[1], argv[2]);
 }
 
@@ -1135,9 +1294,10 @@ static napi_value extract_common(napi_env env, napi_callback_info info, int kind
   size_t argc = 6;
   napi_value argv[6];
   CHECK(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
-  if (argc < (kind == IN_SUMMARY || kind == IN_ONSETS || kind == IN_CHROMA ? 5u : kind == IN_SIGNAL || kind == IN_GATHER ? 4u : 3u)) {
+  if (argc < (kind == IN_SUMMARY || kind == IN_ONSETS || kind == IN_CHROMA || kind == IN_TEMPO ? 5u : kind == IN_SIGNAL || kind == IN_GATHER ? 4u : 3u)) {
     napi_throw_type_error(env, NULL, kind == IN_WAV ? "extractWav(plan, wavBytes, features[, channel[, hop]])"
                                    : kind == IN_CHROMA ? "chromaGather(plan, samples, starts, frameOffsets, {weights, numChroma, ...})"
+                                   : kind == IN_TEMPO ? "tempoGather(plan, samples, starts, frameOffsets, {field, window, prior, ...})"
                                    : kind == IN_ONSETS ? "onsetsGather(plan, samples, starts, frameOffsets, {field, ...})"
                                    : kind == IN_SUMMARY ? "summarizeGather(plan, samples, starts, frameOffsets, features[, {deltaWidth, deltaOrder}])"
                                    : kind == IN_GATHER ? "extractGather(plan, samples, starts, features)"
@@ -1263,6 +1423,7 @@ static napi_value extract_gather_sync(napi_env env, napi_callback_info info) { r
 static napi_value summarize_gather_sync(napi_env env, napi_callback_info info) { return extract_common(env, info, IN_SUMMARY); }
 static napi_value onsets_gather_sync(napi_env env, napi_callback_info info) { return extract_common(env, info, IN_ONSETS); }
 static napi_value chroma_gather_sync(napi_env env, napi_callback_info info) { return extract_common(env, info, IN_CHROMA); }
+static napi_value tempo_gather_sync(napi_env env, napi_callback_info info) { return extract_common(env, info, IN_TEMPO); }
 
 static void async_execute(napi_env env, void* data) {
   (void)env;
@@ -1293,9 +1454,10 @@ static napi_value extract_async_common(napi_env env, napi_callback_info info, in
   size_t argc = 6;
   napi_value argv[6];
   CHECK(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
-  if (argc < (kind == IN_SUMMARY || kind == IN_ONSETS || kind == IN_CHROMA ? 5u : kind == IN_SIGNAL || kind == IN_GATHER ? 4u : 3u)) {
+  if (argc < (kind == IN_SUMMARY || kind == IN_ONSETS || kind == IN_CHROMA || kind == IN_TEMPO ? 5u : kind == IN_SIGNAL || kind == IN_GATHER ? 4u : 3u)) {
     napi_throw_type_error(env, NULL, kind == IN_WAV ? "extractWavAsync(plan, wavBytes, features[, channel[, hop]])"
                                    : kind == IN_CHROMA ? "chromaGatherAsync(plan, samples, starts, frameOffsets, {weights, numChroma, ...})"
+                                   : kind == IN_TEMPO ? "tempoGatherAsync(plan, samples, starts, frameOffsets, {field, window, prior, ...})"
                                    : kind == IN_ONSETS ? "onsetsGatherAsync(plan, samples, starts, frameOffsets, {field, ...})"
                                    : kind == IN_SUMMARY ? "summarizeGatherAsync(plan, samples, starts, frameOffsets, features[, {deltaWidth, deltaOrder}])"
                                    : kind == IN_GATHER ? "extractGatherAsync(plan, samples, starts, features)"
@@ -1334,6 +1496,7 @@ static napi_value extract_gather_async(napi_env env, napi_callback_info info) { 
 static napi_value summarize_gather_async(napi_env env, napi_callback_info info) { return extract_async_common(env, info, IN_SUMMARY); }
 static napi_value onsets_gather_async(napi_env env, napi_callback_info info) { return extract_async_common(env, info, IN_ONSETS); }
 static napi_value chroma_gather_async(napi_env env, napi_callback_info info) { return extract_async_common(env, info, IN_CHROMA); }
+static napi_value tempo_gather_async(napi_env env, napi_callback_info info) { return extract_async_common(env, info, IN_TEMPO); }
 
 /* chromaWeights(bufferSize, sampleRate[, {numChroma, a440, centerOctave, octaveWidth, baseC}]): the chroma filter
  * bank (mgx_chroma_weights; host only), a Float32Array of numChroma x bufferSize / 2, row-major. */
@@ -1379,6 +1542,70 @@ static napi_value chroma_weights(napi_env env, napi_callback_info info) {
   const int rc = mgx_chroma_weights((uint32_t)n, sr, &p, (float*)data);
   if (rc) return throw_mgx(env, rc);
   CHECK(napi_create_typedarray(env, napi_float32_array, count, ab, 0, &ta));
+  return ta;
+}
+
+/* tempogramWindow(winLength): the periodic Hann window of the tempogram (mgx_tempogram_window; host only), a
+ * Float32Array of winLength. */
+static napi_value tempogram_window(napi_env env, napi_callback_info info) {
+  size_t argc = 1;
+  napi_value argv[1];
+  CHECK(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  double w = 0;
+  napi_valuetype t0 = napi_undefined;
+  if (argc >= 1) napi_typeof(env, argv[0], &t0);
+  if (t0 != napi_number) {
+    napi_throw_type_error(env, NULL, "tempogramWindow(winLength)");
+    return NULL;
+  }
+  napi_get_value_double(env, argv[0], &w);
+  if (!(w >= 2) || w > MGX_TEMPOGRAM_MAX_WIN || w != (double)(uint32_t)w) {
+    napi_throw_range_error(env, NULL, "winLength must be an integer from 2 to 1024");
+    return NULL;
+  }
+  napi_value ab, ta;
+  void* data = NULL;
+  CHECK(napi_create_arraybuffer(env, (size_t)w * sizeof(float), &data, &ab));
+  const int rc = mgx_tempogram_window((uint32_t)w, (float*)data);
+  if (rc) return throw_mgx(env, rc);
+  CHECK(napi_create_typedarray(env, napi_float32_array, (size_t)w, ab, 0, &ta));
+  return ta;
+}
+
+/* tempoPrior(frameRate, numLags[, {startBpm = 120, stdOctaves = 1, maxBpm = 320}]): the log-normal tempo prior over the
+ * lags of an envelope of frameRate rows a second (mgx_tempo_prior; host only), a Float64Array of numLags. */
+static napi_value tempo_prior(napi_env env, napi_callback_info info) {
+  size_t argc = 3;
+  napi_value argv[3];
+  CHECK(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  double rate = 0, nl = 0, start = 120.0, std = 1.0, mx = 320.0;
+  napi_valuetype t0 = napi_undefined, t1 = napi_undefined, ot = napi_undefined;
+  if (argc >= 2) napi_typeof(env, argv[0], &t0), napi_typeof(env, argv[1], &t1);
+  if (t0 != napi_number || t1 != napi_number) {
+    napi_throw_type_error(env, NULL, "tempoPrior(frameRate, numLags[, {startBpm, stdOctaves, maxBpm}])");
+    return NULL;
+  }
+  napi_get_value_double(env, argv[0], &rate);
+  napi_get_value_double(env, argv[1], &nl);
+  if (!(nl >= 1) || nl > MGX_TEMPOGRAM_MAX_WIN || nl != (double)(uint32_t)nl) {
+    napi_throw_range_error(env, NULL, "numLags must be an integer from 1 to 1024");
+    return NULL;
+  }
+  if (argc > 2) napi_typeof(env, argv[2], &ot);
+  if (ot == napi_object) {
+    if (!option_f64(env, argv[2], "startBpm", &start) || !option_f64(env, argv[2], "stdOctaves", &std) ||
+        !option_f64(env, argv[2], "maxBpm", &mx))
+      return NULL;
+  } else if (ot != napi_undefined && ot != napi_null) {
+    napi_throw_type_error(env, NULL, "options must be an object: {startBpm, stdOctaves, maxBpm}");
+    return NULL;
+  }
+  napi_value ab, ta;
+  void* data = NULL;
+  CHECK(napi_create_arraybuffer(env, (size_t)nl * sizeof(double), &data, &ab));
+  const int rc = mgx_tempo_prior(rate, start, std, mx, (uint32_t)nl, (double*)data);
+  if (rc) return throw_mgx(env, rc);
+  CHECK(napi_create_typedarray(env, napi_float64_array, (size_t)nl, ab, 0, &ta));
   return ta;
 }
 
@@ -1616,6 +1843,10 @@ static napi_value init(napi_env env, napi_value exports) {
       {"chromaGather", NULL, chroma_gather_sync, NULL, NULL, NULL, napi_enumerable, NULL},
       {"chromaGatherAsync", NULL, chroma_gather_async, NULL, NULL, NULL, napi_enumerable, NULL},
       {"chromaWeights", NULL, chroma_weights, NULL, NULL, NULL, napi_enumerable, NULL},
+      {"tempoGather", NULL, tempo_gather_sync, NULL, NULL, NULL, napi_enumerable, NULL},
+      {"tempoGatherAsync", NULL, tempo_gather_async, NULL, NULL, NULL, napi_enumerable, NULL},
+      {"tempogramWindow", NULL, tempogram_window, NULL, NULL, NULL, napi_enumerable, NULL},
+      {"tempoPrior", NULL, tempo_prior, NULL, NULL, NULL, napi_enumerable, NULL},
       {"signalsFrameStarts", NULL, signals_frame_starts, NULL, NULL, NULL, napi_enumerable, NULL},
       {"wavParse", NULL, wav_parse, NULL, NULL, NULL, napi_enumerable, NULL},
       {"hostTables", NULL, host_tables, NULL, NULL, NULL, napi_enumerable, NULL},

@@ -44,6 +44,8 @@ EXPORTS = ["mgx_plan_desc_init", "mgx_plan_create", "mgx_plan_destroy", "mgx_pla
            "mgx_flux_device", "mgx_summarize_flux_workspace_bytes", "mgx_summarize_flux_device", "mgx_summarize_flux_host",
            "mgx_peaks_workspace_bytes", "mgx_peaks_device", "mgx_onsets_host",
            "mgx_chroma_params_init", "mgx_chroma_weights", "mgx_chroma_device", "mgx_chroma_host",
+           "mgx_tempo_params_init", "mgx_tempogram_window", "mgx_tempo_prior", "mgx_tempogram_device",
+           "mgx_tempo_workspace_bytes", "mgx_tempo_device", "mgx_tempo_host",
            "mgx_shard_range", "mgx_packed_layout", "mgx_comm_unique_id", "mgx_group_create",
            "mgx_group_create_rank", "mgx_group_create_loopback", "mgx_group_create_loopback_rccl", "mgx_group_destroy",
            "mgx_group_info", "mgx_group_comm_info", "mgx_group_extract_device", "mgx_group_extract_host"]
@@ -185,6 +187,42 @@ class ChromaRequest(ctypes.Structure):
     _fields_ = [("struct_size", ctypes.c_uint32), ("num_chroma", ctypes.c_uint32), ("norm", ctypes.c_uint32),
                 ("reserved", ctypes.c_uint32), ("weights", ctypes.c_void_p), ("per_frame", ctypes.c_void_p),
                 ("summary", ctypes.c_void_p)]
+
+
+TEMPOGRAM_MAX_WIN = 1024  # MGX_TEMPOGRAM_MAX_WIN
+TEMPO_CHUNK_ROWS = 65536  # MGX_TEMPO_CHUNK_ROWS
+TEMPOGRAM_NORMS = {"none": 0, "lag0": 1}  # mgx_tempogram_norm
+TEMPO_PARAMS = ("win_length", "num_lags", "norm", "gain")
+
+
+class TempoParams(ctypes.Structure):
+    """mgx_tempo_params: the window length, the lags, the normalisation of the tempogram and the gain of the pick."""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("win_length", ctypes.c_uint32), ("num_lags", ctypes.c_uint32),
+                ("norm", ctypes.c_uint32), ("gain", ctypes.c_double)]
+
+
+def _tempogram_norm(norm):
+    if isinstance(norm, str):
+        if norm not in TEMPOGRAM_NORMS:
+            raise ValueError("tempogram norm %r: one of %s" % (norm, sorted(TEMPOGRAM_NORMS)))
+        return TEMPOGRAM_NORMS[norm]
+    return int(norm)
+
+
+def tempo_params(win_length=None, num_lags=None, norm=None, gain=None):
+    """A TempoParams with the library's defaults (mgx_tempo_params_init: 384, 384, "lag0", 1e6) and the arguments
+    over them; num_lags defaults to win_length. Numbers out of range pass through: the library refuses them."""
+    p = TempoParams()
+    lib().mgx_tempo_params_init(ctypes.byref(p))
+    if win_length is not None:
+        p.win_length = p.num_lags = int(win_length)
+    if num_lags is not None:
+        p.num_lags = int(num_lags)
+    if norm is not None:
+        p.norm = _tempogram_norm(norm)
+    if gain is not None:
+        p.gain = float(gain)
+    return p
 
 
 def chroma_params(**params):
@@ -336,6 +374,22 @@ def lib():
                                         ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p]
         L.mgx_chroma_host.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64,
                                       ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(ChromaRequest)]
+        tpar = ctypes.POINTER(TempoParams)
+        L.mgx_tempo_params_init.argtypes = [tpar]
+        L.mgx_tempo_params_init.restype = None
+        L.mgx_tempogram_window.argtypes = [ctypes.c_uint32, ctypes.c_void_p]
+        L.mgx_tempo_prior.argtypes = [ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_uint32,
+                                      ctypes.c_void_p]
+        L.mgx_tempogram_device.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint64,
+                                           ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p,
+                                           ctypes.c_void_p]
+        L.mgx_tempo_workspace_bytes.argtypes = [ctypes.c_uint64, ctypes.c_uint64, tpar, ctypes.c_uint32, u64p]
+        L.mgx_tempo_device.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint64, tpar,
+                                       ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                       ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p]
+        L.mgx_tempo_host.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64,
+                                     ctypes.c_void_p, ctypes.c_uint64, freq, tpar, ctypes.c_void_p, ctypes.c_void_p,
+                                     ctypes.c_void_p, ctypes.c_void_p]
         L.mgx_shard_range.argtypes = [ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, u64p, u64p]
         L.mgx_packed_layout.argtypes = [ctypes.POINTER(PlanDesc), ctypes.c_uint32, ctypes.c_uint64, u64p]
         L.mgx_packed_layout.restype = ctypes.c_uint64
@@ -820,6 +874,54 @@ class Plan:
             res["summary"] = fres[0]["summary"]
         return res
 
+    def tempo(self, samples, starts, frame_offsets, frame_rate, feature="melBands", mode="rectified", lag=1, win_length=384,
+              num_lags=None, norm="lag0", gain=1e6, start_bpm=120.0, std_octaves=1.0, max_bpm=320.0, window=None, prior=None,
+              mean=False, envelope=False, envelope_summary=False):
+        """Host numpy in / numpy out (mgx_tempo_host): the flux of `feature` over the buffers at `starts`, its
+        autocorrelation tempogram (window: W float32, None: tempogram_window) pooled per signal, and the lag the
+        prior picks (prior: L float64, None: tempo_prior of frame_rate, the rows per second, with start_bpm,
+        std_octaves, max_bpm). Returns a dict: "lag" ((S,) uint32, 0: none), "bpm" ((S,) float64, 60 frame_rate /
+        lag, NaN where the lag is 0), "window", "prior", and when asked "summary" ((S, 4, L) float64: mean, variance,
+        min, max of the tempogram rows per signal; `mean`), "envelope" ((F,) float32) and "envelope_summary" ((S, 4))."""
+        samples = np.ascontiguousarray(samples, dtype=np.float32)
+        starts = np.ascontiguousarray(starts, dtype=np.uint64)
+        frame_offsets = np.ascontiguousarray(frame_offsets, dtype=np.uint64)
+        assert samples.ndim == 1 and starts.ndim == 1 and frame_offsets.ndim == 1 and frame_offsets.size >= 1
+        S = frame_offsets.size - 1
+        tp = tempo_params(win_length, num_lags, norm, gain)
+        W, L = int(tp.win_length), int(tp.num_lags)
+        window = tempogram_window(W) if window is None else np.ascontiguousarray(window, dtype=np.float32)
+        prior = tempo_prior(frame_rate, L, start_bpm, std_octaves, max_bpm) if prior is None else np.ascontiguousarray(prior, dtype=np.float64)
+        assert window.shape == (W,) and prior.shape == (L,)
+        req = {"feature": feature, "mode": mode, "lag": lag, "per_frame": envelope, "summary": envelope_summary}
+        reqs, fres = self._flux_requests(starts.size, S, [req], lambda shape: np.empty(shape, np.float64),
+                                         lambda shape: np.zeros(shape, np.float32))
+        lags = np.zeros(S, np.uint32)
+        summ = np.empty((S, len(STATS), L), np.float64) if mean else None
+        check(lib().mgx_tempo_host(self._h, samples.ctypes.data, samples.size, starts.ctypes.data, starts.size,
+                                   frame_offsets.ctypes.data, S, reqs, ctypes.byref(tp), window.ctypes.data, prior.ctypes.data,
+                                   None if summ is None else summ.ctypes.data, lags.ctypes.data))
+        res = {"lag": lags, "bpm": lag_bpm(lags, frame_rate), "window": window, "prior": prior}
+        if mean:
+            res["summary"] = summ
+        if envelope:
+            res["envelope"] = fres[0]["per_frame"]
+        if envelope_summary:
+            res["envelope_summary"] = fres[0]["summary"]
+        return res
+
+    def tempo_signals(self, signals, hop, frame_rate=None, **kw):
+        """A list of 1-D host signals in one call (Plan.tempo over signals_frame_starts of their lengths; frame_rate
+        None: the plan's sample rate / hop): the dict Plan.tempo returns, with "frame_offsets"."""
+        signals = [np.ascontiguousarray(x, dtype=np.float32).ravel() for x in signals]
+        starts, frame_offsets = signals_frame_starts([x.size for x in signals], self.n, hop)
+        samples = np.concatenate(signals) if signals else np.empty(0, np.float32)
+        if frame_rate is None:
+            frame_rate = float(self.desc.sample_rate) / hop
+        res = self.tempo(samples, starts, frame_offsets, frame_rate, **kw)
+        res["frame_offsets"] = frame_offsets
+        return res
+
     def chroma(self, samples, starts, frame_offsets=None, weights=None, norm="max", per_frame=True, summary=False, **params):
         """Host numpy in / numpy out (mgx_chroma_host): the chroma rows of the buffers at `starts` under `weights`
         (a (C, N/2) float32 bank; None: chroma_weights of the plan's size and sample rate with `params`), computed
@@ -1280,3 +1382,131 @@ def chroma_torch(rows, weights, norm="max", stream=None, out=None):
         stream = torch.cuda.current_stream(rows.device).cuda_stream
     chroma_device(rows.data_ptr(), F, cols, weights.data_ptr(), C, _chroma_norm(norm), out.data_ptr(), stream)
     return out
+
+
+def tempogram_window(win_length):
+    """mgx_tempogram_window (host only): the periodic Hann window of win_length float32 values."""
+    h = np.zeros(max(int(win_length), 0), np.float32)
+    buf = h if h.size else np.zeros(1, np.float32)
+    check(lib().mgx_tempogram_window(int(win_length), buf.ctypes.data))
+    return h
+
+
+def tempo_prior(frame_rate, num_lags, start_bpm=120.0, std_octaves=1.0, max_bpm=320.0):
+    """mgx_tempo_prior (host only): librosa's log-normal tempo prior over the lags 0 .. num_lags - 1 of an envelope of
+    frame_rate rows per second, without its constant factor; p[0] = 0, and 0 above max_bpm (0: no limit)."""
+    p = np.zeros(max(int(num_lags), 0), np.float64)
+    buf = p if p.size else np.zeros(1, np.float64)
+    check(lib().mgx_tempo_prior(float(frame_rate), float(start_bpm), float(std_octaves), float(max_bpm), int(num_lags),
+                                buf.ctypes.data))
+    return p
+
+
+def lag_bpm(lag, frame_rate):
+    """60 frame_rate / lag as float64, NaN where the lag is 0 (no tempo)."""
+    lag = np.asarray(lag, dtype=np.float64)
+    with np.errstate(divide="ignore"):
+        return np.where(lag > 0, 60.0 * float(frame_rate) / np.where(lag > 0, lag, 1.0), np.nan)
+
+
+def tempogram_device(envelope_ptr, num_frames, envelope_f64, offsets_ptr, num_signals, window_ptr, win_length, num_lags, norm,
+                     tempogram_ptr, stream=None):
+    """mgx_tempogram_device on device pointers (async on `stream`); a pointer may be None."""
+    check(lib().mgx_tempogram_device(ctypes.c_void_p(envelope_ptr or 0), num_frames, 1 if envelope_f64 else 0,
+                                     ctypes.c_void_p(offsets_ptr or 0), num_signals, ctypes.c_void_p(window_ptr or 0), win_length,
+                                     num_lags, norm, ctypes.c_void_p(tempogram_ptr or 0), ctypes.c_void_p(stream or 0)))
+
+
+def tempo_workspace_bytes(num_frames, num_signals, params, keep_rows):
+    """mgx_tempo_workspace_bytes (host only); params: a TempoParams; keep_rows: the call has a tempogram output."""
+    b = ctypes.c_uint64()
+    check(lib().mgx_tempo_workspace_bytes(num_frames, num_signals, ctypes.byref(params), 1 if keep_rows else 0, ctypes.byref(b)))
+    return b.value
+
+
+def tempo_device(envelope_ptr, num_frames, envelope_f64, offsets_ptr, num_signals, params, window_ptr, prior_ptr, tempogram_ptr,
+                 summary_ptr, lag_ptr, workspace_ptr, workspace_bytes, stream=None):
+    """mgx_tempo_device on device pointers (async on `stream`); params: a TempoParams; a pointer may be None."""
+    check(lib().mgx_tempo_device(ctypes.c_void_p(envelope_ptr or 0), num_frames, 1 if envelope_f64 else 0,
+                                 ctypes.c_void_p(offsets_ptr or 0), num_signals, ctypes.byref(params),
+                                 ctypes.c_void_p(window_ptr or 0), ctypes.c_void_p(prior_ptr or 0), ctypes.c_void_p(tempogram_ptr or 0),
+                                 ctypes.c_void_p(summary_ptr or 0), ctypes.c_void_p(lag_ptr or 0), ctypes.c_void_p(workspace_ptr or 0),
+                                 workspace_bytes, ctypes.c_void_p(stream or 0)))
+
+
+def _device_table(frame_offsets, dev):
+    import torch
+    if frame_offsets is None:
+        return None, 0
+    if not torch.is_tensor(frame_offsets):
+        frame_offsets = torch.from_numpy(np.ascontiguousarray(frame_offsets, dtype=np.uint64).view(np.int64)).to(dev)
+    assert frame_offsets.is_cuda and frame_offsets.dtype == torch.int64 and frame_offsets.is_contiguous()
+    assert frame_offsets.dim() == 1 and frame_offsets.shape[0] >= 1
+    return frame_offsets, frame_offsets.shape[0] - 1
+
+
+def tempogram_torch(envelope, window, frame_offsets=None, num_lags=None, norm="lag0", stream=None, out=None):
+    """The autocorrelation tempogram of `envelope`, a (F,) float32 or float64 CUDA tensor, under `window`, a (W,)
+    float32 CUDA tensor, within each signal (include/meyda_gpu.h): a (F, L) float32 tensor, L = num_lags (None: W).
+    Signal s owns rows [frame_offsets[s], frame_offsets[s + 1]) (an int64 CUDA tensor, or anything numpy turns into
+    one; None: one signal, every row); rows of no signal keep what `out` held (zero when it is allocated here)."""
+    import torch
+    assert envelope.is_cuda and envelope.is_contiguous() and envelope.dim() == 1
+    assert envelope.dtype in (torch.float32, torch.float64)
+    assert window.is_cuda and window.is_contiguous() and window.dim() == 1 and window.dtype == torch.float32
+    dev = envelope.device
+    F, W = envelope.shape[0], window.shape[0]
+    L = W if num_lags is None else int(num_lags)
+    frame_offsets, S = _device_table(frame_offsets, dev)
+    if out is None:
+        out = torch.zeros((F, max(L, 0)), dtype=torch.float32, device=dev)
+    assert out.is_cuda and out.is_contiguous() and out.dtype == torch.float32 and out.shape == (F, L)
+    if stream is None:
+        stream = torch.cuda.current_stream(dev).cuda_stream
+    tempogram_device(envelope.data_ptr(), F, envelope.dtype == torch.float64, None if frame_offsets is None else frame_offsets.data_ptr(),
+                     S, window.data_ptr(), W, L, _tempogram_norm(norm), out.data_ptr(), stream)
+    return out
+
+
+def tempo_torch(envelope, window, prior=None, frame_offsets=None, num_lags=None, norm="lag0", gain=1e6, tempogram=False,
+                summary=True, stream=None, workspace=None):
+    """mgx_tempo_device on CUDA tensors: the tempogram of `envelope` under `window` (as tempogram_torch), pooled per
+    signal, and the lag `prior` (a (L,) float64 CUDA tensor; None: no pick) picks from the mean row. Returns a dict
+    with "lag" ((S,) int32, with a prior), "summary" ((S, 4, L) float64, with summary) and "tempogram" ((F, L)
+    float32, zero in rows of no signal, with tempogram=True or a tensor to write into). Without a tempogram the
+    rows pass through the workspace TEMPO_CHUNK_ROWS at a time. The workspace is allocated here unless one is given
+    (a uint8 CUDA tensor of tempo_workspace_bytes, for a capture)."""
+    import torch
+    assert envelope.is_cuda and envelope.is_contiguous() and envelope.dim() == 1
+    assert envelope.dtype in (torch.float32, torch.float64)
+    assert window.is_cuda and window.is_contiguous() and window.dim() == 1 and window.dtype == torch.float32
+    dev = envelope.device
+    F, W = envelope.shape[0], window.shape[0]
+    tp = tempo_params(W, num_lags, norm, gain)
+    L = int(tp.num_lags)
+    frame_offsets, S = _device_table(frame_offsets, dev)
+    Sout = S if frame_offsets is not None else 1
+    res = {}
+    if tempogram is True:
+        tempogram = torch.zeros((F, L), dtype=torch.float32, device=dev)
+    if tempogram is not None and tempogram is not False:
+        assert tempogram.is_cuda and tempogram.is_contiguous() and tempogram.dtype == torch.float32 and tempogram.shape == (F, L)
+        res["tempogram"] = tempogram
+    else:
+        tempogram = None
+    if summary:
+        res["summary"] = torch.empty((Sout, len(STATS), L), dtype=torch.float64, device=dev)
+    if prior is not None:
+        assert prior.is_cuda and prior.is_contiguous() and prior.dtype == torch.float64 and prior.shape == (L,)
+        res["lag"] = torch.zeros(Sout, dtype=torch.int32, device=dev)
+    nbytes = tempo_workspace_bytes(F, S, tp, tempogram is not None)
+    if workspace is None:
+        workspace = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+    assert workspace.is_cuda and workspace.dtype == torch.uint8 and workspace.numel() >= nbytes
+    if stream is None:
+        stream = torch.cuda.current_stream(dev).cuda_stream
+    tempo_device(envelope.data_ptr(), F, envelope.dtype == torch.float64, None if frame_offsets is None else frame_offsets.data_ptr(),
+                 S, tp, window.data_ptr(), None if prior is None else prior.data_ptr(), None if tempogram is None else tempogram.data_ptr(),
+                 res["summary"].data_ptr() if summary else None, res["lag"].data_ptr() if prior is not None else None,
+                 workspace.data_ptr(), workspace.numel(), stream)
+    return res

@@ -4001,6 +4001,202 @@ hipError_t launch_chroma(const float* rows, uint64_t num_frames, uint32_t cols, 
   return launch_chroma_c<MGX_CHROMA_MAX_BINS>(g, kChromaBlocks, g.lds ? (size_t)bank : 0, stream, num_chroma);
 }
 
+// ---- Tempo (mgx_tempogram_device, mgx_tempo_device, mgx_tempo_host): the autocorrelation tempogram and the pick ----
+// tempogram_kernel<K>: a wave takes a row. It finds the row's signal by the binary search of flux_kernel, forms
+// y(j) = h(j) x~(t - W/2 + j) (include/meyda_gpu.h) straight from the envelope -- W loads a row against W L / 64
+// FMAs a lane, and neighbouring waves take neighbouring rows, so the loads are L1 / L2 hits; the envelope is not
+// staged -- and writes it as float32 into the wave's own LDS strip, which ends in zeros. Lane p owns the K
+// consecutive lags p K .. p K + K - 1 and walks j ascending with a register window of the K values y(j + l): a
+// step reads y(j) (one address for the wave: a broadcast) and the one value that enters the window, and does K
+// float64 FMAs; the loop is unrolled K times so the window rotates by name, not by moves. The product of two
+// float32 is exact in float64, so the FMA rounds what the definition's addition rounds, and the additions of a
+// lag are in the definition's order. Terms past a lag's last (j + l >= W) meet a zero of the strip: they add a
+// signed zero to a sum that is never -0, which changes no bit -- while every y is finite. A row with a NaN or an
+// infinite y takes the same walk with each term predicated on j + l < W instead (a wave-uniform branch; such
+// rows are rare), so an infinite y(j) never meets a padding zero. MGX_TEMPOGRAM_NORM_LAG0 reads S(0) from lane 0
+// and divides (the compiler's correctly rounded float64 division). Lanes whose lags are all >= L only idle at the
+// store; the idle half of the triangle (lag l has W - l terms) is paid in full.
+// No atomics; one writer per output; nothing depends on the grid.
+// tempo_pick_kernel: a wave per signal over the L means; a lane keeps the first maximum of its lags l = lane,
+// lane + 64, ..., then the wave takes the highest score, the lowest lag among equals: the first maximum of the
+// ascending scan. The file is compiled with -ffp-contract=off: (1 + g m) p is three roundings.
+namespace {
+
+constexpr uint32_t kTempogramBlocks = 4096;  // at most: 16 workgroups a CU
+
+struct TempogramArgs {
+  const void* env;
+  const float* window;
+  float* out;             // row row0's
+  const uint64_t* table;  // null: one signal, rows [0, num_frames)
+  uint64_t num_signals, num_frames, row0, nrows;
+  uint32_t W, L, norm, f64, strip;  // strip: the floats of a wave's LDS strip, >= roundup(W, K) + 64 K
+};
+
+template <int K>
+__global__ __launch_bounds__(256) void tempogram_kernel(TempogramArgs g) {
+  extern __shared__ float tempo_strips[];
+  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  float* const ys = tempo_strips + wave * g.strip;
+  const uint32_t W = g.W, L = g.L, half = W / 2, l0 = lane * K;
+  const uint64_t T_ = g.num_frames;
+  const float* __restrict__ const h = g.window;
+  for (uint32_t i = W + lane; i < g.strip; i += 64) ys[i] = 0.0f;
+  for (uint64_t i = (uint64_t)blockIdx.x * 4 + wave; i < g.nrows; i += (uint64_t)gridDim.x * 4) {
+    // the row's signal: the last s with table[s] <= t (wave-uniform), every entry limited to num_frames
+    const uint64_t t = g.row0 + i;
+    uint64_t a = 0, b = T_;
+    if (g.table) {
+      uint64_t lo = 0, hi = g.num_signals + 1;  // the first entry above t
+      while (lo < hi) {
+        const uint64_t mid = lo + (hi - lo) / 2;
+        if (g.table[mid] <= t) lo = mid + 1;
+        else hi = mid;
+      }
+      a = b = 0;
+      if (lo > 0 && lo <= g.num_signals) {
+        a = g.table[lo - 1];
+        b = g.table[lo];
+        a = a < T_ ? a : T_;
+        b = b < T_ ? b : T_;
+      }
+    }
+    if (!(t >= a && t < b)) continue;  // (whatever the table holds: a <= t < b <= num_frames from here on)
+    bool odd = false;
+    for (uint32_t j = lane; j < W; j += 64) {
+      const uint64_t u = t + j - half;  // (below row 0 it wraps: above b)
+      double x = 0.0;
+      if (u >= a && u < b) x = g.f64 ? static_cast<const double*>(g.env)[u] : (double)static_cast<const float*>(g.env)[u];
+      const float y = (float)((double)h[j] * x);
+      ys[j] = y;
+      odd |= !(fabsf(y) < __builtin_huge_valf());
+    }
+    __builtin_amdgcn_wave_barrier();
+    const bool checked = __ballot(odd) != 0;
+    double acc[K], win[K];
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      acc[k] = 0.0;
+      win[k] = (double)ys[l0 + k];
+    }
+    auto walk = [&](auto guard) {
+      for (uint32_t j = 0; j < W; j += K) {
+#pragma unroll
+        for (int s = 0; s < K; ++s) {
+          const double yj = (double)ys[j + s];
+          const double next = (double)ys[j + s + l0 + K];
+#pragma unroll
+          for (int k = 0; k < K; ++k)
+            if (!decltype(guard)::value || j + s + l0 + k < W) acc[k] = __builtin_fma(yj, win[(s + k) % K], acc[k]);
+          win[s] = next;
+        }
+      }
+    };
+    if (checked) walk(std::true_type{});
+    else walk(std::false_type{});
+    __builtin_amdgcn_wave_barrier();
+    if (g.norm == MGX_TEMPOGRAM_NORM_LAG0) {
+      const double s0 = __shfl(acc[0], 0);
+      if (s0 > 0.0 && s0 < __builtin_huge_val()) {
+#pragma unroll
+        for (int k = 0; k < K; ++k) acc[k] = acc[k] / s0;
+      }
+    }
+    float* __restrict__ const o = g.out + i * L;
+#pragma unroll
+    for (int k = 0; k < K; ++k)
+      if (l0 + k < L) o[l0 + k] = (float)acc[k];
+  }
+}
+
+// table[0] = 0, table[1] = num_frames: the one signal of a call without a table, for the summary kernels
+__global__ void tempo_one_signal_kernel(uint64_t* table, uint64_t num_frames) {
+  if (threadIdx.x < 2) table[threadIdx.x] = threadIdx.x ? num_frames : 0;
+}
+
+// blockIdx.x: the signal; one wave
+__global__ __launch_bounds__(64) void tempo_pick_kernel(const double* __restrict__ summary, const double* __restrict__ prior,
+                                                        double gain, uint32_t L, uint32_t* __restrict__ lag) {
+  const uint64_t s = blockIdx.x;
+  const double* __restrict__ const m = summary + (s * MGX_NUM_STATS + MGX_STAT_MEAN) * L;
+  double best = 0.0;
+  uint32_t at = 0;
+  for (uint32_t l = threadIdx.x; l < L; l += 64) {
+    const double gm = gain * m[l];
+    const double one = 1.0 + gm;
+    const double score = one * prior[l];
+    if (score > best) {  // (a NaN compares false)
+      best = score;
+      at = l;
+    }
+  }
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) {
+    const double ob = __shfl_xor(best, d);
+    const uint32_t oa = __shfl_xor(at, d);
+    if (ob > best || (ob == best && oa < at)) {
+      best = ob;
+      at = oa;
+    }
+  }
+  if (threadIdx.x == 0) lag[s] = best > 0.0 ? at : 0u;
+}
+
+template <int K>
+void launch_tempogram_k(TempogramArgs g, hipStream_t stream) {
+  g.strip = ((g.W + K - 1) / K * K + 64 * K + 1) & ~1u;
+  const uint64_t blocks = (g.nrows + 3) / 4;
+  hipLaunchKernelGGL((tempogram_kernel<K>), dim3((unsigned)(blocks < kTempogramBlocks ? blocks : kTempogramBlocks)), dim3(256),
+                     (size_t)g.strip * 4 * sizeof(float), stream, g);
+}
+
+}  // namespace
+
+hipError_t launch_tempogram(const void* env, uint64_t num_frames, bool f64, const uint64_t* table, uint64_t num_signals,
+                            const float* window, uint32_t W, uint32_t L, uint32_t norm, float* out, uint64_t row0, uint64_t nrows,
+                            hipStream_t stream) {
+  if (nrows == 0) return hipSuccess;
+  if (W < 2 || W > MGX_TEMPOGRAM_MAX_WIN || L < 1 || L > W || norm >= MGX_NUM_TEMPOGRAM_NORMS || row0 + nrows > num_frames || !env ||
+      !window || !out)
+    return hipErrorInvalidValue;
+  TempogramArgs g{};
+  g.env = env;
+  g.window = window;
+  g.out = out;
+  g.table = table;
+  g.num_signals = num_signals;
+  g.num_frames = num_frames;
+  g.row0 = row0;
+  g.nrows = nrows;
+  g.W = W;
+  g.L = L;
+  g.norm = norm;
+  g.f64 = f64;
+  const uint32_t k = (L + 63) / 64;  // lags a lane, at least
+  if (k <= 1) launch_tempogram_k<1>(g, stream);
+  else if (k <= 2) launch_tempogram_k<2>(g, stream);
+  else if (k <= 3) launch_tempogram_k<3>(g, stream);
+  else if (k <= 4) launch_tempogram_k<4>(g, stream);
+  else if (k <= 6) launch_tempogram_k<6>(g, stream);
+  else if (k <= 8) launch_tempogram_k<8>(g, stream);
+  else if (k <= 12) launch_tempogram_k<12>(g, stream);
+  else launch_tempogram_k<16>(g, stream);
+  return hipGetLastError();
+}
+
+hipError_t launch_tempo_one_signal(uint64_t* table, uint64_t num_frames, hipStream_t stream) {
+  hipLaunchKernelGGL(tempo_one_signal_kernel, dim3(1), dim3(64), 0, stream, table, num_frames);
+  return hipGetLastError();
+}
+
+hipError_t launch_tempo_pick(const double* summary, const double* prior, double gain, uint32_t L, uint64_t num_signals, uint32_t* lag,
+                             hipStream_t stream) {
+  if (num_signals == 0) return hipSuccess;
+  if (num_signals > 0x7FFFFFFFull || L == 0) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(tempo_pick_kernel, dim3((unsigned)num_signals), dim3(64), 0, stream, summary, prior, gain, L, lag);
+  return hipGetLastError();
+}
+
 }  // namespace mgx
 
 #if MGX_WAVE_TIMES

@@ -255,6 +255,19 @@ hipError_t launch_peaks(const void* env, uint64_t num_frames, bool f64, const ui
 // maximum under MGX_CHROMA_NORM_MAX. All three are float32 arrays in device memory. One launch, asynchronous.
 hipError_t launch_chroma(const float* rows, uint64_t num_frames, uint32_t cols, const float* weights, uint32_t num_chroma,
                          uint32_t norm, float* out, hipStream_t stream);
+// Tempo (mgx_tempogram_device, mgx_tempo_device, mgx_tempo_host; kernels.hip tempogram_kernel, tempo_pick_kernel).
+// launch_tempogram: out[i * L + l] = the autocorrelation of row row0 + i of the one-column envelope env (num_frames
+// values, float32 or float64 as f64 says) under the window (W float32, device) at lag l, for the nrows rows from row0
+// on (row0 + nrows <= num_frames); env is the whole array, out is at row row0. The table as launch_delta reads it.
+// launch_tempo_one_signal: table[0..1] = {0, num_frames}. launch_tempo_pick: lag[s] of the mean row of
+// summary (num_signals x MGX_NUM_STATS x L doubles) under prior (L doubles) and the gain. One launch each, asynchronous.
+constexpr uint64_t kTempoChunkRows = 65536;  // mgx_tempo_device without a tempogram output: rows per pass
+hipError_t launch_tempogram(const void* env, uint64_t num_frames, bool f64, const uint64_t* table, uint64_t num_signals,
+                            const float* window, uint32_t W, uint32_t L, uint32_t norm, float* out, uint64_t row0, uint64_t nrows,
+                            hipStream_t stream);
+hipError_t launch_tempo_one_signal(uint64_t* table, uint64_t num_frames, hipStream_t stream);
+hipError_t launch_tempo_pick(const double* summary, const double* prior, double gain, uint32_t L, uint64_t num_signals, uint32_t* lag,
+                             hipStream_t stream);
 size_t extract_lds_bytes(int n, int ncoef, int nfilt, bool chain);
 size_t lds_image_bytes(int n, int ncoef, int nfilt);  // DevTables::lds_image, a multiple of 16
 hipError_t launch_lds_image(int n, int precision, int mode, const KernelArgs& a, void* image, hipStream_t stream);

@@ -506,6 +506,10 @@ struct mgx_plan {
   // allocation, grown when a call needs more)
   unsigned char* s_chroma = nullptr;
   size_t s_chroma_bytes = 0;
+  // mgx_tempo_host: the window, the prior, the workspace of mgx_tempo_device and the lags (one allocation, grown
+  // when a call needs more)
+  unsigned char* s_tempo = nullptr;
+  size_t s_tempo_bytes = 0;
   hipStream_t s_copy = nullptr, s_comp = nullptr;
   hipEvent_t ev_loaded[2] = {nullptr, nullptr}, ev_done[2] = {nullptr, nullptr}, ev_back[2] = {nullptr, nullptr};
   // small host batches (kSmallBatchFrames): pinned, device-mapped, coherent host buffers
@@ -859,6 +863,7 @@ int mgx_plan_destroy(mgx_plan* p) {
   if (p->s_delta) (void)hipFree(p->s_delta);
   if (p->s_flux) (void)hipFree(p->s_flux);
   if (p->s_chroma) (void)hipFree(p->s_chroma);
+  if (p->s_tempo) (void)hipFree(p->s_tempo);
   if (p->s_copy) (void)hipStreamDestroy(p->s_copy);
   if (p->s_comp) (void)hipStreamDestroy(p->s_comp);
   if (p->s_res) (void)hipStreamDestroy(p->s_res);
@@ -1917,6 +1922,101 @@ int check_peak_params(const mgx_peak_params* pp) {
   return MGX_OK;
 }
 
+// mgx_tempo_host: the tempogram, its pooling and the pick behind the host flux call, over the column of its request
+struct TempoHost {
+  const mgx_tempo_params* params;
+  const float* window;  // host, W
+  const double* prior;  // host, L, or null without lag
+  double* summary;      // host, num_signals x MGX_NUM_STATS x L, or null
+  uint32_t* lag;        // host, num_signals, or null
+};
+
+int check_tempo_params(const mgx_tempo_params* tp) {
+  if (!tp) return fail(MGX_E_INVALID_ARGUMENT, "params is NULL");
+  if (tp->struct_size != sizeof(mgx_tempo_params))
+    return fail(MGX_E_INVALID_ARGUMENT, "mgx_tempo_params.struct_size is %u, expected %zu", tp->struct_size, sizeof(mgx_tempo_params));
+  if (tp->win_length < 2 || tp->win_length > MGX_TEMPOGRAM_MAX_WIN)
+    return fail(MGX_E_INVALID_ARGUMENT, "mgx_tempo_params.win_length is %u, expected 2..%d", tp->win_length, MGX_TEMPOGRAM_MAX_WIN);
+  if (tp->num_lags < 1 || tp->num_lags > tp->win_length)
+    return fail(MGX_E_INVALID_ARGUMENT, "mgx_tempo_params.num_lags is %u, expected 1..%u (win_length)", tp->num_lags, tp->win_length);
+  if (tp->norm >= MGX_NUM_TEMPOGRAM_NORMS)
+    return fail(MGX_E_INVALID_ARGUMENT, "mgx_tempo_params.norm is %u, expected 0..%d", tp->norm, MGX_NUM_TEMPOGRAM_NORMS - 1);
+  if (!(std::isfinite(tp->gain) && tp->gain >= 0)) return fail(MGX_E_INVALID_ARGUMENT, "mgx_tempo_params.gain must be finite and not negative");
+  return MGX_OK;
+}
+
+// The workspace of mgx_tempo_device: the table, the shifts, the partials, the summaries and, without a tempogram
+// output, a pass of rows. S: the signals as the kernels count them (1 without a table).
+struct TempoLayout {
+  uint64_t table, shift, part, result, rows, total;
+};
+
+TempoLayout tempo_layout(uint64_t nframes, uint64_t S, uint32_t L, bool keep_rows) {
+  TempoLayout l{};
+  uint64_t total = 0;
+  auto take = [&total](uint64_t bytes) {
+    const uint64_t at = total;
+    total += (bytes + 255) / 256 * 256;
+    return at;
+  };
+  l.table = take((S + 1) * sizeof(uint64_t));
+  l.shift = take(S * L * sizeof(double));
+  l.part = take((nframes / mgx::kSummaryBlock + S + 1) * mgx::kSummaryWords * L * sizeof(double));
+  l.result = take(S * MGX_NUM_STATS * L * sizeof(double));
+  l.rows = take(keep_rows ? 0 : std::min(nframes, mgx::kTempoChunkRows) * L * sizeof(float));
+  l.total = total;
+  return l;
+}
+
+// mgx_tempo_device after its checks, and the last step of mgx_tempo_host: every pointer a device pointer, S >= 1.
+// pool: the rows are pooled, into `summary` or, when that is null, into the workspace's own summaries
+hipError_t tempo_run(const void* env, uint64_t nframes, bool f64, const uint64_t* raw_table, uint64_t S, const mgx_tempo_params& tp,
+                     const float* window, const double* prior, float* tempogram, double* summary, bool pool, uint32_t* lag,
+                     unsigned char* ws, hipStream_t stream) {
+  const uint32_t W = tp.win_length, L = tp.num_lags;
+  const TempoLayout l = tempo_layout(nframes, S, L, tempogram != nullptr);
+  uint64_t* const table = reinterpret_cast<uint64_t*>(ws + l.table);
+  hipError_t e = hipSuccess;
+  if (nframes > 0)
+    e = raw_table ? mgx::launch_summary_table(raw_table, table, S, nframes, stream) : mgx::launch_tempo_one_signal(table, nframes, stream);
+  if (!pool) {
+    if (e == hipSuccess) e = mgx::launch_tempogram(env, nframes, f64, table, S, window, W, L, tp.norm, tempogram, 0, nframes, stream);
+    return e;
+  }
+  mgx::SummaryArgs a{};
+  a.nfields = 1;
+  a.cols = L;
+  a.f[0].dst = summary ? summary : reinterpret_cast<double*>(ws + l.result);
+  a.f[0].width = L;
+  a.table = table;
+  a.num_signals = S;
+  a.num_frames = nframes;
+  a.nslots = nframes / mgx::kSummaryBlock + S;
+  a.shift = reinterpret_cast<double*>(ws + l.shift);
+  a.part = reinterpret_cast<double*>(ws + l.part);
+  if (tempogram) {
+    if (e == hipSuccess) e = mgx::launch_tempogram(env, nframes, f64, table, S, window, W, L, tp.norm, tempogram, 0, nframes, stream);
+    a.f[0].src = tempogram;
+    a.rows = nframes;
+    if (e == hipSuccess) e = mgx::launch_summary_partial(a, stream);
+  } else {
+    // a pass of rows at a time through the workspace; a block of the summaries that a pass cuts goes on from its
+    // stored state in the next, with the same additions in the same order
+    float* const rows = reinterpret_cast<float*>(ws + l.rows);
+    a.f[0].src = rows;
+    for (uint64_t r0 = 0; r0 < nframes && e == hipSuccess; r0 += mgx::kTempoChunkRows) {
+      const uint64_t cnt = std::min(mgx::kTempoChunkRows, nframes - r0);
+      e = mgx::launch_tempogram(env, nframes, f64, table, S, window, W, L, tp.norm, rows, r0, cnt, stream);
+      a.row0 = r0;
+      a.rows = cnt;
+      if (e == hipSuccess) e = mgx::launch_summary_partial(a, stream);
+    }
+  }
+  if (e == hipSuccess) e = mgx::launch_summary_final(a, stream);
+  if (e == hipSuccess && lag) e = mgx::launch_tempo_pick(a.f[0].dst, prior, tp.gain, L, S, lag, stream);
+  return e;
+}
+
 // mgx_summarize_flux_*: the caller's requests, the fields whose rows the call has to hold, and the requests that
 // are pooled as the columns of one summary launch (each of width 1; destinations the caller's arrays).
 struct FluxReq {
@@ -2021,7 +2121,8 @@ int flux_pool(FluxReq& q, float* const* col, unsigned char* buf, const FluxLayou
 int summarize_host_impl(mgx_plan* p, const float* samples, uint64_t num_samples, const uint64_t* starts, uint64_t nframes,
                         const uint64_t* frame_offsets, uint64_t nsignals, const mgx_outputs* outputs, const mgx_aux_outputs* aux,
                         const mgx_summary_outputs* summary, const mgx_delta_summaries* deltas,
-                        const mgx_flux_request* flux = nullptr, uint32_t nflux = 0, const PeakHost* pick = nullptr);
+                        const mgx_flux_request* flux = nullptr, uint32_t nflux = 0, const PeakHost* pick = nullptr,
+                        const TempoHost* tempo = nullptr);
 
 // mgx_summarize_deltas_workspace_bytes (deltas there, no request) and mgx_summarize_flux_workspace_bytes (deltas or
 // not, requests): the summary call's buffer with the rows of every delta'd or flux'd field kept, then what the
@@ -2374,13 +2475,13 @@ namespace {
 int summarize_host_impl(mgx_plan* p, const float* samples, uint64_t num_samples, const uint64_t* starts, uint64_t nframes,
                         const uint64_t* frame_offsets, uint64_t nsignals, const mgx_outputs* outputs, const mgx_aux_outputs* aux,
                         const mgx_summary_outputs* summary, const mgx_delta_summaries* deltas, const mgx_flux_request* flux,
-                        uint32_t nflux, const PeakHost* pick) {
+                        uint32_t nflux, const PeakHost* pick, const TempoHost* tempo) {
   const mgx_outputs none{};
   mgx::Outputs x;
   DeltaReq q;
   FluxReq fq;
   int rc = check_summary(summary);
-  if (rc || (rc = delta_request(p, deltas, &q)) || (rc = flux_request(p, flux, nflux, nsignals, &fq, pick != nullptr)) ||
+  if (rc || (rc = delta_request(p, deltas, &q)) || (rc = flux_request(p, flux, nflux, nsignals, &fq, pick != nullptr || tempo != nullptr)) ||
       (rc = make_outputs(p, outputs ? outputs : &none, aux, &x)))
     return rc;
   SummaryFields sf;
@@ -2411,6 +2512,8 @@ int summarize_host_impl(mgx_plan* p, const float* samples, uint64_t num_samples,
         std::fill_n(q.sf[k].a.f[i].dst, nsignals * MGX_NUM_STATS * q.sf[k].a.f[i].width, std::nan(""));
     for (uint32_t i = 0; i < fq.sf.a.nfields; ++i) std::fill_n(fq.sf.a.f[i].dst, nsignals * MGX_NUM_STATS, std::nan(""));
     if (pick) std::fill_n(pick->peak_offsets, nsignals + 1, (uint64_t)0);
+    if (tempo && tempo->summary) std::fill_n(tempo->summary, nsignals * MGX_NUM_STATS * tempo->params->num_lags, std::nan(""));
+    if (tempo && tempo->lag) std::fill_n(tempo->lag, nsignals, (uint32_t)0);
     return MGX_OK;
   }
   if (nsignals == 0 || (a.cols == 0 && !q.any() && !fq.any())) return gather_host_chunked(p, samples, starts, nframes, &x, nullptr);
@@ -2453,6 +2556,20 @@ int summarize_host_impl(mgx_plan* p, const float* samples, uint64_t num_samples,
     e = hipMalloc(reinterpret_cast<void**>(&p->s_flux), flux_total);
     if (e != hipSuccess) { p->s_flux = nullptr; return hip_fail(e, "hipMalloc(flux columns)"); }
     p->s_flux_bytes = flux_total;
+  }
+  // mgx_tempo_host's own buffer: the window, the prior, the workspace of mgx_tempo_device and the lags
+  const uint32_t tempo_L = tempo ? tempo->params->num_lags : 0;
+  const uint64_t tempo_win = 0, tempo_prior = MGX_TEMPOGRAM_MAX_WIN * sizeof(float);
+  const uint64_t tempo_ws = tempo_prior + MGX_TEMPOGRAM_MAX_WIN * sizeof(double);
+  const uint64_t tempo_lag = tempo_ws + (tempo ? tempo_layout(nframes, nsignals, tempo_L, false).total : 0);
+  const uint64_t tempo_total = tempo_lag + (nsignals * sizeof(uint32_t) + 255) / 256 * 256;
+  if (tempo && p->s_tempo_bytes < tempo_total) {
+    if (p->s_tempo) (void)hipFree(p->s_tempo);
+    p->s_tempo = nullptr;
+    p->s_tempo_bytes = 0;
+    e = hipMalloc(reinterpret_cast<void**>(&p->s_tempo), tempo_total);
+    if (e != hipSuccess) { p->s_tempo = nullptr; return hip_fail(e, "hipMalloc(tempo buffers)"); }
+    p->s_tempo_bytes = tempo_total;
   }
   if (fq.any()) {
     e = hipMemcpyAsync(p->s_flux + fl.table, frame_offsets, (nsignals + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, p->s_comp);
@@ -2591,6 +2708,25 @@ int summarize_host_impl(mgx_plan* p, const float* samples, uint64_t num_samples,
       if (e == hipSuccess) e = hipStreamSynchronize(p->s_comp);
       const uint64_t total = e == hipSuccess ? std::min(pick->peak_offsets[nsignals], pick_cap) : 0;
       if (total > 0) e = hipMemcpyAsync(pick->peaks, po.peaks, total * 8, hipMemcpyDeviceToHost, p->s_comp);
+    }
+    if (tempo && rc == MGX_OK && e == hipSuccess) {
+      // the tempogram of the request's column where it lies, a pass of rows at a time, pooled and picked; the
+      // summaries and the lags alone cross back
+      const mgx_tempo_params& tp = *tempo->params;
+      const TempoLayout tl = tempo_layout(nframes, nsignals, tempo_L, false);
+      e = hipMemcpyAsync(p->s_tempo + tempo_win, tempo->window, tp.win_length * sizeof(float), hipMemcpyHostToDevice, p->s_comp);
+      if (e == hipSuccess && tempo->lag)
+        e = hipMemcpyAsync(p->s_tempo + tempo_prior, tempo->prior, tp.num_lags * sizeof(double), hipMemcpyHostToDevice, p->s_comp);
+      uint32_t* const dlag = tempo->lag ? reinterpret_cast<uint32_t*>(p->s_tempo + tempo_lag) : nullptr;
+      if (e == hipSuccess)
+        e = tempo_run(col[0], nframes, false, reinterpret_cast<const uint64_t*>(p->s_flux + fl.table), nsignals, tp,
+                      reinterpret_cast<const float*>(p->s_tempo + tempo_win), reinterpret_cast<const double*>(p->s_tempo + tempo_prior),
+                      nullptr, nullptr, true, dlag, p->s_tempo + tempo_ws, p->s_comp);
+      if (e == hipSuccess && tempo->summary)
+        e = hipMemcpyAsync(tempo->summary, p->s_tempo + tempo_ws + tl.result, nsignals * MGX_NUM_STATS * tp.num_lags * sizeof(double),
+                           hipMemcpyDeviceToHost, p->s_comp);
+      if (e == hipSuccess && tempo->lag)
+        e = hipMemcpyAsync(tempo->lag, dlag, nsignals * sizeof(uint32_t), hipMemcpyDeviceToHost, p->s_comp);
     }
   }
   const hipError_t es = hipStreamSynchronize(p->s_comp);
@@ -2782,6 +2918,122 @@ int mgx_chroma_host(mgx_plan* p, const float* samples, uint64_t num_samples, con
   const hipError_t es = hipStreamSynchronize(p->s_comp);
   if (e == hipSuccess) e = es;
   return e == hipSuccess ? MGX_OK : hip_fail(e, "chroma and summary kernels and copies");
+}
+
+void mgx_tempo_params_init(mgx_tempo_params* t) {
+  if (!t) return;
+  memset(t, 0, sizeof *t);
+  t->struct_size = sizeof *t;
+  t->win_length = 384;
+  t->num_lags = 384;
+  t->norm = MGX_TEMPOGRAM_NORM_LAG0;
+  t->gain = 1e6;
+}
+
+int mgx_tempogram_window(uint32_t W, float* h) {
+  if (W < 2 || W > MGX_TEMPOGRAM_MAX_WIN) return fail(MGX_E_INVALID_ARGUMENT, "win_length is %u, expected 2..%d", W, MGX_TEMPOGRAM_MAX_WIN);
+  if (!h) return fail(MGX_E_INVALID_ARGUMENT, "window is NULL");
+  const double two_pi = 6.283185307179586476925286766559;
+  for (uint32_t j = 0; j < W; ++j) h[j] = (float)(0.5 - 0.5 * std::cos(two_pi * (double)j / (double)W));
+  return MGX_OK;
+}
+
+int mgx_tempo_prior(double frame_rate, double start_bpm, double std_octaves, double max_bpm, uint32_t L, double* prior) {
+  if (!(std::isfinite(frame_rate) && frame_rate > 0)) return fail(MGX_E_INVALID_ARGUMENT, "frame_rate must be finite and positive");
+  if (!(std::isfinite(start_bpm) && start_bpm > 0)) return fail(MGX_E_INVALID_ARGUMENT, "start_bpm must be finite and positive");
+  if (!(std::isfinite(std_octaves) && std_octaves > 0)) return fail(MGX_E_INVALID_ARGUMENT, "std_octaves must be finite and positive");
+  if (!(max_bpm >= 0)) return fail(MGX_E_INVALID_ARGUMENT, "max_bpm must not be negative or NaN (0: no limit)");
+  if (L == 0) return fail(MGX_E_INVALID_ARGUMENT, "num_lags is 0");
+  if (!prior) return fail(MGX_E_INVALID_ARGUMENT, "prior is NULL");
+  prior[0] = 0.0;
+  const double l2s = std::log2(start_bpm);
+  for (uint32_t l = 1; l < L; ++l) {
+    const double bpm = 60.0 * frame_rate / (double)l;
+    if (max_bpm > 0 && bpm > max_bpm) {
+      prior[l] = 0.0;
+      continue;
+    }
+    const double z = (std::log2(bpm) - l2s) / std_octaves;
+    prior[l] = std::exp(-0.5 * (z * z));
+  }
+  return MGX_OK;
+}
+
+// what mgx_tempogram_device and mgx_tempo_device refuse about the arguments they share
+static int check_tempogram_args(const void* envelope, uint64_t num_frames, uint32_t envelope_f64, const uint64_t* frame_offsets,
+                                uint64_t num_signals, const float* window, uint32_t W, uint32_t L, uint32_t norm) {
+  if (envelope_f64 > 1) return fail(MGX_E_INVALID_ARGUMENT, "envelope_f64 is %u, expected 0 or 1", envelope_f64);
+  if (W < 2 || W > MGX_TEMPOGRAM_MAX_WIN) return fail(MGX_E_INVALID_ARGUMENT, "win_length is %u, expected 2..%d", W, MGX_TEMPOGRAM_MAX_WIN);
+  if (L < 1 || L > W) return fail(MGX_E_INVALID_ARGUMENT, "num_lags is %u, expected 1..%u (win_length)", L, W);
+  if (norm >= MGX_NUM_TEMPOGRAM_NORMS) return fail(MGX_E_INVALID_ARGUMENT, "norm is %u, expected 0..%d", norm, MGX_NUM_TEMPOGRAM_NORMS - 1);
+  if (!window) return fail(MGX_E_INVALID_ARGUMENT, "window is NULL");
+  if (num_signals > 0 && !frame_offsets) return fail(MGX_E_INVALID_ARGUMENT, "frame_offsets is NULL");
+  if (num_frames > 0 && !envelope) return fail(MGX_E_INVALID_ARGUMENT, "envelope is NULL");
+  return MGX_OK;
+}
+
+int mgx_tempogram_device(const void* envelope, uint64_t num_frames, uint32_t envelope_f64, const uint64_t* frame_offsets,
+                         uint64_t num_signals, const float* window, uint32_t W, uint32_t L, uint32_t norm, float* tempogram,
+                         void* stream) {
+  const int rc = check_tempogram_args(envelope, num_frames, envelope_f64, frame_offsets, num_signals, window, W, L, norm);
+  if (rc) return rc;
+  if (!tempogram) return fail(MGX_E_INVALID_ARGUMENT, "tempogram is NULL");
+  if (tempogram == envelope || tempogram == window)
+    return fail(MGX_E_INVALID_ARGUMENT, "tempogram is the same array as %s", tempogram == envelope ? "envelope" : "window");
+  if (num_frames == 0 || (frame_offsets && num_signals == 0)) return MGX_OK;
+  const hipError_t e = mgx::launch_tempogram(envelope, num_frames, envelope_f64 != 0, frame_offsets, num_signals, window, W, L, norm,
+                                             tempogram, 0, num_frames, (hipStream_t)stream);
+  return e == hipSuccess ? MGX_OK : hip_fail(e, "tempogram kernel launch");
+}
+
+int mgx_tempo_workspace_bytes(uint64_t num_frames, uint64_t num_signals, const mgx_tempo_params* params, uint32_t keep_rows,
+                              uint64_t* bytes) {
+  const int rc = check_tempo_params(params);
+  if (rc) return rc;
+  if (keep_rows > 1) return fail(MGX_E_INVALID_ARGUMENT, "keep_rows is %u, expected 0 or 1", keep_rows);
+  if (!bytes) return fail(MGX_E_INVALID_ARGUMENT, "bytes is NULL");
+  *bytes = tempo_layout(num_frames, num_signals ? num_signals : 1, params->num_lags, keep_rows != 0).total;
+  return MGX_OK;
+}
+
+int mgx_tempo_device(const void* envelope, uint64_t num_frames, uint32_t envelope_f64, const uint64_t* frame_offsets,
+                     uint64_t num_signals, const mgx_tempo_params* params, const float* window, const double* prior, float* tempogram,
+                     double* summary, uint32_t* lag, void* workspace, uint64_t workspace_bytes, void* stream) {
+  int rc = check_tempo_params(params);
+  if (rc || (rc = check_tempogram_args(envelope, num_frames, envelope_f64, frame_offsets, num_signals, window, params->win_length,
+                                       params->num_lags, params->norm)))
+    return rc;
+  if (!tempogram && !summary && !lag) return fail(MGX_E_INVALID_ARGUMENT, "tempogram, summary and lag are all NULL");
+  if (lag && !prior) return fail(MGX_E_INVALID_ARGUMENT, "lag is set without prior");
+  if (tempogram && (tempogram == envelope || tempogram == window))
+    return fail(MGX_E_INVALID_ARGUMENT, "tempogram is the same array as %s", tempogram == envelope ? "envelope" : "window");
+  const uint64_t S = frame_offsets ? num_signals : 1;
+  const uint64_t need = tempo_layout(num_frames, S ? S : 1, params->num_lags, tempogram != nullptr).total;
+  if (workspace_bytes < need || !workspace)
+    return fail(MGX_E_INVALID_ARGUMENT, "the workspace holds %llu bytes, the call needs %llu (mgx_tempo_workspace_bytes)",
+                (unsigned long long)(workspace ? workspace_bytes : 0), (unsigned long long)need);
+  if (reinterpret_cast<uintptr_t>(workspace) % 256 != 0) return fail(MGX_E_INVALID_ARGUMENT, "the workspace is not 256-byte aligned");
+  if (S == 0) return MGX_OK;  // (a table of no signals: no row, no summary, no lag)
+  const hipError_t e = tempo_run(envelope, num_frames, envelope_f64 != 0, frame_offsets, S, *params, window, prior, tempogram, summary,
+                                 summary || lag, lag, static_cast<unsigned char*>(workspace), (hipStream_t)stream);
+  return e == hipSuccess ? MGX_OK : hip_fail(e, "tempo kernel launch");
+}
+
+int mgx_tempo_host(mgx_plan* p, const float* samples, uint64_t num_samples, const uint64_t* starts, uint64_t nframes,
+                   const uint64_t* frame_offsets, uint64_t nsignals, const mgx_flux_request* flux, const mgx_tempo_params* params,
+                   const float* window, const double* prior, double* summary, uint32_t* lag) {
+  const int rc = check_tempo_params(params);
+  if (rc) return rc;
+  if (nsignals == 0) return fail(MGX_E_INVALID_ARGUMENT, "num_signals is 0: a tempo is a clip's");
+  if (!flux) return fail(MGX_E_INVALID_ARGUMENT, "flux is NULL");
+  if (!window) return fail(MGX_E_INVALID_ARGUMENT, "window is NULL");
+  if (!summary && !lag) return fail(MGX_E_INVALID_ARGUMENT, "summary and lag are both NULL");
+  if (lag && !prior) return fail(MGX_E_INVALID_ARGUMENT, "lag is set without prior");
+  mgx_summary_outputs none{};
+  none.struct_size = sizeof(none);
+  const TempoHost th{params, window, prior, summary, lag};
+  return summarize_host_impl(p, samples, num_samples, starts, nframes, frame_offsets, nsignals, nullptr, nullptr, &none, nullptr, flux, 1,
+                             nullptr, &th);
 }
 
 int mgx_wav_parse(const void* bytes, uint64_t len, mgx_wav_info* info) {

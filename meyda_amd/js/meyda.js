@@ -40,6 +40,13 @@
 //                                   frameOffsets[, summaries]}
 //   Meyda.chromaFilterBank(bufferSize, sampleRate[, options])
 //                                   the numChroma x bufferSize / 2 chroma filter bank (host only)
+//   getSignalTempo(signals, {hopSize, feature, mode, lag, winLength, numLags, norm, gain, startBpm, stdOctaves,
+//                            maxBpm, window, prior, mean, envelope}) / getSignalTempoAsync(...)
+//                                   the tempo of every signal: the autocorrelation tempogram of a feature's spectral
+//                                   flux, pooled per signal, and the lag a tempo prior picks, all on the device;
+//                                   {frameOffsets, lag, bpm, numLags[, mean][, envelope]}
+//   Meyda.tempogramWindow(winLength), Meyda.tempoPrior(frameRate, numLags[, {startBpm, stdOctaves, maxBpm}])
+//                                   the periodic Hann window and the log-normal tempo prior (host only)
 //   Meyda.signalsFrameStarts(lengths, bufferSize, hopSize)
 //                                   {starts, frameOffsets} of signals stored one after another
 //   Meyda.readWav(wavBytes)         the header: {pcmFormat, channels, sampleRate, sampleFrames, ...}
@@ -508,6 +515,48 @@ class Meyda {
       .then((r) => onsetResult(r, c.frameOffsets));
   }
 
+  // The tempo of getBatchSignals' signals (librosa.feature.tempogram and librosa.feature.tempo on the device): the
+  // spectral flux of options.feature (default 'melBands'; mode and lag as in getSignalOnsets) at options.hopSize is the
+  // onset envelope; every buffer's row of the tempogram is the autocorrelation of the winLength (384) envelope values
+  // around it under a window (options.window, a Float32Array of winLength, or Meyda.tempogramWindow) at the lags
+  // 0 .. numLags - 1 (numLags defaults to winLength), divided by lag 0 (norm 'lag0'; 'none': the sums) in the fixed
+  // order of include/meyda_gpu.h; the rows are pooled per signal and the lag is the one whose score
+  // (1 + gain mean(lag)) prior(lag) is largest (gain 1e6; options.prior, a Float64Array of numLags, or
+  // Meyda.tempoPrior of the frame rate sampleRate / hopSize with startBpm 120, stdOctaves 1, maxBpm 320). Returns
+  // {frameOffsets, lag, bpm, numLags}: lag a Uint32Array and bpm a Float64Array of signals.length, bpm = 60 frameRate /
+  // lag, NaN where the lag is 0 (no tempo: a signal without buffers); with mean: true also `mean`, the mean tempogram
+  // row of every signal (a Float64Array of signals.length x numLags), with envelope: true the flux per buffer. Only
+  // these cross back from the device.
+  getSignalTempo(signals, options) {
+    const o = tempoOptions(options, this.sampleRate);
+    const c = this._concatSignals(signals, o.hopSize);
+    return tempoResult(addon.tempoGather(this._plan(), c.samples, c.starts, c.frameOffsets, o.addon), c.frameOffsets, o);
+  }
+
+  getSignalTempoAsync(signals, options) {
+    const o = tempoOptions(options, this.sampleRate);
+    const c = this._concatSignals(signals, o.hopSize);
+    return this._runAsync((plan) => addon.tempoGatherAsync(plan, c.samples, c.starts, c.frameOffsets, o.addon))
+      .then((r) => tempoResult(r, c.frameOffsets, o));
+  }
+
+  // The periodic Hann window of the tempogram, 0.5 - 0.5 cos(2 pi j / winLength): a Float32Array. Host only.
+  static tempogramWindow(winLength) {
+    if (!Number.isInteger(winLength) || winLength < 2 || winLength > 1024) throw new RangeError('winLength must be an integer from 2 to 1024');
+    return addon.tempogramWindow(winLength);
+  }
+
+  // librosa's log-normal tempo prior over the lags 0 .. numLags - 1 of an envelope of frameRate rows a second, without
+  // its constant factor: 0 at lag 0 and above maxBpm (0: no limit); options {startBpm: 120, stdOctaves: 1, maxBpm: 320}.
+  // A Float64Array. Host only.
+  static tempoPrior(frameRate, numLags, options) {
+    if (typeof frameRate !== 'number' || !(frameRate > 0) || !Number.isFinite(frameRate)) {
+      throw new RangeError('frameRate must be a positive finite number');
+    }
+    if (!Number.isInteger(numLags) || numLags < 1 || numLags > 1024) throw new RangeError('numLags must be an integer from 1 to 1024');
+    return addon.tempoPrior(frameRate, numLags, tempoPriorOptions(options));
+  }
+
   // The chroma of getBatchSignals' signals (later Meyda's `chroma`): every buffer's amplitude spectrum times a
   // numChroma x bufferSize / 2 filter bank, each product sum added in the fixed order of include/meyda_gpu.h, then
   // divided by the buffer's largest value (norm 'max', Meyda's; 'none': the sums). The bank is options.weights (a
@@ -830,6 +879,67 @@ function onsetOptions(options) {
   if (typeof o.delta !== 'number') throw new TypeError('delta must be a number');
   if (Number.isNaN(o.delta)) throw new RangeError('delta must not be NaN');
   return o;
+}
+
+// Meyda.tempoPrior's options as the addon takes them
+const TEMPOGRAM_NORMS = { none: 0, lag0: 1 };
+function tempoPriorOptions(options) {
+  if (options === undefined || options === null) options = {};
+  if (typeof options !== 'object') throw new TypeError('options must be an object: {startBpm, stdOctaves, maxBpm}');
+  const o = { startBpm: options.startBpm === undefined ? 120 : options.startBpm,
+    stdOctaves: options.stdOctaves === undefined ? 1 : options.stdOctaves,
+    maxBpm: options.maxBpm === undefined ? 320 : options.maxBpm };
+  for (const k of ['startBpm', 'stdOctaves']) {
+    if (typeof o[k] !== 'number' || !Number.isFinite(o[k]) || !(o[k] > 0)) throw new RangeError(k + ' must be a positive finite number');
+  }
+  if (typeof o.maxBpm !== 'number' || !Number.isFinite(o.maxBpm) || o.maxBpm < 0) throw new RangeError('maxBpm must be a finite number, 0 or above');
+  return o;
+}
+
+// getSignalTempo's options: the hop, the frame rate, and what the addon takes (the flux in the library's numbers, the
+// window and the prior as arrays)
+function tempoOptions(options, sampleRate) {
+  if (options === undefined || options === null || typeof options !== 'object') {
+    throw new TypeError('options must be an object: {hopSize, feature, mode, lag, winLength, numLags, norm, gain, startBpm, stdOctaves, ' +
+      'maxBpm, window, prior, mean, envelope}');
+  }
+  const hopSize = options.hopSize;
+  if (!Number.isInteger(hopSize) || hopSize < 1) throw new RangeError('hopSize must be a positive integer');
+  const feature = options.feature === undefined ? 'melBands' : options.feature;
+  if (!Object.prototype.hasOwnProperty.call(FLUX_FIELDS, feature)) throw new TypeError("'" + feature + "' has no flux");
+  const mode = options.mode === undefined ? 'rectified' : options.mode;
+  if (!Object.prototype.hasOwnProperty.call(FLUX_MODES, mode)) throw new RangeError("flux mode must be 'rectified', 'l1' or 'l2'");
+  const lag = options.lag === undefined ? 1 : options.lag;
+  if (!Number.isInteger(lag) || lag < 1 || lag > 8) throw new RangeError('flux lag must be an integer from 1 to 8');
+  const winLength = options.winLength === undefined ? 384 : options.winLength;
+  if (!Number.isInteger(winLength) || winLength < 2 || winLength > 1024) throw new RangeError('winLength must be an integer from 2 to 1024');
+  const numLags = options.numLags === undefined ? winLength : options.numLags;
+  if (!Number.isInteger(numLags) || numLags < 1 || numLags > winLength) throw new RangeError('numLags must be an integer from 1 to winLength');
+  const norm = options.norm === undefined ? 'lag0' : options.norm;
+  if (!Object.prototype.hasOwnProperty.call(TEMPOGRAM_NORMS, norm)) throw new RangeError("tempogram norm must be 'lag0' or 'none'");
+  const gain = options.gain === undefined ? 1e6 : options.gain;
+  if (typeof gain !== 'number' || !Number.isFinite(gain) || gain < 0) throw new RangeError('gain must be a finite number, 0 or above');
+  const frameRate = sampleRate / hopSize;
+  let window = options.window, prior = options.prior;
+  if (window === undefined || window === null) window = addon.tempogramWindow(winLength);
+  else if (!(window instanceof Float32Array) || window.length !== winLength) throw new TypeError('window must be a Float32Array of winLength values');
+  if (prior === undefined || prior === null) prior = addon.tempoPrior(frameRate, numLags, tempoPriorOptions(options));
+  else if (!(prior instanceof Float64Array) || prior.length !== numLags) throw new TypeError('prior must be a Float64Array of numLags values');
+  return { hopSize, frameRate, mean: !!options.mean,
+    addon: { field: FLUX_FIELDS[feature], mode: FLUX_MODES[mode], lag, winLength, numLags, norm: TEMPOGRAM_NORMS[norm], gain, window, prior,
+      mean: !!options.mean, envelope: !!options.envelope } };
+}
+
+function tempoResult(raw, frameOffsets, o) {
+  const S = frameOffsets.length - 1, L = raw.numLags;
+  const r = { frameOffsets, lag: raw.lag, bpm: new Float64Array(S), numLags: L };
+  for (let s = 0; s < S; ++s) r.bpm[s] = raw.lag[s] > 0 ? 60 * o.frameRate / raw.lag[s] : NaN;
+  if (o.mean && raw.summary) {
+    r.mean = new Float64Array(S * L);
+    for (let s = 0; s < S; ++s) r.mean.set(raw.summary.subarray(s * STATS.length * L, (s * STATS.length + 1) * L), s * L);
+  }
+  if (raw.envelope) r.envelope = raw.envelope;
+  return r;
 }
 
 // Meyda.chromaFilterBank's options as the addon takes them

@@ -1,0 +1,48 @@
+"""getSignalTempo / getSignalTempoAsync through the JavaScript facade (meyda_amd/js/meyda.js) and the N-API addon on
+the GPU: the lags, the mean tempogram rows and the envelope of three signals equal Plan.tempo_signals (mgx_tempo_host
+through ctypes) on the same signals bit for bit -- this test writes the binding's values to files,
+tests/js/tempo_gpu.js reads and compares them --, and the async form equals the synchronous one."""
+import os
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+ADDON = os.path.join(ROOT, "meyda_amd", "addon", "meyda_napi.node")
+
+
+@pytest.mark.gpu
+def test_facade_tempo_on_gpu(tmp_path):
+    if not shutil.which("node"):
+        pytest.skip("node is not installed")
+    if not os.path.exists(ADDON):
+        pytest.skip("N-API addon not built (make -C meyda_amd/addon)")
+    from meyda_amd import capi
+    n, hop = 256, 64
+    rng = np.random.default_rng(67)
+    x = rng.uniform(-0.05, 0.05, 1000 * hop + 3 * n).astype(np.float32)
+    for at in range(0, x.size - n, 24 * hop):  # a click every 24 buffers
+        x[at:at + 32] += rng.uniform(-1, 1, 32).astype(np.float32)
+    x.tofile(tmp_path / "signal.f32")
+    cuts = [0, 600 * hop + n + 7, 600 * hop + n + 7 + n - 1, x.size]  # (as tests/js/tempo_gpu.js cuts them)
+    signals = [x[cuts[s]:cuts[s + 1]] for s in range(3)]
+    plan = capi.Plan(buffer_size=n, scalar_f64=True, num_mel_bands=40)  # (the facade's plans: scalarF64)
+    try:
+        # (689 rows a second: the prior is centred on the clicks' 24 rows and has no upper limit, as tests/js/tempo_gpu.js asks)
+        res = plan.tempo_signals(signals, hop, win_length=64, num_lags=48, mean=True, envelope=True, start_bpm=1722.65625, max_bpm=0.0)
+        dflt = plan.tempo_signals(signals, hop)
+    finally:
+        plan.close()
+    fo = res["frame_offsets"]
+    assert list(fo[:3]) == [0, 601, 601] and res["lag"].shape == (3,) and res["summary"].shape == (3, 4, 48)
+    assert res["lag"][1] == 0 and np.isnan(res["summary"][1]).all() and (res["lag"][[0, 2]] > 0).all()
+    res["lag"].tofile(tmp_path / "tempo.lag.u32")
+    np.ascontiguousarray(res["summary"][:, 0, :]).tofile(tmp_path / "tempo.mean.f64")
+    res["envelope"].tofile(tmp_path / "tempo.envelope.f32")
+    dflt["lag"].tofile(tmp_path / "tempo384.lag.u32")
+    r = subprocess.run(["node", os.path.join(ROOT, "tests", "js", "tempo_gpu.js"), str(tmp_path / "signal.f32"), str(tmp_path)],
+                       capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
+    assert "tempo_gpu: 4 checks passed" in r.stdout
