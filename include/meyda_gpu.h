@@ -45,6 +45,9 @@
  *   mgx_tempogram_device, tempo: the local autocorrelation of a       no counterpart: librosa.feature.tempogram
  *   mgx_tempo_device,    clip's envelope per frame, pooled per clip,  and librosa.feature.tempo in a host
  *   mgx_tempo_host       and the lag a tempo prior picks              application
+ *   mgx_beat_tables,     beats: a clip's beats placed on its         no counterpart: librosa.beat.beat_track's
+ *   mgx_beats_device,    envelope at the tempo's lag by dynamic      tracker in a host application
+ *   mgx_beats_host       programming
  *   mgx_group_*          several devices, RCCL gather of the        src/meyda.js:17-97 (one plan
  *                        per-frame records to the root device       per device), :69-91 (buffers
  *                                                                   are independent: shardable)
@@ -947,6 +950,106 @@ int mgx_tempo_host(mgx_plan* plan, const float* samples, uint64_t num_samples, c
                    uint64_t num_frames, const uint64_t* frame_offsets, uint64_t num_signals,
                    const mgx_flux_request* flux, const mgx_tempo_params* params, const float* window,
                    const double* prior, double* summary, uint32_t* lag);
+
+/* ---- Beats: a clip's beats by dynamic programming on the device ------------------------------------
+ * Replaces, in a host application, the loop that places the beats on the onset envelope after it was copied back
+ * (librosa.beat.beat_track's tracker: a local score, a cumulative score with a log-squared penalty on the distance
+ * to the beat before, the last beat at a late local maximum, the chain of back links, a trim of weak ends). With it,
+ * envelope -> tempo -> beats -> beat-aligned starts -> a second gather launch runs without a host round trip. The
+ * period is the lag mgx_tempo_device writes: librosa's round(60 frame_rate / bpm) with bpm = 60 frame_rate / lag. The
+ * reference snapshot has no counterpart, so the definition is stated here in full. Like the statistics, the deltas,
+ * the flux, the peaks, the chroma and the tempo it is no feature: MGX_NUM_FEATURES, the name table and every struct
+ * above are as they were.
+ *
+ * The tables (mgx_beat_tables; host only, no device is touched; the caller's, as chroma's bank and the tempogram's
+ * window are). P = max_period, 1 .. MGX_BEAT_MAX_PERIOD; tightness finite and > 0 (librosa: 100).
+ *   gauss: (P + 1)(P + 2) / 2 float32. Entry p (p + 1) / 2 + k, 1 <= p <= P, k = 0 .. p, is exp(-0.5 (32 k / p)^2),
+ *     formed in float64 and rounded once to float32; entry 0 is 1. Underflow to +0 is kept.
+ *   penalty: (P + 1)^2 float64. Entry p^2 + d, d = 0 .. 2 p, is -tightness (ln(d / p))^2 for lo(p) <= d <= 2 p -- one
+ *     division, one log, one square, one product, in that order -- and -Infinity for d < lo(p) and for p = 0.
+ *   lo(p) is p / 2 rounded to the nearest integer, ties to even, and at least 1 (h = p div 2; if p is odd,
+ *     h += h & 1; lo = max(1, h)): librosa's np.round(period / 2).
+ *
+ * The operator. A signal owns rows [a, b) of a one-column envelope x of num_frames values, float32 or float64, taken
+ * as float64; n = b - a; p is the signal's entry of `period`. A signal has no beats when n < 2, p = 0 or p > P, and
+ * wherever the steps below say so. (local_score and cum_score are +0 in the rows of a signal that stops before
+ * step 3, and the values of steps 3 and 5 otherwise.)
+ *
+ *   1. Scale. 64 partials start at +0; for i = 0 .. n - 1 ascending, P[i mod 64] += x(a + i); then P[l] += P[l + h]
+ *      for l < h, with h = 32, 16, .., 1. S = P[0], mean = S / n. Q is formed the same way from e e with
+ *      e = x - mean, the product rounded and then added. sd = sqrt(Q / (n - 1)), one correctly rounded division and
+ *      one correctly rounded root. No beats unless sd > 0 and sd is finite (so none with a NaN or infinite row).
+ *   2. Normalise. xn(t) = x(t) / sd in float64, rounded once to float32; outside [a, b), xn~ is +0.
+ *   3. Local score. ls(t) starts at +0; for k = -p .. p ascending, ls(t) += gauss(p, |k|) xn~(t + k): the product of
+ *      two float32 values is exact in float64, each addition is rounded once. (The terms outside [a, b) add +0 to a
+ *      sum that is never -0, so they may be skipped. |xn| stays near sqrt(n) at most, so it is finite, and a weight
+ *      that underflowed to +0 adds a signed zero likewise.)
+ *   4. Start. lsmax is a scan of ls over [a, b) from -Infinity with `>`; thr = 0.01 lsmax; t0 is the first t for
+ *      which ls(t) < thr is false, or b.
+ *   5. Recurrence. For t = a .. b - 1 ascending: best = -Infinity, arg = none; for d = 2 p down to lo(p):
+ *      c = penalty(p, d) + C~(t - d), C~(u) = +0 for u < a; if c > best then best = c, arg = d (on a tie the larger d
+ *      wins, a NaN never wins). C(t) = ls(t) + best. B(t) = t - arg if t >= t0, arg exists and t - arg >= a; else none.
+ *   6. Tail. M(t), a local maximum: for a < t < b - 1, C(t) > C(t - 1) and C(t) >= C(t + 1); M(a) is false; M(b - 1) is
+ *      C(b - 1) > C(b - 2). Of the m values C(t) with M(t) in ascending order v (m = 0: no beats), med = v[(m - 1) / 2]
+ *      for odd m and (v[m / 2 - 1] + v[m / 2]) 0.5 for even m. tail is the largest t with M(t) and 2 C(t) > med; none:
+ *      no beats.
+ *   7. Chain. b_0 = tail, b_(i+1) = B(b_i) until none: K rows.
+ *   8. Trim. s_i = (0.5 ls(the earlier neighbour in the chain) + ls(b_i)) + 0.5 ls(the later neighbour), a missing
+ *      neighbour contributing +0. trim 0: thr = +0. trim 1: R starts at +0 and over the chain in the order of step 7
+ *      (descending rows) R += s s, the product rounded and then added; thr = 0.5 sqrt(R / K). A chain row is valid if
+ *      s_i > thr; the beats are the chain rows between the lowest and the highest valid row, inclusive; none valid:
+ *      no beats.
+ *
+ * Rows of no signal are never beats and are never written. No atomics: every call below, a repeated call, a graph
+ * replay and any grid give the same values. */
+#define MGX_BEAT_MAX_PERIOD 1023
+typedef struct mgx_beat_params {
+  uint32_t struct_size;  /* = sizeof(mgx_beat_params), 16; anything else: MGX_E_INVALID_ARGUMENT */
+  uint32_t max_period;   /* P, 1 .. MGX_BEAT_MAX_PERIOD: the tables' size; 1023 */
+  uint32_t trim;         /* 0 or 1; 1 */
+  uint32_t reserved;
+} mgx_beat_params;
+void mgx_beat_params_init(mgx_beat_params* params);
+/* MGX_E_INVALID_ARGUMENT: max_period outside 1 .. MGX_BEAT_MAX_PERIOD, a tightness that is not finite or not
+ * positive, NULL gauss or penalty. */
+int mgx_beat_tables(uint32_t max_period, double tightness, float* gauss /* (P + 1)(P + 2) / 2 */,
+                    double* penalty /* (P + 1)^2 */);
+/* The bytes mgx_beats_device works in: a multiple of 256, non-decreasing in both arguments (the picker's bitmaps,
+ * two doubles and a back link per row, three words per signal). Host only. */
+int mgx_beats_workspace_bytes(uint64_t num_frames, uint64_t num_signals, uint64_t* bytes);
+
+/* The tracker on device arrays; no plan: asynchronous on `stream`, no allocation, no host-side state, capturable.
+ * Every pointer is a device pointer. envelope_f64: 0 float32, 1 float64. S is num_signals, or 1 when frame_offsets
+ * is NULL and num_signals is 0: one signal [0, num_frames). period: S uint32 (the lag array of mgx_tempo_device).
+ * gauss and penalty: mgx_beat_tables of params->max_period, on the device. local_score, cum_score: optional,
+ * num_frames doubles each, rows of no signal untouched. The table is read as mgx_peaks_device reads it, and `out` has
+ * the picker's exact semantics: the true counts in peak_offsets, the first min(total, capacity) rows in peaks,
+ * peak_starts from starts, mask 1 on a beat and 0 on another row of a signal. num_frames = 0 writes peak_offsets (all
+ * 0) and nothing else.
+ * MGX_E_INVALID_ARGUMENT before any launch: a bad struct_size in either struct, max_period outside 1 ..
+ * MGX_BEAT_MAX_PERIOD, trim > 1, envelope_f64 > 1, NULL period, gauss or penalty, mask, peak_offsets and peaks all
+ * NULL, peaks set with capacity 0, peak_starts without starts or without peaks, num_signals > 0 with NULL
+ * frame_offsets, NULL envelope with num_frames > 0, a workspace smaller than mgx_beats_workspace_bytes or not
+ * 256-byte aligned. */
+int mgx_beats_device(const void* envelope, uint64_t num_frames, uint32_t envelope_f64, const uint64_t* frame_offsets,
+                     uint64_t num_signals, const uint32_t* period, const mgx_beat_params* params, const float* gauss,
+                     const double* penalty, double* local_score, double* cum_score, const mgx_peak_outputs* out,
+                     void* workspace, uint64_t workspace_bytes, void* stream);
+
+/* Host pointers throughout: mgx_tempo_host's route (the flux of the one request `flux`, its tempogram pooled per
+ * clip, the pick under `prior`) with the tracker behind it. The flux column and the lags stay on the device, and the
+ * lag array is handed to the tracker as `period`; the tables (mgx_beat_tables of params->max_period) are uploaded once
+ * per call. flux->per_frame and flux->summary are honoured as there. Only lag (S uint32, optional), peak_offsets
+ * (S + 1, non-NULL: the true counts), the first min(total, capacity) beats (rows of the whole array, ascending; peaks
+ * NULL with capacity 0 for the counts alone) and what the request names cross back. The result equals
+ * mgx_beats_device on the column and the lags the separate host calls return, wherever the chunks end.
+ * MGX_E_INVALID_ARGUMENT: tempo->num_lags - 1 > params->max_period (a lag the tables do not hold), NULL prior or
+ * tables, num_signals = 0, and every refusal of mgx_tempo_host and mgx_onsets_host about the arguments they share. */
+int mgx_beats_host(mgx_plan* plan, const float* samples, uint64_t num_samples, const uint64_t* starts,
+                   uint64_t num_frames, const uint64_t* frame_offsets, uint64_t num_signals,
+                   const mgx_flux_request* flux, const mgx_tempo_params* tempo, const float* window, const double* prior,
+                   const mgx_beat_params* params, const float* gauss, const double* penalty, uint32_t* lag,
+                   uint64_t* peak_offsets, uint64_t* peaks, uint64_t capacity);
 
 /* ---- Multi-device groups -------------------------------
  * Replaces nothing in the reference (single-threaded browser code); it exists because

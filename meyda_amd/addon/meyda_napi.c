@@ -35,6 +35,11 @@
  *   tempogramWindow(winLength)           -> Float32Array(winLength): the periodic Hann window (mgx_tempogram_window; host only)
  *   tempoPrior(frameRate, numLags[, {startBpm, stdOctaves, maxBpm}])
  *                                        -> Float64Array(numLags): the log-normal tempo prior (mgx_tempo_prior; host only)
+ *   beatTables(maxPeriod[, tightness])   -> {gauss: Float32Array, penalty: Float64Array}: the tables of the beat tracker
+ *                                           (mgx_beat_tables; host only)
+ *   beatsGather(plan, samples, starts, frameOffsets, {tempoGather's options but mean, gauss, penalty, maxPeriod, trim})
+ *     / beatsGatherAsync(...)            -> {lag, numLags, beatOffsets, beats[, envelope]}: tempoGather's route and the
+ *                                           beats of every signal at its lag, tracked on the device (mgx_beats_host)
  *   tempoGather(plan, samples, starts, frameOffsets, {field, mode, lag, winLength, numLags, norm, gain, window, prior,
  *               mean, envelope}) / tempoGatherAsync(...)
  *                                        -> { lag: Uint32Array(S), numLags[, summary: Float64Array(S x 4 x numLags)][,
@@ -330,6 +335,12 @@ typedef struct {
   double* tsummary;
   uint32_t* tlag;
   napi_ref trefs[4];  /* the window and the prior (kept alive), the lags, the summaries */
+  /* beatsGather: a tempo job with the tracker behind it (mgx_beats_host); peak_offsets and peaks as for onsetsGather */
+  int beats;
+  mgx_beat_params bpar;
+  const float* bgauss;
+  const double* bpenalty;
+  napi_ref brefs[2];  /* the two tables (kept alive) */
   mgx_outputs out;
   mgx_aux_outputs aux;  /* melBands (SLOT_MEL): the job then makes the mgx_extract_*_ex call */
   /* The outputs are written straight into JS ArrayBuffers (napi_create_arraybuffer), held by
@@ -366,6 +377,11 @@ static void job_free_buffers(napi_env env, job* j) {
     if (j->trefs[i]) {
       napi_delete_reference(env, j->trefs[i]);
       j->trefs[i] = NULL;
+    }
+  for (int i = 0; i < 2; ++i)
+    if (j->brefs[i]) {
+      napi_delete_reference(env, j->brefs[i]);
+      j->brefs[i] = NULL;
     }
   for (int i = 0; i < NSLOTS; ++i)
     if (j->refs[i]) {
@@ -917,15 +933,20 @@ static int option_typed(napi_env env, napi_value obj, const char* name, napi_typ
 /* tempoGather(plan, samples, starts, frameOffsets, options): summarizeGather's inputs; options: {field, mode = 0,
  * lag = 1, winLength = 384, numLags = winLength, norm = 1 (0 none, 1 lag0), gain = 1e6, window: a Float32Array of
  * winLength, prior: a Float64Array of numLags, mean = false, envelope = false}. */
+/* beatsGather(plan, samples, starts, frameOffsets, options): the same, without mean, and {maxPeriod = max(numLags - 1, 1),
+ * trim = true, gauss: a Float32Array of (maxPeriod + 1)(maxPeriod + 2) / 2, penalty: a Float64Array of (maxPeriod + 1)^2}. */
 static int job_prepare_tempo(napi_env env, job* j, napi_value samples_v, napi_value starts_v, napi_value offsets_v,
-                             napi_value options_v) {
+                             napi_value options_v, int beats) {
   napi_valuetype ot = napi_undefined;
   napi_typeof(env, options_v, &ot);
   if (ot != napi_object) {
-    napi_throw_type_error(env, NULL, "options must be an object: {field, mode, lag, winLength, numLags, norm, gain, window, prior, mean, envelope}");
+    napi_throw_type_error(env, NULL, beats ? "options must be an object: {field, mode, lag, winLength, numLags, norm, gain, window, prior, "
+                                             "maxPeriod, trim, gauss, penalty, envelope}"
+                                           : "options must be an object: {field, mode, lag, winLength, numLags, norm, gain, window, prior, mean, envelope}");
     return 0;
   }
   j->tempo = 1;
+  j->beats = beats;
   mgx_flux_request* r = &j->flux[0];
   r->struct_size = sizeof *r;
   if (!option_u32(env, options_v, "field", 0, MGX_NUM_FEATURES - 1, MGX_NUM_FEATURES, &r->field)) return 0;
@@ -952,7 +973,22 @@ static int job_prepare_tempo(napi_env env, job* j, napi_value samples_v, napi_va
   j->tprior = (const double*)data;
   napi_value v, ab;
   bool want_mean = false, b = false;
-  if (option_given(env, options_v, "mean", &v)) napi_coerce_to_bool(env, v, &v), napi_get_value_bool(env, v, &want_mean);
+  if (beats) {
+    mgx_beat_params* bp = &j->bpar;
+    mgx_beat_params_init(bp);
+    const uint32_t reach = tp->num_lags > 1 ? tp->num_lags - 1 : 1;  /* the largest lag there can be */
+    if (!option_u32(env, options_v, "maxPeriod", reach, MGX_BEAT_MAX_PERIOD, reach, &bp->max_period)) return 0;
+    bool trim = true;
+    if (option_given(env, options_v, "trim", &v)) napi_coerce_to_bool(env, v, &v), napi_get_value_bool(env, v, &trim);
+    bp->trim = trim ? 1 : 0;
+    const size_t P = bp->max_period;
+    if (!option_typed(env, options_v, "gauss", napi_float32_array, (P + 1) * (P + 2) / 2, &j->brefs[0], &data)) return 0;
+    j->bgauss = (const float*)data;
+    if (!option_typed(env, options_v, "penalty", napi_float64_array, (P + 1) * (P + 1), &j->brefs[1], &data)) return 0;
+    j->bpenalty = (const double*)data;
+  } else if (option_given(env, options_v, "mean", &v)) {
+    napi_coerce_to_bool(env, v, &v), napi_get_value_bool(env, v, &want_mean);
+  }
   if (option_given(env, options_v, "envelope", &v)) napi_coerce_to_bool(env, v, &v), napi_get_value_bool(env, v, &b);
   j->flux_per_frame[0] = b ? 1 : 0;
   size_t count = 0, len = 0, off = 0;
@@ -988,6 +1024,14 @@ static int job_prepare_tempo(napi_env env, job* j, napi_value samples_v, napi_va
   }
   memset(data, 0, (size_t)j->nsignals * sizeof(uint32_t));
   j->tlag = (uint32_t*)data;
+  if (beats) {
+    j->peak_offsets = (uint64_t*)calloc(j->nsignals + 1, sizeof(uint64_t));
+    j->peaks = (uint64_t*)calloc(j->nframes ? j->nframes : 1, sizeof(uint64_t));
+    if (!j->peak_offsets || !j->peaks) {
+      napi_throw_error(env, NULL, "out of host memory");
+      return 0;
+    }
+  }
   if (want_mean) {
     if (napi_create_arraybuffer(env, (size_t)j->nsignals * MGX_NUM_STATS * tp->num_lags * sizeof(double), &data, &ab) != napi_ok ||
         napi_create_reference(env, ab, 1, &j->trefs[3]) != napi_ok) {
@@ -1130,6 +1174,10 @@ static void job_run(job* j) {
   const uint32_t n = j->box->desc.buffer_size;
   if (j->chroma)
     j->rc = mgx_chroma_host(j->box->plan, j->frames, j->nsamples, j->starts, j->nframes, j->frame_offsets, j->nsignals, &j->creq);
+  else if (j->beats)
+    j->rc = mgx_beats_host(j->box->plan, j->frames, j->nsamples, j->starts, j->nframes, j->frame_offsets, j->nsignals, &j->flux[0],
+                           &j->tpar, j->twindow, j->tprior, &j->bpar, j->bgauss, j->bpenalty, j->tlag, j->peak_offsets,
+                           j->nframes ? j->peaks : NULL, j->nframes);
   else if (j->tempo)
     j->rc = mgx_tempo_host(j->box->plan, j->frames, j->nsamples, j->starts, j->nframes, j->frame_offsets, j->nsignals, &j->flux[0],
                            &j->tpar, j->twindow, j->tprior, j->tsummary, j->tlag);
@@ -1207,6 +1255,21 @@ static napi_value job_result(napi_env env, job* j) {
     if (j->trefs[3])
       napi_set_named_property(env, obj, "summary",
                               typed_of(env, j->trefs[3], (size_t)j->nsignals * MGX_NUM_STATS * L * sizeof(double), napi_float64_array, 8));
+    if (j->beats) {  /* the index arrays as onsetsGather returns its own: Float64Arrays */
+      const uint64_t total = j->peak_offsets[j->nsignals];
+      const uint64_t* const src[2] = {j->peak_offsets, j->peaks};
+      const uint64_t count[2] = {j->nsignals + 1, total};
+      static const char* const nm[2] = {"beatOffsets", "beats"};
+      for (int k = 0; k < 2; ++k) {
+        napi_value abv, ta;
+        void* data = NULL;
+        if (napi_create_arraybuffer(env, (size_t)count[k] * sizeof(double), &data, &abv) != napi_ok ||
+            napi_create_typedarray(env, napi_float64_array, (size_t)count[k], abv, 0, &ta) != napi_ok)
+          return NULL;
+        for (uint64_t i = 0; i < count[k]; ++i) ((double*)data)[i] = (double)src[k][i];
+        napi_set_named_property(env, obj, nm[k], ta);
+      }
+    }
     if (j->frefs[1][0])
       napi_set_named_property(env, obj, "envelope", typed_of(env, j->frefs[1][0], (size_t)j->nframes * sizeof(float), napi_float32_array, 4));
     return obj;
@@ -1277,7 +1340,7 @@ static napi_value job_result(napi_env env, job* j) {
 }
 
 /* kind: the input of an extraction job */
-enum { IN_FRAMES = 0, IN_WAV = 1, IN_SIGNAL = 2, IN_GATHER = 3, IN_SUMMARY = 4, IN_ONSETS = 5, IN_CHROMA = 6, IN_TEMPO = 7 };
+enum { IN_FRAMES = 0, IN_WAV = 1, IN_SIGNAL = 2, IN_GATHER = 3, IN_SUMMARY = 4, IN_ONSETS = 5, IN_CHROMA = 6, IN_TEMPO = 7, IN_BEATS = 8 };
 
 static int job_prepare_kind(napi_env env, job* j, int kind, size_t argc, napi_value* argv) {
   if (kind == IN_WAV) return job_prepare_wav(env, j, argv[1], argv[2], argc > 3 ? argv[3] : NULL, argc > 4 ? argv[4] : NULL);
@@ -1286,7 +1349,7 @@ static int job_prepare_kind(napi_env env, job* j, int kind, size_t argc, napi_va
   if (kind == IN_SUMMARY) return job_prepare_summary(env, j, argv[1], argv[2], argv[3], argv[4], argc > 5 ? argv[5] : NULL);
   if (kind == IN_ONSETS) return job_prepare_onsets(env, j, argv[1], argv[2], argv[3], argv[4]);
   if (kind == IN_CHROMA) return job_prepare_chroma(env, j, argv[1], argv[2], argv[3], argv[4]);
-  if (kind == IN_TEMPO) return job_prepare_tempo(env, j, argv[1], argv[2], argv[3], argv[4]);
+  if (kind == IN_TEMPO || kind == IN_BEATS) return job_prepare_tempo(env, j, argv[1], argv[2], argv[3], argv[4], kind == IN_BEATS);
   return job_prepare(env, j, argv[1], argv[2]);
 }
 
@@ -1294,10 +1357,11 @@ static napi_value extract_common(napi_env env, napi_callback_info info, int kind
   size_t argc = 6;
   napi_value argv[6];
   CHECK(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
-  if (argc < (kind == IN_SUMMARY || kind == IN_ONSETS || kind == IN_CHROMA || kind == IN_TEMPO ? 5u : kind == IN_SIGNAL || kind == IN_GATHER ? 4u : 3u)) {
+  if (argc < (kind == IN_SUMMARY || kind == IN_ONSETS || kind == IN_CHROMA || kind == IN_TEMPO || kind == IN_BEATS ? 5u : kind == IN_SIGNAL || kind == IN_GATHER ? 4u : 3u)) {
     napi_throw_type_error(env, NULL, kind == IN_WAV ? "extractWav(plan, wavBytes, features[, channel[, hop]])"
                                    : kind == IN_CHROMA ? "chromaGather(plan, samples, starts, frameOffsets, {weights, numChroma, ...})"
                                    : kind == IN_TEMPO ? "tempoGather(plan, samples, starts, frameOffsets, {field, window, prior, ...})"
+                                   : kind == IN_BEATS ? "beatsGather(plan, samples, starts, frameOffsets, {field, window, prior, gauss, penalty, ...})"
                                    : kind == IN_ONSETS ? "onsetsGather(plan, samples, starts, frameOffsets, {field, ...})"
                                    : kind == IN_SUMMARY ? "summarizeGather(plan, samples, starts, frameOffsets, features[, {deltaWidth, deltaOrder}])"
                                    : kind == IN_GATHER ? "extractGather(plan, samples, starts, features)"
@@ -1424,6 +1488,7 @@ static napi_value summarize_gather_sync(napi_env env, napi_callback_info info) {
 static napi_value onsets_gather_sync(napi_env env, napi_callback_info info) { return extract_common(env, info, IN_ONSETS); }
 static napi_value chroma_gather_sync(napi_env env, napi_callback_info info) { return extract_common(env, info, IN_CHROMA); }
 static napi_value tempo_gather_sync(napi_env env, napi_callback_info info) { return extract_common(env, info, IN_TEMPO); }
+static napi_value beats_gather_sync(napi_env env, napi_callback_info info) { return extract_common(env, info, IN_BEATS); }
 
 static void async_execute(napi_env env, void* data) {
   (void)env;
@@ -1454,10 +1519,11 @@ static napi_value extract_async_common(napi_env env, napi_callback_info info, in
   size_t argc = 6;
   napi_value argv[6];
   CHECK(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
-  if (argc < (kind == IN_SUMMARY || kind == IN_ONSETS || kind == IN_CHROMA || kind == IN_TEMPO ? 5u : kind == IN_SIGNAL || kind == IN_GATHER ? 4u : 3u)) {
+  if (argc < (kind == IN_SUMMARY || kind == IN_ONSETS || kind == IN_CHROMA || kind == IN_TEMPO || kind == IN_BEATS ? 5u : kind == IN_SIGNAL || kind == IN_GATHER ? 4u : 3u)) {
     napi_throw_type_error(env, NULL, kind == IN_WAV ? "extractWavAsync(plan, wavBytes, features[, channel[, hop]])"
                                    : kind == IN_CHROMA ? "chromaGatherAsync(plan, samples, starts, frameOffsets, {weights, numChroma, ...})"
                                    : kind == IN_TEMPO ? "tempoGatherAsync(plan, samples, starts, frameOffsets, {field, window, prior, ...})"
+                                   : kind == IN_BEATS ? "beatsGatherAsync(plan, samples, starts, frameOffsets, {field, window, prior, gauss, penalty, ...})"
                                    : kind == IN_ONSETS ? "onsetsGatherAsync(plan, samples, starts, frameOffsets, {field, ...})"
                                    : kind == IN_SUMMARY ? "summarizeGatherAsync(plan, samples, starts, frameOffsets, features[, {deltaWidth, deltaOrder}])"
                                    : kind == IN_GATHER ? "extractGatherAsync(plan, samples, starts, features)"
@@ -1497,6 +1563,7 @@ static napi_value summarize_gather_async(napi_env env, napi_callback_info info) 
 static napi_value onsets_gather_async(napi_env env, napi_callback_info info) { return extract_async_common(env, info, IN_ONSETS); }
 static napi_value chroma_gather_async(napi_env env, napi_callback_info info) { return extract_async_common(env, info, IN_CHROMA); }
 static napi_value tempo_gather_async(napi_env env, napi_callback_info info) { return extract_async_common(env, info, IN_TEMPO); }
+static napi_value beats_gather_async(napi_env env, napi_callback_info info) { return extract_async_common(env, info, IN_BEATS); }
 
 /* chromaWeights(bufferSize, sampleRate[, {numChroma, a440, centerOctave, octaveWidth, baseC}]): the chroma filter
  * bank (mgx_chroma_weights; host only), a Float32Array of numChroma x bufferSize / 2, row-major. */
@@ -1607,6 +1674,42 @@ static napi_value tempo_prior(napi_env env, napi_callback_info info) {
   if (rc) return throw_mgx(env, rc);
   CHECK(napi_create_typedarray(env, napi_float64_array, (size_t)nl, ab, 0, &ta));
   return ta;
+}
+
+/* beatTables(maxPeriod[, tightness = 100]): the tables of the beat tracker for the periods 1 .. maxPeriod
+ * (mgx_beat_tables; host only): {gauss: a Float32Array of (maxPeriod + 1)(maxPeriod + 2) / 2, penalty: a Float64Array of
+ * (maxPeriod + 1)^2}. */
+static napi_value beat_tables(napi_env env, napi_callback_info info) {
+  size_t argc = 2;
+  napi_value argv[2];
+  CHECK(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  double p = 0, tight = 100.0;
+  napi_valuetype t0 = napi_undefined, t1 = napi_undefined;
+  if (argc >= 1) napi_typeof(env, argv[0], &t0);
+  if (argc >= 2) napi_typeof(env, argv[1], &t1);
+  if (t0 != napi_number || (t1 != napi_number && t1 != napi_undefined)) {
+    napi_throw_type_error(env, NULL, "beatTables(maxPeriod[, tightness])");
+    return NULL;
+  }
+  napi_get_value_double(env, argv[0], &p);
+  if (t1 == napi_number) napi_get_value_double(env, argv[1], &tight);
+  if (!(p >= 1) || p > MGX_BEAT_MAX_PERIOD || p != (double)(uint32_t)p) {
+    napi_throw_range_error(env, NULL, "maxPeriod must be an integer from 1 to 1023");
+    return NULL;
+  }
+  const size_t P = (size_t)p, ng = (P + 1) * (P + 2) / 2, np = (P + 1) * (P + 1);
+  napi_value gab, pab, gta, pta, obj;
+  void *gdata = NULL, *pdata = NULL;
+  CHECK(napi_create_arraybuffer(env, ng * sizeof(float), &gdata, &gab));
+  CHECK(napi_create_arraybuffer(env, np * sizeof(double), &pdata, &pab));
+  const int rc = mgx_beat_tables((uint32_t)P, tight, (float*)gdata, (double*)pdata);
+  if (rc) return throw_mgx(env, rc);
+  CHECK(napi_create_typedarray(env, napi_float32_array, ng, gab, 0, &gta));
+  CHECK(napi_create_typedarray(env, napi_float64_array, np, pab, 0, &pta));
+  CHECK(napi_create_object(env, &obj));
+  CHECK(napi_set_named_property(env, obj, "gauss", gta));
+  CHECK(napi_set_named_property(env, obj, "penalty", pta));
+  return obj;
 }
 
 /* signalsFrameStarts(lengths, bufferSize, hop): mgx_signals_frame_starts (host only) for signals stored one after
@@ -1847,6 +1950,9 @@ static napi_value init(napi_env env, napi_value exports) {
       {"tempoGatherAsync", NULL, tempo_gather_async, NULL, NULL, NULL, napi_enumerable, NULL},
       {"tempogramWindow", NULL, tempogram_window, NULL, NULL, NULL, napi_enumerable, NULL},
       {"tempoPrior", NULL, tempo_prior, NULL, NULL, NULL, napi_enumerable, NULL},
+      {"beatsGather", NULL, beats_gather_sync, NULL, NULL, NULL, napi_enumerable, NULL},
+      {"beatsGatherAsync", NULL, beats_gather_async, NULL, NULL, NULL, napi_enumerable, NULL},
+      {"beatTables", NULL, beat_tables, NULL, NULL, NULL, napi_enumerable, NULL},
       {"signalsFrameStarts", NULL, signals_frame_starts, NULL, NULL, NULL, napi_enumerable, NULL},
       {"wavParse", NULL, wav_parse, NULL, NULL, NULL, napi_enumerable, NULL},
       {"hostTables", NULL, host_tables, NULL, NULL, NULL, napi_enumerable, NULL},

@@ -46,6 +46,7 @@ EXPORTS = ["mgx_plan_desc_init", "mgx_plan_create", "mgx_plan_destroy", "mgx_pla
            "mgx_chroma_params_init", "mgx_chroma_weights", "mgx_chroma_device", "mgx_chroma_host",
            "mgx_tempo_params_init", "mgx_tempogram_window", "mgx_tempo_prior", "mgx_tempogram_device",
            "mgx_tempo_workspace_bytes", "mgx_tempo_device", "mgx_tempo_host",
+           "mgx_beat_params_init", "mgx_beat_tables", "mgx_beats_workspace_bytes", "mgx_beats_device", "mgx_beats_host",
            "mgx_shard_range", "mgx_packed_layout", "mgx_comm_unique_id", "mgx_group_create",
            "mgx_group_create_rank", "mgx_group_create_loopback", "mgx_group_create_loopback_rccl", "mgx_group_destroy",
            "mgx_group_info", "mgx_group_comm_info", "mgx_group_extract_device", "mgx_group_extract_host"]
@@ -199,6 +200,27 @@ class TempoParams(ctypes.Structure):
     """mgx_tempo_params: the window length, the lags, the normalisation of the tempogram and the gain of the pick."""
     _fields_ = [("struct_size", ctypes.c_uint32), ("win_length", ctypes.c_uint32), ("num_lags", ctypes.c_uint32),
                 ("norm", ctypes.c_uint32), ("gain", ctypes.c_double)]
+
+
+BEAT_MAX_PERIOD = 1023  # MGX_BEAT_MAX_PERIOD
+
+
+class BeatParams(ctypes.Structure):
+    """mgx_beat_params: the size of the tables and the trim of the beat tracker."""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("max_period", ctypes.c_uint32), ("trim", ctypes.c_uint32),
+                ("reserved", ctypes.c_uint32)]
+
+
+def beat_params(max_period=None, trim=None):
+    """A BeatParams with the library's defaults (mgx_beat_params_init: 1023, trim) and the arguments over them.
+    Numbers out of range pass through: the library refuses them."""
+    p = BeatParams()
+    lib().mgx_beat_params_init(ctypes.byref(p))
+    if max_period is not None:
+        p.max_period = int(max_period)
+    if trim is not None:
+        p.trim = int(trim)
+    return p
 
 
 def _tempogram_norm(norm):
@@ -390,6 +412,18 @@ def lib():
         L.mgx_tempo_host.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64,
                                      ctypes.c_void_p, ctypes.c_uint64, freq, tpar, ctypes.c_void_p, ctypes.c_void_p,
                                      ctypes.c_void_p, ctypes.c_void_p]
+        bpar = ctypes.POINTER(BeatParams)
+        L.mgx_beat_params_init.argtypes = [bpar]
+        L.mgx_beat_params_init.restype = None
+        L.mgx_beat_tables.argtypes = [ctypes.c_uint32, ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p]
+        L.mgx_beats_workspace_bytes.argtypes = [ctypes.c_uint64, ctypes.c_uint64, u64p]
+        L.mgx_beats_device.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint64,
+                                       ctypes.c_void_p, bpar, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                       ctypes.POINTER(PeakOutputs), ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p]
+        L.mgx_beats_host.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64,
+                                     ctypes.c_void_p, ctypes.c_uint64, freq, tpar, ctypes.c_void_p, ctypes.c_void_p, bpar,
+                                     ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                     ctypes.c_uint64]
         L.mgx_shard_range.argtypes = [ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, u64p, u64p]
         L.mgx_packed_layout.argtypes = [ctypes.POINTER(PlanDesc), ctypes.c_uint32, ctypes.c_uint64, u64p]
         L.mgx_packed_layout.restype = ctypes.c_uint64
@@ -919,6 +953,71 @@ class Plan:
         if frame_rate is None:
             frame_rate = float(self.desc.sample_rate) / hop
         res = self.tempo(samples, starts, frame_offsets, frame_rate, **kw)
+        res["frame_offsets"] = frame_offsets
+        return res
+
+    def beats(self, samples, starts, frame_offsets, frame_rate, feature="melBands", mode="rectified", lag=1, win_length=384,
+              num_lags=None, norm="lag0", gain=1e6, start_bpm=120.0, std_octaves=1.0, max_bpm=320.0, window=None, prior=None,
+              tightness=100.0, trim=True, max_period=None, tables=None, envelope=False, envelope_summary=False, capacity=None):
+        """Host numpy in / numpy out (mgx_beats_host): Plan.tempo's route -- the flux of `feature`, its tempogram
+        pooled per signal, the lag the prior picks -- and the beats of every signal at its lag, tracked on the
+        device over the column that never crosses back (tables: (gauss, penalty) of beat_tables(max_period,
+        tightness), None: made here; max_period None: num_lags - 1, the largest lag there can be). Returns a dict:
+        "lag" and "bpm" as Plan.tempo, "peak_offsets" (S + 1, uint64: the true counts), "beats" (the row indices,
+        ascending; the first `capacity` when that is given and smaller, None with capacity 0), and "envelope",
+        "envelope_summary" when asked. Without `capacity` the call is made twice: for the counts, then for the list."""
+        samples = np.ascontiguousarray(samples, dtype=np.float32)
+        starts = np.ascontiguousarray(starts, dtype=np.uint64)
+        frame_offsets = np.ascontiguousarray(frame_offsets, dtype=np.uint64)
+        assert samples.ndim == 1 and starts.ndim == 1 and frame_offsets.ndim == 1 and frame_offsets.size >= 1
+        S = frame_offsets.size - 1
+        tp = tempo_params(win_length, num_lags, norm, gain)
+        W, L = int(tp.win_length), int(tp.num_lags)
+        window = tempogram_window(W) if window is None else np.ascontiguousarray(window, dtype=np.float32)
+        prior = tempo_prior(frame_rate, L, start_bpm, std_octaves, max_bpm) if prior is None else np.ascontiguousarray(prior, dtype=np.float64)
+        assert window.shape == (W,) and prior.shape == (L,)
+        bp = beat_params(max(L - 1, 1) if max_period is None else max_period, trim)
+        P = int(bp.max_period)
+        gauss, penalty = beat_tables(P, tightness) if tables is None else tables
+        gauss, penalty = np.ascontiguousarray(gauss, dtype=np.float32), np.ascontiguousarray(penalty, dtype=np.float64)
+        if 1 <= P <= BEAT_MAX_PERIOD:
+            assert gauss.shape == ((P + 1) * (P + 2) // 2,) and penalty.shape == ((P + 1) ** 2,)
+        req = {"feature": feature, "mode": mode, "lag": lag, "per_frame": envelope, "summary": envelope_summary}
+        reqs, fres = self._flux_requests(starts.size, S, [req], lambda shape: np.empty(shape, np.float64),
+                                         lambda shape: np.zeros(shape, np.float32))
+        lags = np.zeros(S, np.uint32)
+        offsets = np.zeros(S + 1, np.uint64)
+
+        def call(rows, cap):
+            check(lib().mgx_beats_host(self._h, samples.ctypes.data, samples.size, starts.ctypes.data, starts.size,
+                                       frame_offsets.ctypes.data, S, reqs, ctypes.byref(tp), window.ctypes.data, prior.ctypes.data,
+                                       ctypes.byref(bp), gauss.ctypes.data, penalty.ctypes.data, lags.ctypes.data, offsets.ctypes.data,
+                                       None if rows is None else rows.ctypes.data, cap))
+        rows = None
+        if capacity is None or capacity == 0:
+            call(None, 0)
+            if capacity is None:
+                capacity, rows = int(offsets[S]), np.zeros(0, np.uint64)
+        if capacity > 0:
+            rows = np.zeros(capacity, np.uint64)
+            call(rows, capacity)
+            rows = rows[:min(capacity, int(offsets[S]))]
+        res = {"lag": lags, "bpm": lag_bpm(lags, frame_rate), "peak_offsets": offsets, "beats": rows, "window": window, "prior": prior}
+        if envelope:
+            res["envelope"] = fres[0]["per_frame"]
+        if envelope_summary:
+            res["envelope_summary"] = fres[0]["summary"]
+        return res
+
+    def beats_signals(self, signals, hop, frame_rate=None, **kw):
+        """A list of 1-D host signals in one call (Plan.beats over signals_frame_starts of their lengths; frame_rate
+        None: the plan's sample rate / hop): the dict Plan.beats returns, with "frame_offsets"."""
+        signals = [np.ascontiguousarray(x, dtype=np.float32).ravel() for x in signals]
+        starts, frame_offsets = signals_frame_starts([x.size for x in signals], self.n, hop)
+        samples = np.concatenate(signals) if signals else np.empty(0, np.float32)
+        if frame_rate is None:
+            frame_rate = float(self.desc.sample_rate) / hop
+        res = self.beats(samples, starts, frame_offsets, frame_rate, **kw)
         res["frame_offsets"] = frame_offsets
         return res
 
@@ -1509,4 +1608,101 @@ def tempo_torch(envelope, window, prior=None, frame_offsets=None, num_lags=None,
                  S, tp, window.data_ptr(), None if prior is None else prior.data_ptr(), None if tempogram is None else tempogram.data_ptr(),
                  res["summary"].data_ptr() if summary else None, res["lag"].data_ptr() if prior is not None else None,
                  workspace.data_ptr(), workspace.numel(), stream)
+    return res
+
+
+def beat_tables(max_period, tightness=100.0):
+    """mgx_beat_tables (host only): (gauss, penalty) -- (P + 1)(P + 2) / 2 float32 and (P + 1)^2 float64 -- for the
+    periods 1 .. max_period (include/meyda_gpu.h)."""
+    P = int(max_period)
+    ok = 1 <= P <= BEAT_MAX_PERIOD
+    # (a refused size leaves nothing to size the arrays by: the library checks it before it writes)
+    gauss = np.zeros((P + 1) * (P + 2) // 2 if ok else 1, np.float32)
+    penalty = np.zeros((P + 1) ** 2 if ok else 1, np.float64)
+    check(lib().mgx_beat_tables(P if 0 <= P < 2 ** 32 else 0, float(tightness), gauss.ctypes.data, penalty.ctypes.data))
+    return gauss, penalty
+
+
+def beats_workspace_bytes(num_frames, num_signals=0):
+    """mgx_beats_workspace_bytes (host only)."""
+    b = ctypes.c_uint64()
+    check(lib().mgx_beats_workspace_bytes(num_frames, num_signals, ctypes.byref(b)))
+    return b.value
+
+
+def beats_device(envelope_ptr, num_frames, envelope_f64, offsets_ptr, num_signals, period_ptr, params, gauss_ptr, penalty_ptr,
+                 local_score_ptr, cum_score_ptr, out, workspace_ptr, workspace_bytes, stream=None):
+    """mgx_beats_device on device pointers (async on `stream`); params: a BeatParams, out: a PeakOutputs; a pointer may be None."""
+    check(lib().mgx_beats_device(ctypes.c_void_p(envelope_ptr or 0), num_frames, 1 if envelope_f64 else 0,
+                                 ctypes.c_void_p(offsets_ptr or 0), num_signals, ctypes.c_void_p(period_ptr or 0), ctypes.byref(params),
+                                 ctypes.c_void_p(gauss_ptr or 0), ctypes.c_void_p(penalty_ptr or 0), ctypes.c_void_p(local_score_ptr or 0),
+                                 ctypes.c_void_p(cum_score_ptr or 0), ctypes.byref(out), ctypes.c_void_p(workspace_ptr or 0),
+                                 workspace_bytes, ctypes.c_void_p(stream or 0)))
+
+
+def beats_torch(envelope, period, gauss, penalty, frame_offsets=None, max_period=None, trim=True, capacity=None, starts=None,
+                scores=False, stream=None, workspace=None, mask_fill=0, score_fill=0.0):
+    """mgx_beats_device on CUDA tensors: the beats of `envelope`, a (F,) float32 or float64 tensor, within each signal
+    (frame_offsets as peaks_torch takes them) at the signal's entry of `period`, an (S,) int32 tensor -- the "lag" of
+    tempo_torch as it is -- under the tables of beat_tables(max_period) (tensors, or anything numpy turns into them;
+    max_period None: from the size of penalty). Returns a dict: "mask" ((F,) uint8, `mask_fill` in rows of no
+    signal), "peak_offsets" ((S + 1,) int64: the true counts), "peaks" ((capacity,) int64, the first
+    min(peak_offsets[S], capacity) written; capacity None: F), with `starts` "peak_starts", and with scores=True
+    "local_score" and "cum_score" ((F,) float64, `score_fill` in rows of no signal). workspace: a uint8 CUDA tensor
+    of beats_workspace_bytes (for a capture), None: allocated here."""
+    import torch
+    assert envelope.is_cuda and envelope.is_contiguous() and envelope.dim() == 1
+    assert envelope.dtype in (torch.float32, torch.float64)
+    dev = envelope.device
+    F = envelope.shape[0]
+    S = 0
+    if frame_offsets is not None:
+        if not torch.is_tensor(frame_offsets):
+            frame_offsets = torch.from_numpy(np.ascontiguousarray(frame_offsets, dtype=np.uint64).view(np.int64)).to(dev)
+        assert frame_offsets.is_cuda and frame_offsets.dtype == torch.int64 and frame_offsets.is_contiguous()
+        assert frame_offsets.dim() == 1 and frame_offsets.shape[0] >= 1
+        S = frame_offsets.shape[0] - 1
+    nsig = S if frame_offsets is not None else 1
+    if not torch.is_tensor(period):
+        period = torch.from_numpy(np.ascontiguousarray(period, dtype=np.uint32).view(np.int32)).to(dev)
+    assert period.is_cuda and period.is_contiguous() and period.dtype == torch.int32 and period.shape == (nsig,)
+    if not torch.is_tensor(gauss):
+        gauss = torch.from_numpy(np.ascontiguousarray(gauss, dtype=np.float32)).to(dev)
+    if not torch.is_tensor(penalty):
+        penalty = torch.from_numpy(np.ascontiguousarray(penalty, dtype=np.float64)).to(dev)
+    assert gauss.is_cuda and gauss.is_contiguous() and gauss.dtype == torch.float32 and gauss.dim() == 1
+    assert penalty.is_cuda and penalty.is_contiguous() and penalty.dtype == torch.float64 and penalty.dim() == 1
+    if max_period is None:
+        max_period = int(round(penalty.shape[0] ** 0.5)) - 1
+    bp = beat_params(max_period, trim)
+    P = int(bp.max_period)
+    if 1 <= P <= BEAT_MAX_PERIOD:
+        assert gauss.shape[0] == (P + 1) * (P + 2) // 2 and penalty.shape[0] == (P + 1) ** 2
+    if capacity is None:
+        capacity = max(F, 1)
+    res = {"mask": torch.full((F,), mask_fill, dtype=torch.uint8, device=dev),
+           "peak_offsets": torch.zeros(nsig + 1, dtype=torch.int64, device=dev),
+           "peaks": torch.zeros(capacity, dtype=torch.int64, device=dev)}
+    o = PeakOutputs()
+    o.struct_size = ctypes.sizeof(PeakOutputs)
+    o.mask, o.peak_offsets, o.peaks, o.capacity = res["mask"].data_ptr(), res["peak_offsets"].data_ptr(), res["peaks"].data_ptr(), capacity
+    if starts is not None:
+        if not torch.is_tensor(starts):
+            starts = torch.from_numpy(np.ascontiguousarray(starts, dtype=np.uint64).view(np.int64)).to(dev)
+        assert starts.is_cuda and starts.dtype == torch.int64 and starts.is_contiguous() and starts.shape == (F,)
+        res["peak_starts"] = torch.zeros(capacity, dtype=torch.int64, device=dev)
+        o.starts, o.peak_starts = starts.data_ptr(), res["peak_starts"].data_ptr()
+    if scores:
+        res["local_score"] = torch.full((F,), score_fill, dtype=torch.float64, device=dev)
+        res["cum_score"] = torch.full((F,), score_fill, dtype=torch.float64, device=dev)
+    nbytes = beats_workspace_bytes(F, S)
+    if workspace is None:
+        workspace = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+    assert workspace.is_cuda and workspace.dtype == torch.uint8 and workspace.numel() >= nbytes
+    if stream is None:
+        stream = torch.cuda.current_stream(dev).cuda_stream
+    beats_device(envelope.data_ptr(), F, envelope.dtype == torch.float64, None if frame_offsets is None else frame_offsets.data_ptr(),
+                 S, period.data_ptr(), bp, gauss.data_ptr(), penalty.data_ptr(),
+                 res["local_score"].data_ptr() if scores else None, res["cum_score"].data_ptr() if scores else None, o,
+                 workspace.data_ptr(), nbytes, stream)
     return res

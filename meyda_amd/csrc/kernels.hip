@@ -4197,6 +4197,539 @@ hipError_t launch_tempo_pick(const double* summary, const double* prior, double 
   return hipGetLastError();
 }
 
+// ---- Beats (mgx_beats_device, mgx_beats_host): a clip's beats by dynamic programming (include/meyda_gpu.h) ----
+//   beat_scale_kernel<T>: a wave per signal; the 64 partials of step 1 are its lanes (lane l adds rows l, l + 64, ..
+//     ascending, the halvings are shuffles), twice: for the mean and for the squares. sd[s] is 0 for a signal that
+//     has no beats by n, p or sd: the flag the later kernels read.
+//   beat_score_kernel<T>: a workgroup owns a tile of 256 rows and keeps xn of the tile and of P rows on each side
+//     in LDS as float32, each row normalised by its own signal's sd; a thread owns a row and adds its 2 p + 1 terms
+//     in the definition's order, leaving out only those outside its signal (they add +0 to a sum that is never -0).
+//     It also writes the picker's `member` word, clears the back link and, for a flagged signal, both scores.
+//   beat_track_kernel: a workgroup of 512 per signal. The penalties of p and a ring of the last 2,048 values of C
+//     are in LDS. A step takes the next lo(p) rows -- no row among them reads another --, G = 64, 32, .., 1 lanes a
+//     row (the most that 512 / lo(p) allows): a lane scans its candidates d = 2 p - j, 2 p - j - G, .. downwards
+//     with `>`, the G lanes merge (c, d) pairs by greater c, then greater d, which is the definition's scan in any
+//     tree. All reads of the ring precede the step's writes (a barrier between). One long signal is bound by this
+//     chain: n / lo(p) steps of two barriers each.
+//   beat_tail_kernel: a wave per signal. It notes the local maxima of C in bit 30 of their back links, and selects
+//     their median by radix on order-preserving 64-bit keys, four bits a pass: 16 counting passes per order statistic
+//     into lane-private counters in LDS, no sort, no memory beyond them, exact; then the last maximum above half of it.
+//   beat_chain_kernel: a lane per signal walks the chain three times (the sum of squares; the valid ends; the
+//     marks) and marks a beat in bit 31 of its row's back link -- a row has one owner, a bitmap word may have many.
+//   beat_pack_kernel: the marks as the picker's `acc` words, from which its count, scan, write and offsets kernels
+//     make mask, peak_offsets, peaks and peak_starts unchanged.
+// No atomics, one writer per output, nothing depends on the grid.
+namespace {
+
+constexpr uint32_t kBeatRing = 2048;  // a power of two >= 2 MGX_BEAT_MAX_PERIOD
+constexpr uint32_t kBeatMark = 0x80000000u;  // of a back link: the row is a beat
+constexpr uint32_t kBeatMax = 0x40000000u;   // ... the row is a local maximum of C (beat_tail_kernel's note to itself)
+constexpr uint32_t kBeatLink = ~(kBeatMark | kBeatMax);
+constexpr uint64_t kBeatNone = ~0ull;
+constexpr int kBeatAhead = 8;  // rows a lane loads before it uses the first: the per-signal loops wait on loads, not on arithmetic
+static_assert(kBeatRing >= 2 * MGX_BEAT_MAX_PERIOD && (kBeatRing & (kBeatRing - 1)) == 0, "the ring holds 2 p rows");
+
+struct BeatArgs {
+  const void* env;
+  const uint64_t* table;  // null: one signal, rows [0, num_frames)
+  const uint32_t* period;
+  const float* gauss;
+  const double* penalty;
+  uint64_t num_signals, num_frames, nwords, ntiles;
+  uint32_t P, trim;
+  double* sd;      // num_signals: sd of step 1, or 0: no beats
+  uint64_t* tail;  // num_signals: the row of step 6, or kBeatNone
+  double* ls;      // num_frames
+  double* C;       // num_frames
+  uint32_t* back;  // num_frames: t - B(t), 0 for none; kBeatMark: a beat
+  uint64_t* acc;
+  uint64_t* member;
+};
+
+__device__ __forceinline__ void beat_signal(const BeatArgs& g, uint64_t s, uint64_t& a, uint64_t& b) {
+  const uint64_t T_ = g.num_frames;
+  if (!g.table) {
+    a = 0;
+    b = T_;
+    return;
+  }
+  a = g.table[s];
+  b = g.table[s + 1];
+  a = a < T_ ? a : T_;
+  b = b < T_ ? b : T_;
+}
+
+// the signal of row t: the last s with table[s] <= t; false when the row belongs to none
+__device__ __forceinline__ bool beat_find(const BeatArgs& g, uint64_t t, uint64_t& s, uint64_t& a, uint64_t& b) {
+  s = 0;
+  if (g.table) {
+    uint64_t lo = 0, hi = g.num_signals + 1;  // the first entry above t
+    while (lo < hi) {
+      const uint64_t mid = lo + (hi - lo) / 2;
+      if (g.table[mid] <= t) lo = mid + 1;
+      else hi = mid;
+    }
+    if (lo == 0 || lo > g.num_signals) return false;
+    s = lo - 1;
+  }
+  beat_signal(g, s, a, b);
+  return t >= a && t < b;
+}
+
+__device__ __forceinline__ uint32_t beat_lo(uint32_t p) {
+  uint32_t h = p >> 1;
+  if (p & 1) h += h & 1;
+  return h > 1 ? h : 1;
+}
+
+// P[l] += P[l + h] for l < h, h = 32 .. 1; lane 0 holds P[0], broadcast
+__device__ __forceinline__ double beat_fold(double v) {
+#pragma unroll
+  for (int h = 32; h >= 1; h >>= 1) v += __shfl_down(v, h);
+  return __shfl(v, 0);
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void beat_scale_kernel(BeatArgs g) {
+  const T* __restrict__ const env = static_cast<const T*>(g.env);
+  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  for (uint64_t s = (uint64_t)blockIdx.x * 4 + wave; s < g.num_signals; s += (uint64_t)gridDim.x * 4) {
+    uint64_t a, b;
+    beat_signal(g, s, a, b);
+    const uint32_t p = g.period[s];
+    double sd = 0.0;
+    if (b > a && b - a >= 2 && p >= 1 && p <= g.P) {  // (wave-uniform)
+      const uint64_t n = b - a;
+      // (the additions of a partial in ascending order; the loads of kBeatAhead of them issued together)
+      double part = 0.0;
+      for (uint64_t i0 = lane; i0 < n; i0 += 64 * kBeatAhead) {
+        double x[kBeatAhead];
+#pragma unroll
+        for (int u = 0; u < kBeatAhead; ++u) x[u] = i0 + 64 * u < n ? (double)env[a + i0 + 64 * u] : 0.0;
+#pragma unroll
+        for (int u = 0; u < kBeatAhead; ++u)
+          if (i0 + 64 * u < n) part += x[u];
+      }
+      const double mean = beat_fold(part) / (double)n;
+      part = 0.0;
+      for (uint64_t i0 = lane; i0 < n; i0 += 64 * kBeatAhead) {
+        double x[kBeatAhead];
+#pragma unroll
+        for (int u = 0; u < kBeatAhead; ++u) x[u] = i0 + 64 * u < n ? (double)env[a + i0 + 64 * u] : 0.0;
+#pragma unroll
+        for (int u = 0; u < kBeatAhead; ++u)
+          if (i0 + 64 * u < n) {
+            const double e = x[u] - mean;
+            const double ee = e * e;
+            part += ee;
+          }
+      }
+      const double var = beat_fold(part) / (double)(n - 1);
+      const double r = __builtin_sqrt(var);
+      if (r > 0.0 && r < __builtin_huge_val()) sd = r;
+    }
+    if (lane == 0) g.sd[s] = sd;
+  }
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void beat_score_kernel(BeatArgs g) {
+  extern __shared__ float beat_xn[];  // row r0 - P + i of the tile at r0, normalised within its own signal
+  const T* __restrict__ const env = static_cast<const T*>(g.env);
+  const uint64_t T_ = g.num_frames;
+  const uint32_t halo = g.P, width = 256 + 2 * halo;
+  for (uint64_t tile = blockIdx.x; tile < g.ntiles; tile += gridDim.x) {
+    const uint64_t r0 = tile * 256;
+    for (uint32_t i = threadIdx.x; i < width; i += 256) {
+      const uint64_t u = r0 + i;
+      float v = 0.0f;
+      if (u >= halo && u - halo < T_) {
+        uint64_t s, a, b;
+        if (beat_find(g, u - halo, s, a, b)) {
+          const double sd = g.sd[s];
+          if (sd > 0.0) v = (float)((double)env[u - halo] / sd);
+        }
+      }
+      beat_xn[i] = v;
+    }
+    __syncthreads();
+    const uint64_t t = r0 + threadIdx.x;
+    uint64_t s = 0, a = 0, b = 0;
+    const bool in = t < T_ && beat_find(g, t, s, a, b);
+    if (in) {
+      const double sd = g.sd[s];
+      double ls = 0.0;
+      if (sd > 0.0) {
+        const uint32_t p = g.period[s];  // 1 .. P
+        const float* __restrict__ const gw = g.gauss + (size_t)p * (p + 1) / 2;
+        const int32_t before = (int32_t)(t - a < p ? t - a : p), after = (int32_t)(b - 1 - t < p ? b - 1 - t : p);
+        const float* const x = beat_xn + threadIdx.x + halo;
+        for (int32_t k = -before; k <= after; ++k) {
+          const double term = (double)gw[k < 0 ? -k : k] * (double)x[k];
+          ls += term;
+        }
+      } else {
+        g.C[t] = 0.0;
+      }
+      g.ls[t] = ls;
+      g.back[t] = 0;
+    }
+    const uint64_t mw = __ballot(in);
+    const uint64_t w = (r0 >> 6) + (threadIdx.x >> 6);
+    if ((threadIdx.x & 63) == 0 && w < g.nwords) {
+      g.member[w] = mw;
+      g.acc[w] = 0;
+    }
+    __syncthreads();
+  }
+}
+
+// blockIdx.x: the signal; 512 threads
+__global__ __launch_bounds__(512) void beat_track_kernel(BeatArgs g) {
+  __shared__ double ring[kBeatRing];
+  __shared__ double pen[2 * MGX_BEAT_MAX_PERIOD + 2];
+  __shared__ double red_d[8];
+  __shared__ uint64_t red_u[8];
+  const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+  for (uint64_t s = blockIdx.x; s < g.num_signals; s += gridDim.x) {
+    if (!(g.sd[s] > 0.0)) continue;  // (uniform over the workgroup)
+    uint64_t a, b;
+    beat_signal(g, s, a, b);
+    const uint64_t n = b - a;
+    const uint32_t p = g.period[s], lo = beat_lo(p);
+    const double* __restrict__ const ls = g.ls + a;
+    for (uint32_t d = tid; d <= 2 * p; d += 512) pen[d] = g.penalty[(size_t)p * p + d];
+    // step 4: the maximum without its NaNs, then the first row not below a hundredth of it
+    double m = -__builtin_huge_val();
+    for (uint64_t i = tid; i < n; i += 512) {
+      const double v = ls[i];
+      if (v > m) m = v;
+    }
+#pragma unroll
+    for (int h = 32; h >= 1; h >>= 1) {
+      const double o = __shfl_xor(m, h);
+      if (o > m) m = o;
+    }
+    if (lane == 0) red_d[wave] = m;
+    __syncthreads();
+    m = red_d[0];
+    for (int i = 1; i < 8; ++i)
+      if (red_d[i] > m) m = red_d[i];
+    const double thr = 0.01 * m;
+    uint64_t t0 = n;
+    for (uint64_t i = tid; i < n; i += 512)
+      if (!(ls[i] < thr)) {
+        t0 = i;
+        break;
+      }
+#pragma unroll
+    for (int h = 32; h >= 1; h >>= 1) {
+      const uint64_t o = __shfl_xor((unsigned long long)t0, h);
+      if (o < t0) t0 = o;
+    }
+    if (lane == 0) red_u[wave] = t0;
+    __syncthreads();  // (also: pen is staged)
+    t0 = red_u[0];
+    for (int i = 1; i < 8; ++i)
+      if (red_u[i] < t0) t0 = red_u[i];
+    // step 5
+    uint32_t G = 64;
+    while (G > 1 && G * lo > 512) G >>= 1;
+    const uint32_t r = tid / G, j = tid % G;
+    double ahead = r < lo && r < n && j == 0 ? ls[r] : 0.0;  // ls of the row's lane, loaded a step before it is added
+    for (uint64_t t = 0; t < n; t += lo) {
+      const uint64_t row = t + r;  // (relative to a)
+      const bool live = r < lo && row < n;
+      double best = -__builtin_huge_val();
+      uint32_t arg = 0;
+      const double mine = ahead;
+      if (r < lo && j == 0 && row + lo < n) ahead = ls[row + lo];
+      if (live) {
+        for (int32_t d = (int32_t)(2 * p - j); d >= (int32_t)lo; d -= (int32_t)G) {
+          const double prev = row >= (uint64_t)d ? ring[(row - (uint64_t)d) & (kBeatRing - 1)] : 0.0;
+          const double c = pen[d] + prev;
+          if (c > best) {  // (a NaN compares false)
+            best = c;
+            arg = (uint32_t)d;
+          }
+        }
+      }
+      for (uint32_t h = G >> 1; h >= 1; h >>= 1) {
+        const double ob = __shfl_xor(best, (int)h);
+        const uint32_t oa = __shfl_xor(arg, (int)h);
+        if (ob > best || (ob == best && oa > arg)) {
+          best = ob;
+          arg = oa;
+        }
+      }
+      __syncthreads();  // every read of the ring is done
+      if (live && j == 0) {
+        const double c = mine + best;
+        ring[row & (kBeatRing - 1)] = c;
+        g.C[a + row] = c;
+        g.back[a + row] = row >= t0 && arg != 0 && row >= arg ? arg : 0u;
+      }
+      __syncthreads();
+    }
+  }
+}
+
+// order-preserving: a < b as doubles (neither a NaN) iff key(a) < key(b), -0 below +0
+__device__ __forceinline__ uint64_t beat_key(double c) {
+  const uint64_t u = (uint64_t)__double_as_longlong(c);
+  return (u >> 63) ? ~u : (u | (1ull << 63));
+}
+__device__ __forceinline__ double beat_unkey(uint64_t k) {
+  return __longlong_as_double((long long)((k >> 63) ? (k & ~(1ull << 63)) : ~k));
+}
+__device__ __forceinline__ uint64_t beat_wave_sum(uint64_t v) {
+#pragma unroll
+  for (int h = 32; h >= 1; h >>= 1) v += __shfl_xor((unsigned long long)v, h);
+  return v;
+}
+// M(i) of step 6, i relative to the signal's first row, n >= 2
+__device__ __forceinline__ bool beat_is_max(const double* __restrict__ C, uint64_t i, uint64_t n) {
+  if (i == 0 || i >= n) return false;
+  const double c = C[i];
+  return c > C[i - 1] && (i == n - 1 || c >= C[i + 1]);
+}
+// The k-th smallest (from 0) of the values C[i] whose back link carries kBeatMax, by the whole wave: a radix selection
+// on the order-preserving keys, four bits a pass from the top, sixteen counting passes. hist: the wave's 16 x 64
+// counters in LDS, a lane its own column.
+__device__ __forceinline__ double beat_select(const double* __restrict__ C, const uint32_t* __restrict__ back, uint64_t n, uint64_t k,
+                                              uint32_t lane, uint32_t* hist) {
+  uint64_t prefix = 0;
+  for (int shift = 60; shift >= 0; shift -= 4) {
+    const uint64_t decided = shift == 60 ? 0ull : ~0ull << (shift + 4);
+    for (int b = 0; b < 16; ++b) hist[b * 64 + lane] = 0;
+    for (uint64_t i0 = lane; i0 < n; i0 += 64 * kBeatAhead) {
+      uint32_t f[kBeatAhead];
+      double c[kBeatAhead];
+#pragma unroll
+      for (int u = 0; u < kBeatAhead; ++u) {
+        const uint64_t i = i0 + 64 * u;
+        f[u] = i < n ? back[i] : 0u;
+        c[u] = i < n ? C[i] : 0.0;
+      }
+#pragma unroll
+      for (int u = 0; u < kBeatAhead; ++u)
+        if (f[u] & kBeatMax) {
+          const uint64_t key = beat_key(c[u]);
+          if ((key & decided) == prefix) hist[((key >> shift) & 15) * 64 + lane] += 1;
+        }
+    }
+    for (uint64_t b = 0; b < 16; ++b) {
+      const uint64_t cnt = beat_wave_sum(hist[b * 64 + lane]);
+      if (k < cnt || b == 15) {  // (the digit's bin holds the k-th: k < cnt there for any k below the count of maxima)
+        prefix |= b << shift;
+        break;
+      }
+      k -= cnt;
+    }
+  }
+  return beat_unkey(prefix);
+}
+
+__global__ __launch_bounds__(256) void beat_tail_kernel(BeatArgs g) {
+  __shared__ uint32_t hists[4][16 * 64];
+  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  for (uint64_t s = (uint64_t)blockIdx.x * 4 + wave; s < g.num_signals; s += (uint64_t)gridDim.x * 4) {
+    uint64_t tail = kBeatNone;
+    if (g.sd[s] > 0.0) {  // (wave-uniform)
+      uint64_t a, b;
+      beat_signal(g, s, a, b);
+      const uint64_t n = b - a;
+      const double* __restrict__ const C = g.C + a;
+      uint32_t* const back = g.back + a;
+      uint64_t m = 0;
+      for (uint64_t i = lane; i < n; i += 64)
+        if (beat_is_max(C, i, n)) {
+          back[i] |= kBeatMax;  // (the row's own word: beat_track_kernel wrote it without the flag)
+          ++m;
+        }
+      m = beat_wave_sum(m);
+      if (m > 0) {
+        double med;
+        if (m & 1) {
+          med = beat_select(C, back, n, (m - 1) / 2, lane, hists[wave]);
+        } else {
+          const double v0 = beat_select(C, back, n, m / 2 - 1, lane, hists[wave]), v1 = beat_select(C, back, n, m / 2, lane, hists[wave]);
+          const double sum = v0 + v1;
+          med = sum * 0.5;
+        }
+        uint64_t last = 0;  // (row 0 is no maximum: 0 is "none")
+        for (uint64_t i0 = lane; i0 < n; i0 += 64 * kBeatAhead) {
+          uint32_t f[kBeatAhead];
+          double c[kBeatAhead];
+#pragma unroll
+          for (int u = 0; u < kBeatAhead; ++u) {
+            const uint64_t i = i0 + 64 * u;
+            f[u] = i < n ? back[i] : 0u;
+            c[u] = i < n ? C[i] : 0.0;
+          }
+#pragma unroll
+          for (int u = 0; u < kBeatAhead; ++u)
+            if ((f[u] & kBeatMax) && 2.0 * c[u] > med) last = i0 + 64 * u;
+        }
+#pragma unroll
+        for (int h = 32; h >= 1; h >>= 1) {
+          const uint64_t o = __shfl_xor((unsigned long long)last, h);
+          if (o > last) last = o;
+        }
+        if (last > 0) tail = a + last;
+      }
+    }
+    if (lane == 0) g.tail[s] = tail;
+  }
+}
+
+__global__ __launch_bounds__(64) void beat_chain_kernel(BeatArgs g) {
+  for (uint64_t s = (uint64_t)blockIdx.x * 64 + threadIdx.x; s < g.num_signals; s += (uint64_t)gridDim.x * 64) {
+    const uint64_t tail = g.tail[s];
+    if (tail == kBeatNone) continue;
+    // the chain from `tail` down, with s_i of step 8: f(row, s_i); a link is at least 1 and at most the row
+    auto walk = [&](auto f) {
+      uint64_t cur = tail;
+      double ls_later = 0.0, ls_cur = g.ls[cur];
+      for (;;) {
+        const uint32_t d = g.back[cur] & kBeatLink;
+        const double ls_earlier = d ? g.ls[cur - d] : 0.0;
+        const double half = 0.5 * ls_earlier;
+        const double left = half + ls_cur;
+        const double right = 0.5 * ls_later;
+        f(cur, left + right);
+        if (!d) break;
+        ls_later = ls_cur;
+        ls_cur = ls_earlier;
+        cur -= d;
+      }
+    };
+    double R = 0.0, thr = 0.0;
+    uint64_t K = 0;
+    walk([&](uint64_t, double v) {
+      const double q = v * v;
+      R += q;
+      ++K;
+    });
+    if (g.trim) {
+      const double mean = R / (double)K;
+      thr = 0.5 * __builtin_sqrt(mean);
+    }
+    uint64_t high = kBeatNone, low = kBeatNone;
+    walk([&](uint64_t row, double v) {
+      if (v > thr) {
+        if (high == kBeatNone) high = row;
+        low = row;
+      }
+    });
+    if (high == kBeatNone) continue;
+    walk([&](uint64_t row, double) {
+      if (row >= low && row <= high) g.back[row] |= kBeatMark;
+    });
+  }
+}
+
+__global__ __launch_bounds__(256) void beat_pack_kernel(BeatArgs g) {
+  for (uint64_t tile = blockIdx.x; tile < g.ntiles; tile += gridDim.x) {
+    const uint64_t t = tile * 256 + threadIdx.x, w = t >> 6;
+    // (a row of no signal has no back link written: its member bit is clear)
+    const bool in = t < g.num_frames && ((g.member[w] >> (t & 63)) & 1);
+    const uint64_t bits = __ballot(in && (g.back[t] & kBeatMark));
+    if ((threadIdx.x & 63) == 0 && w < g.nwords) g.acc[w] = bits;
+  }
+}
+
+}  // namespace
+
+uint64_t beats_workspace_bytes(uint64_t num_frames, uint64_t num_signals, BeatLayout* l) {
+  BeatLayout x{};
+  if (num_frames > 0) {
+    x.total = peaks_workspace_bytes(num_frames);
+    auto take = [&x](uint64_t bytes) {
+      const uint64_t at = x.total;
+      x.total += (bytes + 255) / 256 * 256;
+      return at;
+    };
+    const uint64_t S = num_signals ? num_signals : 1;
+    x.sd = take(S * 8);
+    x.tail = take(S * 8);
+    x.ls = take(num_frames * 8);
+    x.C = take(num_frames * 8);
+    x.back = take(num_frames * 4);
+  }
+  if (l) *l = x;
+  return x.total;
+}
+
+hipError_t launch_beats(const void* env, uint64_t num_frames, bool f64, const uint64_t* table, uint64_t num_signals,
+                        const uint32_t* period, uint32_t max_period, uint32_t trim, const float* gauss, const double* penalty,
+                        double* local_score, double* cum_score, const mgx_peak_outputs& o, void* workspace, hipStream_t stream) {
+  if (num_frames == 0) return hipSuccess;
+  if (max_period < 1 || max_period > MGX_BEAT_MAX_PERIOD || !env || !period || !gauss || !penalty || !workspace) return hipErrorInvalidValue;
+  PeakLayout pl;
+  BeatLayout bl;
+  peaks_workspace_bytes(num_frames, &pl);
+  beats_workspace_bytes(num_frames, table ? num_signals : 1, &bl);
+  unsigned char* const ws = static_cast<unsigned char*>(workspace);
+  BeatArgs g{};
+  g.env = env;
+  g.table = table;
+  g.period = period;
+  g.gauss = gauss;
+  g.penalty = penalty;
+  g.num_signals = table ? num_signals : 1;
+  g.num_frames = num_frames;
+  g.nwords = (num_frames + 63) / 64;
+  g.ntiles = (num_frames + 255) / 256;
+  g.P = max_period;
+  g.trim = trim;
+  g.sd = reinterpret_cast<double*>(ws + bl.sd);
+  g.tail = reinterpret_cast<uint64_t*>(ws + bl.tail);
+  g.ls = local_score ? local_score : reinterpret_cast<double*>(ws + bl.ls);
+  g.C = cum_score ? cum_score : reinterpret_cast<double*>(ws + bl.C);
+  g.back = reinterpret_cast<uint32_t*>(ws + bl.back);
+  g.acc = reinterpret_cast<uint64_t*>(ws + pl.acc);
+  g.member = reinterpret_cast<uint64_t*>(ws + pl.member);
+  // the picker's list kernels over the beats' bitmap
+  PeakArgs q{};
+  q.table = table;
+  q.num_signals = g.num_signals;
+  q.num_frames = num_frames;
+  q.nwords = g.nwords;
+  q.nblocks = (g.nwords + kPeakScanWords - 1) / kPeakScanWords;
+  q.acc = g.acc;
+  q.member = g.member;
+  q.wrank = reinterpret_cast<uint64_t*>(ws + pl.wrank);
+  q.bsum = reinterpret_cast<uint64_t*>(ws + pl.bsum);
+  q.mask = o.mask;
+  q.peak_offsets = o.peak_offsets;
+  q.peaks = o.peaks;
+  q.capacity = o.capacity;
+  q.starts = o.starts;
+  q.peak_starts = o.peak_starts;
+  auto blocks = [](uint64_t n) { return dim3((unsigned)(n < 16384 ? (n ? n : 1) : 16384)); };
+  const size_t tile_bytes = (256 + 2 * (size_t)max_period) * sizeof(float);
+  if (g.num_signals > 0) {
+    if (f64) hipLaunchKernelGGL((beat_scale_kernel<double>), blocks((g.num_signals + 3) / 4), dim3(256), 0, stream, g);
+    else hipLaunchKernelGGL((beat_scale_kernel<float>), blocks((g.num_signals + 3) / 4), dim3(256), 0, stream, g);
+  }
+  if (f64) hipLaunchKernelGGL((beat_score_kernel<double>), blocks(g.ntiles), dim3(256), tile_bytes, stream, g);
+  else hipLaunchKernelGGL((beat_score_kernel<float>), blocks(g.ntiles), dim3(256), tile_bytes, stream, g);
+  if (g.num_signals > 0) {
+    hipLaunchKernelGGL(beat_track_kernel, blocks(g.num_signals), dim3(512), 0, stream, g);
+    hipLaunchKernelGGL(beat_tail_kernel, blocks((g.num_signals + 3) / 4), dim3(256), 0, stream, g);
+    hipLaunchKernelGGL(beat_chain_kernel, blocks((g.num_signals + 63) / 64), dim3(64), 0, stream, g);
+    hipLaunchKernelGGL(beat_pack_kernel, blocks(g.ntiles), dim3(256), 0, stream, g);
+  }
+  if (q.peaks || q.peak_offsets) {
+    hipLaunchKernelGGL(peak_count_kernel, blocks(q.nblocks), dim3(256), 0, stream, q);
+    hipLaunchKernelGGL(peak_scan_kernel, dim3(1), dim3(256), 0, stream, q);
+  }
+  if (q.peaks || q.peak_offsets || q.mask) hipLaunchKernelGGL(peak_write_kernel, blocks(q.nblocks), dim3(256), 0, stream, q);
+  if (q.peak_offsets) hipLaunchKernelGGL(peak_offsets_kernel, blocks((q.num_signals + 256) / 256), dim3(256), 0, stream, q);
+  return hipGetLastError();
+}
+
 }  // namespace mgx
 
 #if MGX_WAVE_TIMES

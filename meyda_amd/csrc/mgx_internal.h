@@ -268,6 +268,20 @@ hipError_t launch_tempogram(const void* env, uint64_t num_frames, bool f64, cons
 hipError_t launch_tempo_one_signal(uint64_t* table, uint64_t num_frames, hipStream_t stream);
 hipError_t launch_tempo_pick(const double* summary, const double* prior, double gain, uint32_t L, uint64_t num_signals, uint32_t* lag,
                              hipStream_t stream);
+// Beats (mgx_beats_device, mgx_beats_host; kernels.hip beat_*_kernel): the beats of the one-column envelope env within
+// each signal at the signal's entry of period (device, one per signal; one entry with a null table), the table as
+// launch_peaks reads it; gauss and penalty are mgx_beat_tables of max_period on the device. local_score, cum_score:
+// num_frames doubles each or null (then kept in the workspace). The workspace holds the picker's (its bitmaps and
+// scan words are reused by its own list kernels), sd and the tail row per signal, and per row the two scores and a
+// back link: beats_workspace_bytes, a multiple of 256 (0 for no rows). Up to ten launches, asynchronous; the
+// arguments are checked by the caller.
+struct BeatLayout {
+  uint64_t sd, tail, ls, C, back, total;
+};
+uint64_t beats_workspace_bytes(uint64_t num_frames, uint64_t num_signals, BeatLayout* l = nullptr);
+hipError_t launch_beats(const void* env, uint64_t num_frames, bool f64, const uint64_t* table, uint64_t num_signals,
+                        const uint32_t* period, uint32_t max_period, uint32_t trim, const float* gauss, const double* penalty,
+                        double* local_score, double* cum_score, const mgx_peak_outputs& o, void* workspace, hipStream_t stream);
 size_t extract_lds_bytes(int n, int ncoef, int nfilt, bool chain);
 size_t lds_image_bytes(int n, int ncoef, int nfilt);  // DevTables::lds_image, a multiple of 16
 hipError_t launch_lds_image(int n, int precision, int mode, const KernelArgs& a, void* image, hipStream_t stream);

@@ -1922,6 +1922,29 @@ int check_peak_params(const mgx_peak_params* pp) {
   return MGX_OK;
 }
 
+// mgx_beats_host: the tracker behind mgx_tempo_host's route, over the same column, the lags as its periods
+struct BeatHost {
+  const mgx_beat_params* params;
+  const float* gauss;      // host, mgx_beat_tables of params->max_period
+  const double* penalty;   // host
+  uint64_t* peak_offsets;  // host, num_signals + 1
+  uint64_t* peaks;         // host, capacity entries, or null
+  uint64_t capacity;
+};
+
+int check_beat_params(const mgx_beat_params* bp) {
+  if (!bp) return fail(MGX_E_INVALID_ARGUMENT, "params is NULL");
+  if (bp->struct_size != sizeof(mgx_beat_params))
+    return fail(MGX_E_INVALID_ARGUMENT, "mgx_beat_params.struct_size is %u, expected %zu", bp->struct_size, sizeof(mgx_beat_params));
+  if (bp->max_period < 1 || bp->max_period > MGX_BEAT_MAX_PERIOD)
+    return fail(MGX_E_INVALID_ARGUMENT, "mgx_beat_params.max_period is %u, expected 1..%d", bp->max_period, MGX_BEAT_MAX_PERIOD);
+  if (bp->trim > 1) return fail(MGX_E_INVALID_ARGUMENT, "mgx_beat_params.trim is %u, expected 0 or 1", bp->trim);
+  return MGX_OK;
+}
+
+uint64_t beat_gauss_count(uint32_t P) { return ((uint64_t)P + 1) * ((uint64_t)P + 2) / 2; }
+uint64_t beat_penalty_count(uint32_t P) { return ((uint64_t)P + 1) * ((uint64_t)P + 1); }
+
 // mgx_tempo_host: the tempogram, its pooling and the pick behind the host flux call, over the column of its request
 struct TempoHost {
   const mgx_tempo_params* params;
@@ -1929,6 +1952,7 @@ struct TempoHost {
   const double* prior;  // host, L, or null without lag
   double* summary;      // host, num_signals x MGX_NUM_STATS x L, or null
   uint32_t* lag;        // host, num_signals, or null
+  const BeatHost* beats;  // mgx_beats_host: the lags are picked (prior is set) whether `lag` is or not
 };
 
 int check_tempo_params(const mgx_tempo_params* tp) {
@@ -2514,6 +2538,7 @@ int summarize_host_impl(mgx_plan* p, const float* samples, uint64_t num_samples,
     if (pick) std::fill_n(pick->peak_offsets, nsignals + 1, (uint64_t)0);
     if (tempo && tempo->summary) std::fill_n(tempo->summary, nsignals * MGX_NUM_STATS * tempo->params->num_lags, std::nan(""));
     if (tempo && tempo->lag) std::fill_n(tempo->lag, nsignals, (uint32_t)0);
+    if (tempo && tempo->beats) std::fill_n(tempo->beats->peak_offsets, nsignals + 1, (uint64_t)0);
     return MGX_OK;
   }
   if (nsignals == 0 || (a.cols == 0 && !q.any() && !fq.any())) return gather_host_chunked(p, samples, starts, nframes, &x, nullptr);
@@ -2562,7 +2587,17 @@ int summarize_host_impl(mgx_plan* p, const float* samples, uint64_t num_samples,
   const uint64_t tempo_win = 0, tempo_prior = MGX_TEMPOGRAM_MAX_WIN * sizeof(float);
   const uint64_t tempo_ws = tempo_prior + MGX_TEMPOGRAM_MAX_WIN * sizeof(double);
   const uint64_t tempo_lag = tempo_ws + (tempo ? tempo_layout(nframes, nsignals, tempo_L, false).total : 0);
-  const uint64_t tempo_total = tempo_lag + (nsignals * sizeof(uint32_t) + 255) / 256 * 256;
+  // behind them, for mgx_beats_host: the two tables, the tracker's workspace, its offsets and the beats there is room for
+  const BeatHost* const beats = tempo ? tempo->beats : nullptr;
+  auto up256 = [](uint64_t bytes) { return (bytes + 255) / 256 * 256; };
+  const uint32_t beat_P = beats ? beats->params->max_period : 0;
+  const uint64_t beat_gauss = tempo_lag + up256(nsignals * sizeof(uint32_t));
+  const uint64_t beat_pen = beat_gauss + (beats ? up256(beat_gauss_count(beat_P) * sizeof(float)) : 0);
+  const uint64_t beat_ws = beat_pen + (beats ? up256(beat_penalty_count(beat_P) * sizeof(double)) : 0);
+  const uint64_t beat_off = beat_ws + (beats ? mgx::beats_workspace_bytes(nframes, nsignals) : 0);
+  const uint64_t beat_cap = beats && beats->peaks ? std::min(beats->capacity, nframes) : 0;
+  const uint64_t beat_rows = beat_off + (beats ? up256((nsignals + 1) * 8) : 0);
+  const uint64_t tempo_total = beat_rows + up256(beat_cap * 8);
   if (tempo && p->s_tempo_bytes < tempo_total) {
     if (p->s_tempo) (void)hipFree(p->s_tempo);
     p->s_tempo = nullptr;
@@ -2715,9 +2750,9 @@ int summarize_host_impl(mgx_plan* p, const float* samples, uint64_t num_samples,
       const mgx_tempo_params& tp = *tempo->params;
       const TempoLayout tl = tempo_layout(nframes, nsignals, tempo_L, false);
       e = hipMemcpyAsync(p->s_tempo + tempo_win, tempo->window, tp.win_length * sizeof(float), hipMemcpyHostToDevice, p->s_comp);
-      if (e == hipSuccess && tempo->lag)
+      if (e == hipSuccess && (tempo->lag || beats))
         e = hipMemcpyAsync(p->s_tempo + tempo_prior, tempo->prior, tp.num_lags * sizeof(double), hipMemcpyHostToDevice, p->s_comp);
-      uint32_t* const dlag = tempo->lag ? reinterpret_cast<uint32_t*>(p->s_tempo + tempo_lag) : nullptr;
+      uint32_t* const dlag = tempo->lag || beats ? reinterpret_cast<uint32_t*>(p->s_tempo + tempo_lag) : nullptr;
       if (e == hipSuccess)
         e = tempo_run(col[0], nframes, false, reinterpret_cast<const uint64_t*>(p->s_flux + fl.table), nsignals, tp,
                       reinterpret_cast<const float*>(p->s_tempo + tempo_win), reinterpret_cast<const double*>(p->s_tempo + tempo_prior),
@@ -2727,6 +2762,28 @@ int summarize_host_impl(mgx_plan* p, const float* samples, uint64_t num_samples,
                            hipMemcpyDeviceToHost, p->s_comp);
       if (e == hipSuccess && tempo->lag)
         e = hipMemcpyAsync(tempo->lag, dlag, nsignals * sizeof(uint32_t), hipMemcpyDeviceToHost, p->s_comp);
+      if (beats && e == hipSuccess) {
+        // the tracker over the same column, the lags where the pick left them as its periods; the counts and the
+        // beats alone cross back, the beats when the counts are known
+        e = hipMemcpyAsync(p->s_tempo + beat_gauss, beats->gauss, beat_gauss_count(beat_P) * sizeof(float), hipMemcpyHostToDevice, p->s_comp);
+        if (e == hipSuccess)
+          e = hipMemcpyAsync(p->s_tempo + beat_pen, beats->penalty, beat_penalty_count(beat_P) * sizeof(double), hipMemcpyHostToDevice,
+                             p->s_comp);
+        mgx_peak_outputs po{};
+        po.struct_size = sizeof(po);
+        po.peak_offsets = reinterpret_cast<uint64_t*>(p->s_tempo + beat_off);
+        po.peaks = beat_cap > 0 ? reinterpret_cast<uint64_t*>(p->s_tempo + beat_rows) : nullptr;
+        po.capacity = beat_cap;
+        if (e == hipSuccess)
+          e = mgx::launch_beats(col[0], nframes, false, reinterpret_cast<const uint64_t*>(p->s_flux + fl.table), nsignals, dlag, beat_P,
+                                beats->params->trim, reinterpret_cast<const float*>(p->s_tempo + beat_gauss),
+                                reinterpret_cast<const double*>(p->s_tempo + beat_pen), nullptr, nullptr, po, p->s_tempo + beat_ws, p->s_comp);
+        if (e == hipSuccess)
+          e = hipMemcpyAsync(beats->peak_offsets, po.peak_offsets, (nsignals + 1) * 8, hipMemcpyDeviceToHost, p->s_comp);
+        if (e == hipSuccess) e = hipStreamSynchronize(p->s_comp);
+        const uint64_t total = e == hipSuccess ? std::min(beats->peak_offsets[nsignals], beat_cap) : 0;
+        if (total > 0) e = hipMemcpyAsync(beats->peaks, po.peaks, total * 8, hipMemcpyDeviceToHost, p->s_comp);
+      }
     }
   }
   const hipError_t es = hipStreamSynchronize(p->s_comp);
@@ -3031,7 +3088,115 @@ int mgx_tempo_host(mgx_plan* p, const float* samples, uint64_t num_samples, cons
   if (lag && !prior) return fail(MGX_E_INVALID_ARGUMENT, "lag is set without prior");
   mgx_summary_outputs none{};
   none.struct_size = sizeof(none);
-  const TempoHost th{params, window, prior, summary, lag};
+  const TempoHost th{params, window, prior, summary, lag, nullptr};
+  return summarize_host_impl(p, samples, num_samples, starts, nframes, frame_offsets, nsignals, nullptr, nullptr, &none, nullptr, flux, 1,
+                             nullptr, &th);
+}
+
+void mgx_beat_params_init(mgx_beat_params* b) {
+  if (!b) return;
+  memset(b, 0, sizeof *b);
+  b->struct_size = sizeof *b;
+  b->max_period = MGX_BEAT_MAX_PERIOD;
+  b->trim = 1;
+}
+
+int mgx_beat_tables(uint32_t P, double tightness, float* gauss, double* penalty) {
+  if (P < 1 || P > MGX_BEAT_MAX_PERIOD) return fail(MGX_E_INVALID_ARGUMENT, "max_period is %u, expected 1..%d", P, MGX_BEAT_MAX_PERIOD);
+  if (!(std::isfinite(tightness) && tightness > 0)) return fail(MGX_E_INVALID_ARGUMENT, "tightness must be finite and positive");
+  if (!gauss) return fail(MGX_E_INVALID_ARGUMENT, "gauss is NULL");
+  if (!penalty) return fail(MGX_E_INVALID_ARGUMENT, "penalty is NULL");
+  const double ninf = -std::numeric_limits<double>::infinity();
+  gauss[0] = 1.0f;
+  penalty[0] = ninf;
+  for (uint32_t p = 1; p <= P; ++p) {
+    float* const g = gauss + (size_t)p * (p + 1) / 2;
+    for (uint32_t k = 0; k <= p; ++k) {
+      const double z = 32.0 * (double)k / (double)p;
+      g[k] = (float)std::exp(-0.5 * (z * z));
+    }
+    uint32_t lo = p / 2;
+    if (p & 1) lo += lo & 1;
+    lo = std::max(lo, 1u);
+    double* const w = penalty + (size_t)p * p;
+    for (uint32_t d = 0; d <= 2 * p; ++d) {
+      if (d < lo) {
+        w[d] = ninf;
+        continue;
+      }
+      const double l = std::log((double)d / (double)p);
+      w[d] = -tightness * (l * l);
+    }
+  }
+  return MGX_OK;
+}
+
+int mgx_beats_workspace_bytes(uint64_t num_frames, uint64_t num_signals, uint64_t* bytes) {
+  if (!bytes) return fail(MGX_E_INVALID_ARGUMENT, "bytes is NULL");
+  *bytes = mgx::beats_workspace_bytes(num_frames, num_signals);
+  return MGX_OK;
+}
+
+int mgx_beats_device(const void* envelope, uint64_t num_frames, uint32_t envelope_f64, const uint64_t* frame_offsets,
+                     uint64_t num_signals, const uint32_t* period, const mgx_beat_params* params, const float* gauss,
+                     const double* penalty, double* local_score, double* cum_score, const mgx_peak_outputs* out, void* workspace,
+                     uint64_t workspace_bytes, void* stream) {
+  const int rc = check_beat_params(params);
+  if (rc) return rc;
+  if (!out) return fail(MGX_E_INVALID_ARGUMENT, "out is NULL");
+  if (out->struct_size != sizeof(mgx_peak_outputs))
+    return fail(MGX_E_INVALID_ARGUMENT, "mgx_peak_outputs.struct_size is %u, expected %zu", out->struct_size, sizeof(mgx_peak_outputs));
+  if (envelope_f64 > 1) return fail(MGX_E_INVALID_ARGUMENT, "envelope_f64 is %u, expected 0 or 1", envelope_f64);
+  if (!period) return fail(MGX_E_INVALID_ARGUMENT, "period is NULL");
+  if (!gauss) return fail(MGX_E_INVALID_ARGUMENT, "gauss is NULL");
+  if (!penalty) return fail(MGX_E_INVALID_ARGUMENT, "penalty is NULL");
+  if (!out->mask && !out->peak_offsets && !out->peaks)
+    return fail(MGX_E_INVALID_ARGUMENT, "mgx_peak_outputs.mask, .peak_offsets and .peaks are all NULL");
+  if (out->peaks && out->capacity == 0) return fail(MGX_E_INVALID_ARGUMENT, "mgx_peak_outputs.peaks is set with capacity 0");
+  if (out->peak_starts && !out->starts) return fail(MGX_E_INVALID_ARGUMENT, "mgx_peak_outputs.peak_starts is set without starts");
+  if (out->peak_starts && !out->peaks) return fail(MGX_E_INVALID_ARGUMENT, "mgx_peak_outputs.peak_starts is set without peaks");
+  if (num_signals > 0 && !frame_offsets) return fail(MGX_E_INVALID_ARGUMENT, "frame_offsets is NULL");
+  if (num_frames > 0 && !envelope) return fail(MGX_E_INVALID_ARGUMENT, "envelope is NULL");
+  const uint64_t need = mgx::beats_workspace_bytes(num_frames, frame_offsets ? num_signals : 1);
+  if (workspace_bytes < need || (need > 0 && !workspace))
+    return fail(MGX_E_INVALID_ARGUMENT, "the workspace holds %llu bytes, the call needs %llu (mgx_beats_workspace_bytes)",
+                (unsigned long long)workspace_bytes, (unsigned long long)need);
+  if (need > 0 && reinterpret_cast<uintptr_t>(workspace) % 256 != 0)
+    return fail(MGX_E_INVALID_ARGUMENT, "the workspace is not 256-byte aligned");
+  if (num_frames == 0) {
+    // no rows, no beats: the offsets alone (frame_offsets with num_signals = 0: no signal, one entry)
+    if (!out->peak_offsets) return MGX_OK;
+    const uint64_t S = frame_offsets ? num_signals : 1;
+    const hipError_t e = hipMemsetAsync(out->peak_offsets, 0, (S + 1) * sizeof(uint64_t), (hipStream_t)stream);
+    return e == hipSuccess ? MGX_OK : hip_fail(e, "hipMemsetAsync(peak_offsets)");
+  }
+  const hipError_t e = mgx::launch_beats(envelope, num_frames, envelope_f64 != 0, frame_offsets, num_signals, period, params->max_period,
+                                         params->trim, gauss, penalty, local_score, cum_score, *out, workspace, (hipStream_t)stream);
+  return e == hipSuccess ? MGX_OK : hip_fail(e, "beat kernel launch");
+}
+
+int mgx_beats_host(mgx_plan* p, const float* samples, uint64_t num_samples, const uint64_t* starts, uint64_t nframes,
+                   const uint64_t* frame_offsets, uint64_t nsignals, const mgx_flux_request* flux, const mgx_tempo_params* tempo,
+                   const float* window, const double* prior, const mgx_beat_params* params, const float* gauss, const double* penalty,
+                   uint32_t* lag, uint64_t* peak_offsets, uint64_t* peaks, uint64_t capacity) {
+  int rc = check_tempo_params(tempo);
+  if (rc || (rc = check_beat_params(params))) return rc;
+  if (tempo->num_lags - 1 > params->max_period)
+    return fail(MGX_E_INVALID_ARGUMENT, "num_lags is %u: a lag may reach %u, above max_period %u", tempo->num_lags, tempo->num_lags - 1,
+                params->max_period);
+  if (nsignals == 0) return fail(MGX_E_INVALID_ARGUMENT, "num_signals is 0: beats are a clip's");
+  if (!flux) return fail(MGX_E_INVALID_ARGUMENT, "flux is NULL");
+  if (!window) return fail(MGX_E_INVALID_ARGUMENT, "window is NULL");
+  if (!prior) return fail(MGX_E_INVALID_ARGUMENT, "prior is NULL");
+  if (!gauss) return fail(MGX_E_INVALID_ARGUMENT, "gauss is NULL");
+  if (!penalty) return fail(MGX_E_INVALID_ARGUMENT, "penalty is NULL");
+  if (!peak_offsets) return fail(MGX_E_INVALID_ARGUMENT, "peak_offsets is NULL");
+  if (!peaks && capacity > 0) return fail(MGX_E_INVALID_ARGUMENT, "peaks is NULL with capacity %llu", (unsigned long long)capacity);
+  if (peaks && capacity == 0) return fail(MGX_E_INVALID_ARGUMENT, "peaks is set with capacity 0");
+  mgx_summary_outputs none{};
+  none.struct_size = sizeof(none);
+  const BeatHost bh{params, gauss, penalty, peak_offsets, peaks, capacity};
+  const TempoHost th{tempo, window, prior, nullptr, lag, &bh};
   return summarize_host_impl(p, samples, num_samples, starts, nframes, frame_offsets, nsignals, nullptr, nullptr, &none, nullptr, flux, 1,
                              nullptr, &th);
 }

@@ -47,6 +47,12 @@
 //                                   {frameOffsets, lag, bpm, numLags[, mean][, envelope]}
 //   Meyda.tempogramWindow(winLength), Meyda.tempoPrior(frameRate, numLags[, {startBpm, stdOctaves, maxBpm}])
 //                                   the periodic Hann window and the log-normal tempo prior (host only)
+//   getSignalBeats(signals, {getSignalTempo's options but mean, tightness, trim, maxPeriod}) / getSignalBeatsAsync(...)
+//                                   the beats of every signal: getSignalTempo's lag, and the buffers a dynamic
+//                                   programme places the beats on at that period, all on the device; only the lags
+//                                   and the beat lists cross back
+//   Meyda.beatTables(maxPeriod[, tightness])
+//                                   the tracker's tables {gauss, penalty} (host only)
 //   Meyda.signalsFrameStarts(lengths, bufferSize, hopSize)
 //                                   {starts, frameOffsets} of signals stored one after another
 //   Meyda.readWav(wavBytes)         the header: {pcmFormat, channels, sampleRate, sampleFrames, ...}
@@ -540,6 +546,38 @@ class Meyda {
       .then((r) => tempoResult(r, c.frameOffsets, o));
   }
 
+  // The beats of getBatchSignals' signals (librosa.beat.beat_track's tracker on the device): getSignalTempo's route gives
+  // every signal's lag, which is its beat period in buffers, and the tracker of include/meyda_gpu.h places the beats on
+  // the same onset envelope: a local score (the normalised envelope under a Gaussian of the period), a cumulative score
+  // with the penalty tightness (100) x log^2 on the distance to the beat before, the last beat at a late local maximum,
+  // the chain of back links and, with trim (true), the weak ends cut. The options are getSignalTempo's without `mean`,
+  // and tightness, trim, maxPeriod (default numLags - 1, the largest lag there can be; at most 1023) or tables, a
+  // Meyda.beatTables result for maxPeriod. Returns {frameOffsets, lag, bpm, numLags, beatOffsets, beats, signals}: beats
+  // the buffer indices over all signals, ascending, signal s owning beats[beatOffsets[s] .. beatOffsets[s + 1]), and
+  // signals[s] = {lag, bpm, beats}: the beats of signal s counted from its own first buffer.
+  getSignalBeats(signals, options) {
+    const o = beatOptions(options, this.sampleRate);
+    const c = this._concatSignals(signals, o.hopSize);
+    return beatResult(addon.beatsGather(this._plan(), c.samples, c.starts, c.frameOffsets, o.addon), c.frameOffsets, o);
+  }
+
+  getSignalBeatsAsync(signals, options) {
+    const o = beatOptions(options, this.sampleRate);
+    const c = this._concatSignals(signals, o.hopSize);
+    return this._runAsync((plan) => addon.beatsGatherAsync(plan, c.samples, c.starts, c.frameOffsets, o.addon))
+      .then((r) => beatResult(r, c.frameOffsets, o));
+  }
+
+  // The tracker's tables for the periods 1 .. maxPeriod: {gauss: Float32Array, penalty: Float64Array}. Host only.
+  static beatTables(maxPeriod, tightness) {
+    if (!Number.isInteger(maxPeriod) || maxPeriod < 1 || maxPeriod > 1023) throw new RangeError('maxPeriod must be an integer from 1 to 1023');
+    if (tightness === undefined) tightness = 100;
+    if (typeof tightness !== 'number' || !Number.isFinite(tightness) || !(tightness > 0)) {
+      throw new RangeError('tightness must be a positive finite number');
+    }
+    return addon.beatTables(maxPeriod, tightness);
+  }
+
   // The periodic Hann window of the tempogram, 0.5 - 0.5 cos(2 pi j / winLength): a Float32Array. Host only.
   static tempogramWindow(winLength) {
     if (!Number.isInteger(winLength) || winLength < 2 || winLength > 1024) throw new RangeError('winLength must be an integer from 2 to 1024');
@@ -939,6 +977,43 @@ function tempoResult(raw, frameOffsets, o) {
     for (let s = 0; s < S; ++s) r.mean.set(raw.summary.subarray(s * STATS.length * L, (s * STATS.length + 1) * L), s * L);
   }
   if (raw.envelope) r.envelope = raw.envelope;
+  return r;
+}
+
+// getSignalBeats' options: getSignalTempo's, and the tracker's as the addon takes them (the tables as arrays)
+function beatOptions(options, sampleRate) {
+  const o = tempoOptions(options, sampleRate);
+  if (options.mean) throw new TypeError('getSignalBeats has no mean: getSignalTempo returns the mean tempogram rows');
+  const reach = Math.max(o.addon.numLags - 1, 1);
+  const maxPeriod = options.maxPeriod === undefined ? reach : options.maxPeriod;
+  if (!Number.isInteger(maxPeriod) || maxPeriod < reach || maxPeriod > 1023) {
+    throw new RangeError('maxPeriod must be an integer from numLags - 1 to 1023');
+  }
+  const tightness = options.tightness === undefined ? 100 : options.tightness;
+  if (typeof tightness !== 'number' || !Number.isFinite(tightness) || !(tightness > 0)) {
+    throw new RangeError('tightness must be a positive finite number');
+  }
+  let tables = options.tables;
+  if (tables === undefined || tables === null) tables = addon.beatTables(maxPeriod, tightness);
+  else if (typeof tables !== 'object' || !(tables.gauss instanceof Float32Array) || !(tables.penalty instanceof Float64Array) ||
+    tables.gauss.length !== (maxPeriod + 1) * (maxPeriod + 2) / 2 || tables.penalty.length !== (maxPeriod + 1) * (maxPeriod + 1)) {
+    throw new TypeError('tables must be a Meyda.beatTables result for maxPeriod');
+  }
+  delete o.addon.mean;
+  Object.assign(o.addon, { maxPeriod, trim: options.trim === undefined ? true : !!options.trim, gauss: tables.gauss, penalty: tables.penalty });
+  return o;
+}
+
+function beatResult(raw, frameOffsets, o) {
+  const r = tempoResult(raw, frameOffsets, o);
+  r.beatOffsets = raw.beatOffsets;
+  r.beats = raw.beats;
+  r.signals = [];
+  for (let s = 0; s + 1 < frameOffsets.length; ++s) {
+    const rows = raw.beats.slice(raw.beatOffsets[s], raw.beatOffsets[s + 1]);
+    for (let i = 0; i < rows.length; ++i) rows[i] -= frameOffsets[s];
+    r.signals.push({ lag: r.lag[s], bpm: r.bpm[s], beats: rows });
+  }
   return r;
 }
 

@@ -372,9 +372,36 @@ static void validation() {
   CHECK(strlen(mgx_last_error()) > 0);
 }
 
+// mgx_beat_tables into blocks of exactly the stated sizes, for the smallest and the largest period and some between
+static void beat_tables() {
+  long n = 0;
+  for (uint32_t P : {1u, 2u, 3u, 7u, 128u, 1022u, (uint32_t)MGX_BEAT_MAX_PERIOD}) {
+    std::vector<float> gauss(((size_t)P + 1) * (P + 2) / 2, -1.0f);
+    std::vector<double> penalty(((size_t)P + 1) * (P + 1), 1.0);
+    CHECK(mgx_beat_tables(P, 100.0, gauss.data(), penalty.data()) == MGX_OK);
+    for (float v : gauss) CHECK(v >= 0.0f && v <= 1.0f);
+    for (double v : penalty) CHECK(v <= 0.0);
+    CHECK(gauss[0] == 1.0f && gauss.back() == 0.0f && penalty[(size_t)P * P + P] == 0.0);
+    n += (long)(gauss.size() + penalty.size());
+  }
+  float g1[3];
+  double p1[4];
+  CHECK(mgx_beat_tables(0, 100.0, g1, p1) == MGX_E_INVALID_ARGUMENT);
+  CHECK(mgx_beat_tables(MGX_BEAT_MAX_PERIOD + 1, 100.0, g1, p1) == MGX_E_INVALID_ARGUMENT);
+  CHECK(mgx_beat_tables(1, 0.0, g1, p1) == MGX_E_INVALID_ARGUMENT);
+  CHECK(mgx_beat_tables(1, 100.0, nullptr, p1) == MGX_E_INVALID_ARGUMENT);
+  CHECK(mgx_beat_tables(1, 100.0, g1, nullptr) == MGX_E_INVALID_ARGUMENT);
+  CHECK(mgx_beat_tables(1, 100.0, g1, p1) == MGX_OK);
+  uint64_t bytes = 1;
+  CHECK(mgx_beats_workspace_bytes(0, 0, &bytes) == MGX_OK && bytes == 0);
+  CHECK(mgx_beats_workspace_bytes(1000, 3, &bytes) == MGX_OK && bytes % 256 == 0 && bytes > 20000);
+  printf("beat tables: %ld entries\n", n);
+}
+
 int main() {
   wav_fuzz();
   host_tables();
+  beat_tables();
   arithmetic();
   frame_starts();
   out_fields();
