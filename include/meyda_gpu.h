@@ -1051,6 +1051,114 @@ int mgx_beats_host(mgx_plan* plan, const float* samples, uint64_t num_samples, c
                    const mgx_beat_params* params, const float* gauss, const double* penalty, uint32_t* lag,
                    uint64_t* peak_offsets, uint64_t* peaks, uint64_t capacity);
 
+/* ---- HPSS: the median-filter harmonic / percussive split of a clip's spectra ---------------------------
+ * Replaces, in a host application, the two median filters over the amplitude rows after they were copied back and
+ * the masks formed from them (Fitzgerald's median-filtering separation: librosa.decompose.hpss,
+ * librosa.effects.harmonic / percussive), and the upload of the two arrays that follows: onset, tempo and beat work
+ * runs on the percussive part, chroma on the harmonic part. The reference snapshot has no counterpart. Like the
+ * statistics, the deltas, the flux, the peaks, the chroma, the tempo and the beats it is no feature:
+ * MGX_NUM_FEATURES, the name table and every struct above are as they were.
+ *
+ * A signal owns rows [a, b), n = b - a, of an array of num_frames rows x cols float32 columns (row-major). The
+ * parameters are a time kernel Kt and a frequency kernel Kf, both odd and 1 .. MGX_HPSS_MAX_KERNEL; ht = Kt div 2,
+ * hf = Kf div 2.
+ *
+ * Order. Values are compared by the IEEE total order of their bit patterns, through the order-preserving key the
+ * beat tracker's selection uses: all bits of a negative value flipped, the sign bit of a non-negative one set,
+ * compared as unsigned. So -0 < +0, and a NaN with a clear sign bit sorts above +Infinity (one with the sign bit set
+ * below -Infinity). The median of an odd window is therefore always one element of the window, bit for bit (a NaN's
+ * payload included), and a lone NaN or overflowed amplitude in a window does not become the median.
+ *
+ * Reflection. An index u outside [0, m) is taken at r(u, m): q = u mod 2m, taken in [0, 2m); r = q if q < m, else
+ * 2m - 1 - q. This is the half-sample symmetric extension d c b a | a b c d | d c b a, repeated as often as the
+ * window needs (a clip of 2 rows under Kt = 31).
+ *
+ *   H(t, k) = the median of x(a + r(t - a + j, n), k), j = -ht .. ht     along time, inside the row's own clip only
+ *   P(t, k) = the median of x(t, r(k + j, cols)),      j = -hf .. hf     along frequency, inside the row
+ *
+ * MGX_HPSS_MEDIANS: the two outputs are H and P themselves (the building block of librosa.decompose.nn_filter-style
+ * work).
+ * MGX_HPSS_SOFT1, MGX_HPSS_SOFT2: the soft masks of power p = 1, 2. Values are taken as float64 (a float32 converts
+ * exactly); the margins mh, mp are float32, finite and >= 1. For the harmonic output: A = |H|; R = |P| mh (the
+ * product of two float32 is exact); hp = A^p, rp = R^p (for p = 2 one multiplication each, rounded once; A A is
+ * exact); den = hp + rp, rounded once, never fused; if den == 0 (both medians are zero) the mask is 0.5 when mh == 1
+ * and mp == 1, else 0 (librosa's split_zeros); otherwise mask = hp / den, one correctly rounded float64 division;
+ * y = x(t, k) mask, rounded once in float64 and then once to float32. The percussive output is the same with the
+ * roles swapped: A = |P|, R = |H| mp.
+ * MGX_HPSS_HARD: librosa's power = inf. The harmonic output is x where |H| > |P| mh and +0 elsewhere, the percussive
+ * one x where |P| > |H| mp and +0 elsewhere; the comparison is the IEEE one, so a NaN median gives +0.
+ * Non-finite values follow IEEE: an infinite median gives Inf / Inf = NaN in its own element.
+ *
+ * Differences from librosa: its division of both terms by max(X, R) is dropped -- float64 squares of float32 values
+ * neither overflow nor underflow, so the zero rule is an exact zero and no comparison with `tiny`; and the arithmetic
+ * is float64 with one final rounding, where librosa works in the array's float32.
+ * With this order and reflection a numpy statement (tests/hpss_ref.py) equals scipy.ndimage.median_filter(...,
+ * mode='reflect') bit for bit on finite non-negative input along both axes for every n <= 19 and odd K <= 63, except
+ * for a few cases with K div 2 >= 4 n, where scipy's far extension of a 2-, 4- or 6-row input departs from a periodic
+ * reflection. The definition is the formula above, not scipy.
+ *
+ * An empty signal writes nothing; rows that belong to no signal are not written. A value is a function of its own
+ * signal's rows alone: no atomics, and the same bits from every call below, from a repeated call, from a graph replay
+ * and from any grid. */
+typedef enum mgx_hpss_mode {
+  MGX_HPSS_MEDIANS = 0,
+  MGX_HPSS_SOFT1 = 1,
+  MGX_HPSS_SOFT2 = 2,
+  MGX_HPSS_HARD = 3,
+  MGX_NUM_HPSS_MODES = 4
+} mgx_hpss_mode;
+#define MGX_HPSS_MAX_KERNEL 31
+/* The kernel's tile (mgx_hpss_tile reports it): a clip whose length straddles MGX_HPSS_TILE_ROWS, or an array whose
+ * width straddles MGX_HPSS_TILE_COLS, takes another path through it. Not part of the definition. */
+#define MGX_HPSS_TILE_ROWS 64
+#define MGX_HPSS_TILE_COLS 64
+typedef struct mgx_hpss_params {
+  uint32_t struct_size;      /* = sizeof(mgx_hpss_params), 24; anything else: MGX_E_INVALID_ARGUMENT */
+  uint32_t kernel_time, kernel_freq;   /* Kt, Kf; 31, 31 */
+  uint32_t mode;             /* mgx_hpss_mode; MGX_HPSS_SOFT2 */
+  float margin_harmonic, margin_percussive;   /* 1, 1 */
+} mgx_hpss_params;
+void mgx_hpss_params_init(mgx_hpss_params* params);
+void mgx_hpss_tile(uint32_t* tile_rows, uint32_t* tile_cols);  /* either may be NULL */
+
+/* The operator on device arrays; no plan: asynchronous on `stream`, no allocation, no workspace, no host-side
+ * state, capturable; one launch that reads the array once. rows, harmonic, percussive: num_frames x cols float32;
+ * either output may be NULL, not both. The table is read as mgx_delta_device reads it, every entry limited to
+ * num_frames: a non-decreasing one gives the definition above, any other gives unspecified values and no access
+ * outside the arrays. NULL with num_signals = 0 means one signal [0, num_frames).
+ * MGX_E_INVALID_ARGUMENT before any launch: NULL params or a bad struct_size, an even kernel or one outside 1 ..
+ * MGX_HPSS_MAX_KERNEL, mode >= MGX_NUM_HPSS_MODES, a margin that is NaN, infinite or below 1, cols = 0, both outputs
+ * NULL, an output equal to rows or to the other output (halos are read: the operator cannot run in place),
+ * num_signals > 0 with NULL frame_offsets, NULL rows with num_frames > 0. num_frames = 0 returns MGX_OK and writes
+ * nothing. */
+int mgx_hpss_device(const float* rows, uint64_t num_frames, uint32_t cols,
+                    const uint64_t* frame_offsets, uint64_t num_signals,
+                    const mgx_hpss_params* params,
+                    float* harmonic, float* percussive, void* stream);
+
+/* Host pointers throughout: mgx_extract_gather_host with the amplitude spectrum as a field that does not cross back.
+ * A time median reaches across chunk ends, so each chunk's amplitude rows are copied, device to device, into a
+ * plan-owned num_frames x N/2 array that lasts as long as the call (as the delta host call keeps its rows; grown on
+ * demand, freed at mgx_plan_destroy; MGX_E_OUT_OF_MEMORY when the device has no room). After the last chunk
+ * mgx_hpss_device runs once over it; the harmonic and percussive arrays are plan-owned too, and only those that
+ * something consumes are allocated. Then mgx_chroma_device runs on the harmonic rows (harmonic_chroma) and
+ * mgx_flux_device on the percussive rows (percussive_flux, whose field must be MGX_AMPLITUDE_SPECTRUM); per_frame and
+ * summary of either request are written and pooled exactly as mgx_chroma_host and mgx_summarize_flux_host write and
+ * pool them. harmonic, percussive: num_frames x N/2 floats each, or NULL; of these the rows of the signals alone are
+ * written, as the operator writes them (every row when frame_offsets is NULL with num_signals = 0). The result equals
+ * the composition of the device operators on the rows mgx_extract_gather_host returns, bit for bit, wherever the
+ * chunks end. Only what the caller names crosses back.
+ * MGX_E_INVALID_ARGUMENT: all four outputs NULL, NULL params, and every refusal of mgx_hpss_device, mgx_chroma_host
+ * and the flux request of mgx_summarize_flux_host about the arguments they share (a request with both pointers NULL, a
+ * summary with num_signals = 0); a flux field other than MGX_AMPLITUDE_SPECTRUM is MGX_E_UNSUPPORTED. */
+int mgx_hpss_host(mgx_plan* plan, const float* samples, uint64_t num_samples,
+                  const uint64_t* starts, uint64_t num_frames,
+                  const uint64_t* frame_offsets, uint64_t num_signals,
+                  const mgx_hpss_params* params,
+                  const mgx_chroma_request* harmonic_chroma,   /* or NULL */
+                  const mgx_flux_request* percussive_flux,     /* or NULL; field must be MGX_AMPLITUDE_SPECTRUM */
+                  float* harmonic, float* percussive);         /* num_frames x N/2 each, or NULL */
+
 /* ---- Multi-device groups -------------------------------
  * Replaces nothing in the reference (single-threaded browser code); it exists because
  * buffers are independent (src/meyda.js:69-91 keeps no cross-buffer state), so a batch

@@ -32,6 +32,14 @@
  *                                        -> { chroma: Float32Array(nframes x numChroma), numChroma[, summary:
  *                                           Float64Array(S x 4 x numChroma)] }: the chroma rows of every buffer,
  *                                           computed on the device from spectra that stay there (mgx_chroma_host)
+ *   hpssGather(plan, samples, starts, frameOffsets | null, {kernelTime, kernelFreq, mode, marginHarmonic,
+ *              marginPercussive, harmonic, percussive, chroma: {weights, numChroma, norm, perFrame, summary},
+ *              flux: {mode, lag, perFrame, summary}}) / hpssGatherAsync(...)
+ *                                        -> { [harmonic, percussive: Float32Array(nframes x bufferSize / 2)]
+ *                                           [, chroma, numChroma, chromaSummary][, flux, fluxSummary] }: the median-filter
+ *                                           harmonic / percussive split of every buffer's amplitude spectrum within its
+ *                                           signal, the chroma of the harmonic rows and the flux of the percussive rows,
+ *                                           computed on the device from spectra that stay there (mgx_hpss_host)
  *   tempogramWindow(winLength)           -> Float32Array(winLength): the periodic Hann window (mgx_tempogram_window; host only)
  *   tempoPrior(frameRate, numLags[, {startBpm, stdOctaves, maxBpm}])
  *                                        -> Float64Array(numLags): the log-normal tempo prior (mgx_tempo_prior; host only)
@@ -326,6 +334,14 @@ typedef struct {
   int chroma;
   mgx_chroma_request creq;
   napi_ref crefs[3];  /* the bank (kept alive), the rows, the summaries */
+  /* hpssGather: a gather job whose outputs are the harmonic and percussive parts of the amplitude rows, the chroma of
+   * the harmonic part (creq, crefs) and the flux of the percussive part (flux[0], frefs[.][0]), each where asked for
+   * (mgx_hpss_host) */
+  int hpss;
+  mgx_hpss_params hpar;
+  int hchroma, hflux;
+  float* hparts[2];
+  napi_ref hrefs[2];  /* the harmonic rows, the percussive rows */
   /* tempoGather: a gather job whose outputs are the lag a tempo prior picks from the mean tempogram row of flux[0]'s
    * column within every signal, and with the option mean the pooled tempogram rows (mgx_tempo_host) */
   int tempo;
@@ -372,6 +388,11 @@ static void job_free_buffers(napi_env env, job* j) {
     if (j->crefs[i]) {
       napi_delete_reference(env, j->crefs[i]);
       j->crefs[i] = NULL;
+    }
+  for (int i = 0; i < 2; ++i)
+    if (j->hrefs[i]) {
+      napi_delete_reference(env, j->hrefs[i]);
+      j->hrefs[i] = NULL;
     }
   for (int i = 0; i < 4; ++i)
     if (j->trefs[i]) {
@@ -904,6 +925,177 @@ static int job_prepare_chroma(napi_env env, job* j, napi_value samples_v, napi_v
   return 1;
 }
 
+/* A new ArrayBuffer of `bytes` zero bytes, held by *ref. 0 with an error pending. */
+static int zeroed_buffer(napi_env env, size_t bytes, napi_ref* ref, void** out) {
+  napi_value ab;
+  void* data = NULL;
+  if (napi_create_arraybuffer(env, bytes, &data, &ab) != napi_ok || napi_create_reference(env, ab, 1, ref) != napi_ok) {
+    napi_throw_error(env, NULL, "out of host memory");
+    return 0;
+  }
+  memset(data, 0, bytes);
+  *out = data;
+  return 1;
+}
+
+/* A boolean property of the options object; absent or undefined: dflt. */
+static bool option_bool(napi_env env, napi_value obj, const char* name, bool dflt) {
+  napi_value v;
+  bool b = dflt;
+  if (option_given(env, obj, name, &v)) napi_coerce_to_bool(env, v, &v), napi_get_value_bool(env, v, &b);
+  return b;
+}
+
+/* hpssGather(plan, samples, starts, frameOffsets, options): extractGather's inputs, the table of the signals' buffers
+ * or null (one signal: every buffer), and options: {kernelTime = 31, kernelFreq = 31 (odd, 1 .. 31), mode = 2 (0 medians,
+ * 1 soft1, 2 soft2, 3 hard), marginHarmonic = 1, marginPercussive = 1 (>= 1), harmonic = false, percussive = false (the
+ * rows themselves), chroma: {weights, numChroma, norm = 1, perFrame = true, summary = false} (of the harmonic rows),
+ * flux: {mode = 0, lag = 1, perFrame = true, summary = false} (of the percussive rows)}; one output at least. */
+static int job_prepare_hpss(napi_env env, job* j, napi_value samples_v, napi_value starts_v, napi_value offsets_v,
+                            napi_value options_v) {
+  napi_valuetype ot = napi_undefined;
+  napi_typeof(env, options_v, &ot);
+  if (ot != napi_object) {
+    napi_throw_type_error(env, NULL, "options must be an object: {kernelTime, kernelFreq, mode, marginHarmonic, marginPercussive, harmonic, percussive, chroma, flux}");
+    return 0;
+  }
+  j->hpss = 1;
+  mgx_hpss_params* h = &j->hpar;
+  mgx_hpss_params_init(h);
+  const char* const kname[2] = {"kernelTime", "kernelFreq"};
+  uint32_t* const kdst[2] = {&h->kernel_time, &h->kernel_freq};
+  for (int i = 0; i < 2; ++i) {
+    if (!option_u32(env, options_v, kname[i], 1, MGX_HPSS_MAX_KERNEL, MGX_HPSS_MAX_KERNEL, kdst[i])) return 0;
+    if (!(*kdst[i] & 1u)) {
+      char msg[64];
+      snprintf(msg, sizeof msg, "%s must be odd", kname[i]);
+      napi_throw_range_error(env, NULL, msg);
+      return 0;
+    }
+  }
+  if (!option_u32(env, options_v, "mode", 0, MGX_NUM_HPSS_MODES - 1, MGX_HPSS_SOFT2, &h->mode)) return 0;
+  const char* const mname[2] = {"marginHarmonic", "marginPercussive"};
+  float* const mdst[2] = {&h->margin_harmonic, &h->margin_percussive};
+  for (int i = 0; i < 2; ++i) {
+    double m = 1.0;
+    if (!option_f64(env, options_v, mname[i], &m)) return 0;
+    if (!(m >= 1.0) || (double)(float)m - (double)(float)m != 0) {
+      char msg[64];
+      snprintf(msg, sizeof msg, "%s must be a finite number >= 1", mname[i]);
+      napi_throw_range_error(env, NULL, msg);
+      return 0;
+    }
+    *mdst[i] = (float)m;
+  }
+  const bool want_part[2] = {option_bool(env, options_v, "harmonic", false), option_bool(env, options_v, "percussive", false)};
+  napi_value cv, fv, v, ab;
+  napi_typedarray_type tt = napi_int8_array;
+  size_t len = 0, off = 0, count = 0;
+  void* data = NULL;
+  bool is_ta = false, chroma_rows = true, chroma_summary = false, flux_rows = true, flux_summary = false;
+  const size_t cols = j->box->desc.buffer_size / 2;
+  if (option_given(env, options_v, "chroma", &cv)) {
+    napi_typeof(env, cv, &ot);
+    if (ot != napi_object) {
+      napi_throw_type_error(env, NULL, "chroma must be an object: {weights, numChroma, norm, perFrame, summary}");
+      return 0;
+    }
+    j->hchroma = 1;
+    mgx_chroma_request* r = &j->creq;
+    r->struct_size = sizeof *r;
+    if (!option_u32(env, cv, "numChroma", 1, MGX_CHROMA_MAX_BINS, 12, &r->num_chroma)) return 0;
+    if (!option_u32(env, cv, "norm", 0, MGX_NUM_CHROMA_NORMS - 1, MGX_CHROMA_NORM_MAX, &r->norm)) return 0;
+    chroma_rows = option_bool(env, cv, "perFrame", true);
+    chroma_summary = option_bool(env, cv, "summary", false);
+    if (option_given(env, cv, "weights", &v)) napi_is_typedarray(env, v, &is_ta);
+    if (is_ta) napi_get_typedarray_info(env, v, &tt, &len, &data, &ab, &off);
+    if (!is_ta || tt != napi_float32_array) {
+      napi_throw_type_error(env, NULL, "chroma.weights must be a Float32Array");
+      return 0;
+    }
+    if (len != (size_t)r->num_chroma * cols) {
+      napi_throw_range_error(env, NULL, "chroma.weights.length must be numChroma x bufferSize / 2");
+      return 0;
+    }
+    if (!chroma_rows && !chroma_summary) {
+      napi_throw_range_error(env, NULL, "chroma asks for neither perFrame nor summary");
+      return 0;
+    }
+    if (napi_create_reference(env, v, 1, &j->crefs[0]) != napi_ok) return 0;
+    r->weights = (const float*)data;
+  }
+  if (option_given(env, options_v, "flux", &fv)) {
+    napi_typeof(env, fv, &ot);
+    if (ot != napi_object) {
+      napi_throw_type_error(env, NULL, "flux must be an object: {mode, lag, perFrame, summary}");
+      return 0;
+    }
+    j->hflux = 1;
+    mgx_flux_request* r = &j->flux[0];
+    r->struct_size = sizeof *r;
+    r->field = MGX_AMPLITUDE_SPECTRUM;
+    if (!option_u32(env, fv, "mode", 0, MGX_NUM_FLUX_MODES - 1, MGX_FLUX_RECTIFIED, &r->mode)) return 0;
+    if (!option_u32(env, fv, "lag", 1, MGX_FLUX_MAX_LAG, 1, &r->lag)) return 0;
+    flux_rows = option_bool(env, fv, "perFrame", true);
+    flux_summary = option_bool(env, fv, "summary", false);
+    if (!flux_rows && !flux_summary) {
+      napi_throw_range_error(env, NULL, "flux asks for neither perFrame nor summary");
+      return 0;
+    }
+  }
+  if (!want_part[0] && !want_part[1] && !j->hchroma && !j->hflux) {
+    napi_throw_range_error(env, NULL, "nothing asked for: harmonic, percussive, chroma or flux");
+    return 0;
+  }
+  napi_typeof(env, offsets_v, &ot);
+  if (ot != napi_undefined && ot != napi_null) {
+    j->frame_offsets = u64_of_f64(env, offsets_v, "frameOffsets", &count);
+    if (!j->frame_offsets) return 0;
+    if (count < 1) {
+      napi_throw_range_error(env, NULL, "frameOffsets holds one entry more than there are signals");
+      return 0;
+    }
+    j->nsignals = count - 1;
+  }
+  if (((j->hchroma && chroma_summary) || (j->hflux && flux_summary)) && j->nsignals == 0) {
+    napi_throw_range_error(env, NULL, "summary needs frameOffsets with a signal");
+    return 0;
+  }
+  is_ta = false;
+  napi_is_typedarray(env, samples_v, &is_ta);
+  if (is_ta) napi_get_typedarray_info(env, samples_v, &tt, &len, &data, &ab, &off);
+  if (!is_ta || tt != napi_float32_array) {
+    napi_throw_type_error(env, NULL, "samples must be a Float32Array");
+    return 0;
+  }
+  if (j->box->group) {
+    napi_throw_error(env, NULL, "starts are not supported on a plan created with `devices`: device groups take dense buffers only");
+    return 0;
+  }
+  j->starts = u64_of_f64(env, starts_v, "starts", &count);
+  if (!j->starts) return 0;
+  j->gather = 1;
+  j->frames = (const float*)data;
+  j->nsamples = len;
+  j->nframes = count;
+  for (int i = 0; i < 2; ++i)
+    if (want_part[i] && !zeroed_buffer(env, (size_t)j->nframes * cols * sizeof(float), &j->hrefs[i], (void**)&j->hparts[i])) return 0;
+  if (j->hchroma) {
+    mgx_chroma_request* r = &j->creq;
+    if (chroma_rows && !zeroed_buffer(env, (size_t)j->nframes * r->num_chroma * sizeof(float), &j->crefs[1], (void**)&r->per_frame)) return 0;
+    if (chroma_summary &&
+        !zeroed_buffer(env, (size_t)j->nsignals * MGX_NUM_STATS * r->num_chroma * sizeof(double), &j->crefs[2], (void**)&r->summary))
+      return 0;
+  }
+  if (j->hflux) {
+    mgx_flux_request* r = &j->flux[0];
+    if (flux_rows && !zeroed_buffer(env, (size_t)j->nframes * sizeof(float), &j->frefs[1][0], (void**)&r->per_frame)) return 0;
+    if (flux_summary && !zeroed_buffer(env, (size_t)j->nsignals * MGX_NUM_STATS * sizeof(double), &j->frefs[0][0], (void**)&r->summary))
+      return 0;
+  }
+  return 1;
+}
+
 /* A typed-array property of the options object of the given type and length, kept alive by *ref. 0 with an error pending. */
 static int option_typed(napi_env env, napi_value obj, const char* name, napi_typedarray_type want, size_t count, napi_ref* ref,
                         void** out) {
@@ -1172,7 +1364,10 @@ static void job_run(job* j) {
     return;
   }
   const uint32_t n = j->box->desc.buffer_size;
-  if (j->chroma)
+  if (j->hpss)
+    j->rc = mgx_hpss_host(j->box->plan, j->frames, j->nsamples, j->starts, j->nframes, j->frame_offsets, j->nsignals, &j->hpar,
+                          j->hchroma ? &j->creq : NULL, j->hflux ? &j->flux[0] : NULL, j->hparts[0], j->hparts[1]);
+  else if (j->chroma)
     j->rc = mgx_chroma_host(j->box->plan, j->frames, j->nsamples, j->starts, j->nframes, j->frame_offsets, j->nsignals, &j->creq);
   else if (j->beats)
     j->rc = mgx_beats_host(j->box->plan, j->frames, j->nsamples, j->starts, j->nframes, j->frame_offsets, j->nsignals, &j->flux[0],
@@ -1235,6 +1430,29 @@ static napi_value job_result(napi_env env, job* j) {
       "perceptualSharpness"};
   napi_value obj;
   if (napi_create_object(env, &obj) != napi_ok) return NULL;
+  if (j->hpss) {
+    const size_t cols = j->box->desc.buffer_size / 2, C = j->creq.num_chroma;
+    static const char* const part[2] = {"harmonic", "percussive"};
+    for (int i = 0; i < 2; ++i)
+      if (j->hrefs[i])
+        napi_set_named_property(env, obj, part[i], typed_of(env, j->hrefs[i], (size_t)j->nframes * cols * sizeof(float), napi_float32_array, 4));
+    if (j->hchroma) {
+      napi_value nc;
+      if (napi_create_uint32(env, (uint32_t)C, &nc) != napi_ok) return NULL;
+      napi_set_named_property(env, obj, "numChroma", nc);
+      if (j->crefs[1])
+        napi_set_named_property(env, obj, "chroma", typed_of(env, j->crefs[1], (size_t)j->nframes * C * sizeof(float), napi_float32_array, 4));
+      if (j->crefs[2])
+        napi_set_named_property(env, obj, "chromaSummary",
+                                typed_of(env, j->crefs[2], (size_t)j->nsignals * MGX_NUM_STATS * C * sizeof(double), napi_float64_array, 8));
+    }
+    if (j->frefs[1][0])
+      napi_set_named_property(env, obj, "flux", typed_of(env, j->frefs[1][0], (size_t)j->nframes * sizeof(float), napi_float32_array, 4));
+    if (j->frefs[0][0])
+      napi_set_named_property(env, obj, "fluxSummary",
+                              typed_of(env, j->frefs[0][0], (size_t)j->nsignals * MGX_NUM_STATS * sizeof(double), napi_float64_array, 8));
+    return obj;
+  }
   if (j->chroma) {
     napi_value nc;
     const size_t C = j->creq.num_chroma;
@@ -1340,7 +1558,7 @@ static napi_value job_result(napi_env env, job* j) {
 }
 
 /* kind: the input of an extraction job */
-enum { IN_FRAMES = 0, IN_WAV = 1, IN_SIGNAL = 2, IN_GATHER = 3, IN_SUMMARY = 4, IN_ONSETS = 5, IN_CHROMA = 6, IN_TEMPO = 7, IN_BEATS = 8 };
+enum { IN_FRAMES = 0, IN_WAV = 1, IN_SIGNAL = 2, IN_GATHER = 3, IN_SUMMARY = 4, IN_ONSETS = 5, IN_CHROMA = 6, IN_TEMPO = 7, IN_BEATS = 8, IN_HPSS = 9 };
 
 static int job_prepare_kind(napi_env env, job* j, int kind, size_t argc, napi_value* argv) {
   if (kind == IN_WAV) return job_prepare_wav(env, j, argv[1], argv[2], argc > 3 ? argv[3] : NULL, argc > 4 ? argv[4] : NULL);
@@ -1349,6 +1567,7 @@ static int job_prepare_kind(napi_env env, job* j, int kind, size_t argc, napi_va
   if (kind == IN_SUMMARY) return job_prepare_summary(env, j, argv[1], argv[2], argv[3], argv[4], argc > 5 ? argv[5] : NULL);
   if (kind == IN_ONSETS) return job_prepare_onsets(env, j, argv[1], argv[2], argv[3], argv[4]);
   if (kind == IN_CHROMA) return job_prepare_chroma(env, j, argv[1], argv[2], argv[3], argv[4]);
+  if (kind == IN_HPSS) return job_prepare_hpss(env, j, argv[1], argv[2], argv[3], argv[4]);
   if (kind == IN_TEMPO || kind == IN_BEATS) return job_prepare_tempo(env, j, argv[1], argv[2], argv[3], argv[4], kind == IN_BEATS);
   return job_prepare(env, j, argv[1], argv[2]);
 }
@@ -1357,8 +1576,9 @@ static napi_value extract_common(napi_env env, napi_callback_info info, int kind
   size_t argc = 6;
   napi_value argv[6];
   CHECK(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
-  if (argc < (kind == IN_SUMMARY || kind == IN_ONSETS || kind == IN_CHROMA || kind == IN_TEMPO || kind == IN_BEATS ? 5u : kind == IN_SIGNAL || kind == IN_GATHER ? 4u : 3u)) {
+  if (argc < (kind == IN_SUMMARY || kind == IN_ONSETS || kind == IN_CHROMA || kind == IN_TEMPO || kind == IN_BEATS || kind == IN_HPSS ? 5u : kind == IN_SIGNAL || kind == IN_GATHER ? 4u : 3u)) {
     napi_throw_type_error(env, NULL, kind == IN_WAV ? "extractWav(plan, wavBytes, features[, channel[, hop]])"
+                                   : kind == IN_HPSS ? "hpssGather(plan, samples, starts, frameOffsets, {kernelTime, kernelFreq, mode, ...})"
                                    : kind == IN_CHROMA ? "chromaGather(plan, samples, starts, frameOffsets, {weights, numChroma, ...})"
                                    : kind == IN_TEMPO ? "tempoGather(plan, samples, starts, frameOffsets, {field, window, prior, ...})"
                                    : kind == IN_BEATS ? "beatsGather(plan, samples, starts, frameOffsets, {field, window, prior, gauss, penalty, ...})"
@@ -1487,6 +1707,7 @@ static napi_value extract_gather_sync(napi_env env, napi_callback_info info) { r
 static napi_value summarize_gather_sync(napi_env env, napi_callback_info info) { return extract_common(env, info, IN_SUMMARY); }
 static napi_value onsets_gather_sync(napi_env env, napi_callback_info info) { return extract_common(env, info, IN_ONSETS); }
 static napi_value chroma_gather_sync(napi_env env, napi_callback_info info) { return extract_common(env, info, IN_CHROMA); }
+static napi_value hpss_gather_sync(napi_env env, napi_callback_info info) { return extract_common(env, info, IN_HPSS); }
 static napi_value tempo_gather_sync(napi_env env, napi_callback_info info) { return extract_common(env, info, IN_TEMPO); }
 static napi_value beats_gather_sync(napi_env env, napi_callback_info info) { return extract_common(env, info, IN_BEATS); }
 
@@ -1519,8 +1740,9 @@ static napi_value extract_async_common(napi_env env, napi_callback_info info, in
   size_t argc = 6;
   napi_value argv[6];
   CHECK(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
-  if (argc < (kind == IN_SUMMARY || kind == IN_ONSETS || kind == IN_CHROMA || kind == IN_TEMPO || kind == IN_BEATS ? 5u : kind == IN_SIGNAL || kind == IN_GATHER ? 4u : 3u)) {
+  if (argc < (kind == IN_SUMMARY || kind == IN_ONSETS || kind == IN_CHROMA || kind == IN_TEMPO || kind == IN_BEATS || kind == IN_HPSS ? 5u : kind == IN_SIGNAL || kind == IN_GATHER ? 4u : 3u)) {
     napi_throw_type_error(env, NULL, kind == IN_WAV ? "extractWavAsync(plan, wavBytes, features[, channel[, hop]])"
+                                   : kind == IN_HPSS ? "hpssGatherAsync(plan, samples, starts, frameOffsets, {kernelTime, kernelFreq, mode, ...})"
                                    : kind == IN_CHROMA ? "chromaGatherAsync(plan, samples, starts, frameOffsets, {weights, numChroma, ...})"
                                    : kind == IN_TEMPO ? "tempoGatherAsync(plan, samples, starts, frameOffsets, {field, window, prior, ...})"
                                    : kind == IN_BEATS ? "beatsGatherAsync(plan, samples, starts, frameOffsets, {field, window, prior, gauss, penalty, ...})"
@@ -1562,6 +1784,7 @@ static napi_value extract_gather_async(napi_env env, napi_callback_info info) { 
 static napi_value summarize_gather_async(napi_env env, napi_callback_info info) { return extract_async_common(env, info, IN_SUMMARY); }
 static napi_value onsets_gather_async(napi_env env, napi_callback_info info) { return extract_async_common(env, info, IN_ONSETS); }
 static napi_value chroma_gather_async(napi_env env, napi_callback_info info) { return extract_async_common(env, info, IN_CHROMA); }
+static napi_value hpss_gather_async(napi_env env, napi_callback_info info) { return extract_async_common(env, info, IN_HPSS); }
 static napi_value tempo_gather_async(napi_env env, napi_callback_info info) { return extract_async_common(env, info, IN_TEMPO); }
 static napi_value beats_gather_async(napi_env env, napi_callback_info info) { return extract_async_common(env, info, IN_BEATS); }
 
@@ -1946,6 +2169,8 @@ static napi_value init(napi_env env, napi_value exports) {
       {"chromaGather", NULL, chroma_gather_sync, NULL, NULL, NULL, napi_enumerable, NULL},
       {"chromaGatherAsync", NULL, chroma_gather_async, NULL, NULL, NULL, napi_enumerable, NULL},
       {"chromaWeights", NULL, chroma_weights, NULL, NULL, NULL, napi_enumerable, NULL},
+      {"hpssGather", NULL, hpss_gather_sync, NULL, NULL, NULL, napi_enumerable, NULL},
+      {"hpssGatherAsync", NULL, hpss_gather_async, NULL, NULL, NULL, napi_enumerable, NULL},
       {"tempoGather", NULL, tempo_gather_sync, NULL, NULL, NULL, napi_enumerable, NULL},
       {"tempoGatherAsync", NULL, tempo_gather_async, NULL, NULL, NULL, napi_enumerable, NULL},
       {"tempogramWindow", NULL, tempogram_window, NULL, NULL, NULL, napi_enumerable, NULL},

@@ -47,6 +47,7 @@ EXPORTS = ["mgx_plan_desc_init", "mgx_plan_create", "mgx_plan_destroy", "mgx_pla
            "mgx_tempo_params_init", "mgx_tempogram_window", "mgx_tempo_prior", "mgx_tempogram_device",
            "mgx_tempo_workspace_bytes", "mgx_tempo_device", "mgx_tempo_host",
            "mgx_beat_params_init", "mgx_beat_tables", "mgx_beats_workspace_bytes", "mgx_beats_device", "mgx_beats_host",
+           "mgx_hpss_params_init", "mgx_hpss_tile", "mgx_hpss_device", "mgx_hpss_host",
            "mgx_shard_range", "mgx_packed_layout", "mgx_comm_unique_id", "mgx_group_create",
            "mgx_group_create_rank", "mgx_group_create_loopback", "mgx_group_create_loopback_rccl", "mgx_group_destroy",
            "mgx_group_info", "mgx_group_comm_info", "mgx_group_extract_device", "mgx_group_extract_host"]
@@ -247,6 +248,61 @@ def tempo_params(win_length=None, num_lags=None, norm=None, gain=None):
     return p
 
 
+HPSS_MODES = {"medians": 0, "soft1": 1, "soft2": 2, "hard": 3}  # mgx_hpss_mode
+HPSS_MAX_KERNEL = 31
+
+
+class HpssParams(ctypes.Structure):
+    """mgx_hpss_params: the two median kernels, the mode and the margins of mgx_hpss_device / mgx_hpss_host."""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("kernel_time", ctypes.c_uint32), ("kernel_freq", ctypes.c_uint32),
+                ("mode", ctypes.c_uint32), ("margin_harmonic", ctypes.c_float), ("margin_percussive", ctypes.c_float)]
+
+
+def _pair(v, what):
+    """A value for both sides, or one for each: (time, frequency) or (harmonic, percussive)."""
+    if isinstance(v, (tuple, list, np.ndarray)):
+        if len(v) != 2:
+            raise TypeError("%s: one value or a pair" % what)
+        return v[0], v[1]
+    return v, v
+
+
+def hpss_params(kernel_size=None, mode=None, margin=None, power=None):
+    """An HpssParams with the library's defaults (mgx_hpss_params_init: kernels 31 x 31, "soft2", margins 1) and the
+    arguments over them. kernel_size: one odd size or (time, frequency); margin: one value or (harmonic, percussive);
+    mode: "medians", "soft1", "soft2", "hard" or the enum's number; power: librosa's name for the mode (1, 2 or
+    inf) instead of it. Numbers out of range are refused by the library, not here."""
+    p = HpssParams()
+    lib().mgx_hpss_params_init(ctypes.byref(p))
+    if kernel_size is not None:
+        kt, kf = _pair(kernel_size, "kernel_size")
+        p.kernel_time, p.kernel_freq = int(kt), int(kf)
+    if power is not None:
+        if mode is not None:
+            raise TypeError("hpss: mode or power, not both")
+        if power not in (1, 2, float("inf")):
+            raise ValueError("hpss power %r: 1, 2 or inf" % (power,))
+        mode = "hard" if power == float("inf") else "soft%d" % int(power)
+    if mode is not None:
+        if isinstance(mode, str):
+            if mode not in HPSS_MODES:
+                raise ValueError("hpss mode %r: one of %s" % (mode, sorted(HPSS_MODES)))
+            mode = HPSS_MODES[mode]
+        p.mode = int(mode)
+    if margin is not None:
+        mh, mp = _pair(margin, "margin")
+        p.margin_harmonic, p.margin_percussive = float(mh), float(mp)
+    return p
+
+
+def hpss_tile():
+    """(rows, columns) of the tile a workgroup of the HPSS kernel owns (mgx_hpss_tile): clips and widths around them
+    take different paths through it."""
+    r, c = ctypes.c_uint32(0), ctypes.c_uint32(0)
+    lib().mgx_hpss_tile(ctypes.byref(r), ctypes.byref(c))
+    return int(r.value), int(c.value)
+
+
 def chroma_params(**params):
     """A ChromaParams with the library's defaults (mgx_chroma_params_init) and `params` over them; numbers out of
     range pass through: the library refuses them with its message."""
@@ -389,6 +445,15 @@ def lib():
         L.mgx_onsets_host.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64,
                                       ctypes.c_void_p, ctypes.c_uint64, freq, ctypes.POINTER(PeakParams), ctypes.c_void_p,
                                       ctypes.c_void_p, ctypes.c_uint64]
+        L.mgx_hpss_params_init.argtypes = [ctypes.POINTER(HpssParams)]
+        L.mgx_hpss_params_init.restype = None
+        L.mgx_hpss_tile.argtypes = [ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32)]
+        L.mgx_hpss_tile.restype = None
+        L.mgx_hpss_device.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint64,
+                                      ctypes.POINTER(HpssParams), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+        L.mgx_hpss_host.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64,
+                                    ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(HpssParams), ctypes.POINTER(ChromaRequest),
+                                    ctypes.POINTER(FluxRequest), ctypes.c_void_p, ctypes.c_void_p]
         L.mgx_chroma_params_init.argtypes = [ctypes.POINTER(ChromaParams)]
         L.mgx_chroma_params_init.restype = None
         L.mgx_chroma_weights.argtypes = [ctypes.c_uint32, ctypes.c_double, ctypes.POINTER(ChromaParams), ctypes.c_void_p]
@@ -1066,6 +1131,89 @@ class Plan:
         res["frame_offsets"] = frame_offsets
         return res
 
+    def hpss(self, samples, starts, frame_offsets=None, kernel_size=None, mode=None, margin=None, power=None, harmonic=False,
+             percussive=False, chroma=None, flux=None):
+        """Host numpy in / numpy out (mgx_hpss_host): the harmonic / percussive split of the amplitude rows of the
+        buffers at `starts` (hpss_params of kernel_size, mode or power, margin), computed on the device from rows that
+        never cross back, and what is asked of the two parts. harmonic, percussive: True for the (F, N/2) float32 rows
+        ("harmonic", "percussive"; rows of no signal are 0). chroma: a dict of Plan.chroma's options (weights, norm,
+        per_frame, summary and the bank's parameters) for the chroma of the harmonic rows: "chroma",
+        "chroma_summary", "weights". flux: a dict of mode ("rectified"), lag (1), per_frame (True), summary (False)
+        for the flux of the percussive rows: "flux" ((F,) float32), "flux_summary" ((S, 4) float64). A summary needs
+        frame_offsets."""
+        samples = np.ascontiguousarray(samples, dtype=np.float32)
+        starts = np.ascontiguousarray(starts, dtype=np.uint64)
+        assert samples.ndim == 1 and starts.ndim == 1
+        S = 0
+        if frame_offsets is not None:
+            frame_offsets = np.ascontiguousarray(frame_offsets, dtype=np.uint64)
+            assert frame_offsets.ndim == 1 and frame_offsets.size >= 1
+            S = frame_offsets.size - 1
+        params = hpss_params(kernel_size, mode, margin, power)
+        F, cols = starts.size, self.n // 2
+        res = {}
+        creq = freq = None
+        if chroma is not None:
+            opts = dict(chroma)
+            weights, norm = opts.pop("weights", None), opts.pop("norm", "max")
+            per_frame, summary = opts.pop("per_frame", True), opts.pop("summary", False)
+            if weights is None:
+                weights = chroma_weights(self.n, self.desc.sample_rate, **opts)
+            elif opts:
+                raise TypeError("chroma parameters are given with weights=None")
+            weights = np.ascontiguousarray(weights, dtype=np.float32)
+            assert weights.ndim == 2 and weights.shape[1] == cols
+            C = weights.shape[0]
+            creq = ChromaRequest()
+            creq.struct_size = ctypes.sizeof(ChromaRequest)
+            creq.num_chroma, creq.norm, creq.weights = C, _chroma_norm(norm), weights.ctypes.data
+            res["weights"] = weights
+            if per_frame:
+                res["chroma"] = np.zeros((F, C), np.float32)
+                creq.per_frame = res["chroma"].ctypes.data
+            if summary:
+                res["chroma_summary"] = np.empty((S, len(STATS), C), np.float64)
+                creq.summary = res["chroma_summary"].ctypes.data
+        if flux is not None:
+            opts = dict(flux)
+            fmode, lag = opts.pop("mode", "rectified"), opts.pop("lag", 1)
+            per_frame, summary = opts.pop("per_frame", True), opts.pop("summary", False)
+            if opts:
+                raise TypeError("flux options: mode, lag, per_frame, summary; got %s" % sorted(opts))
+            if isinstance(fmode, str):
+                if fmode not in FLUX_MODES:
+                    raise ValueError("flux mode %r: one of %s" % (fmode, sorted(FLUX_MODES)))
+                fmode = FLUX_MODES[fmode]
+            freq = FluxRequest()
+            freq.struct_size = ctypes.sizeof(FluxRequest)
+            freq.field, freq.mode, freq.lag = FLUX_FEATURES["amplitudeSpectrum"], int(fmode), int(lag)
+            if per_frame:
+                res["flux"] = np.zeros(F, np.float32)
+                freq.per_frame = res["flux"].ctypes.data
+            if summary:
+                res["flux_summary"] = np.empty((S, len(STATS)), np.float64)
+                freq.summary = res["flux_summary"].ctypes.data
+        if harmonic:
+            res["harmonic"] = np.zeros((F, cols), np.float32)
+        if percussive:
+            res["percussive"] = np.zeros((F, cols), np.float32)
+        check(lib().mgx_hpss_host(self._h, samples.ctypes.data, samples.size, starts.ctypes.data, starts.size,
+                                  None if frame_offsets is None else frame_offsets.ctypes.data, S, ctypes.byref(params),
+                                  None if creq is None else ctypes.byref(creq), None if freq is None else ctypes.byref(freq),
+                                  res["harmonic"].ctypes.data if harmonic else None,
+                                  res["percussive"].ctypes.data if percussive else None))
+        return res
+
+    def hpss_signals(self, signals, hop, **kw):
+        """A list of 1-D host signals in one call (Plan.hpss over signals_frame_starts of their lengths): the dict
+        Plan.hpss returns, with "frame_offsets"."""
+        signals = [np.ascontiguousarray(x, dtype=np.float32).ravel() for x in signals]
+        starts, frame_offsets = signals_frame_starts([x.size for x in signals], self.n, hop)
+        samples = np.concatenate(signals) if signals else np.empty(0, np.float32)
+        res = self.hpss(samples, starts, frame_offsets, **kw)
+        res["frame_offsets"] = frame_offsets
+        return res
+
     def summarize_signals(self, signals, hop, features, per_frame=(), deltas=None, flux=None):
         """A list of 1-D host signals in one call, pooled per signal: returns (summaries, frame_offsets), summaries
         being {name: ndarray (S, 4, width)} of mean, variance, min, max (STATS) over each signal's buffers; with
@@ -1481,6 +1629,46 @@ def chroma_torch(rows, weights, norm="max", stream=None, out=None):
         stream = torch.cuda.current_stream(rows.device).cuda_stream
     chroma_device(rows.data_ptr(), F, cols, weights.data_ptr(), C, _chroma_norm(norm), out.data_ptr(), stream)
     return out
+
+
+def hpss_device(rows_ptr, num_frames, cols, offsets_ptr, num_signals, params, harmonic_ptr, percussive_ptr, stream=None):
+    """mgx_hpss_device on device pointers (async on `stream`); a pointer may be None. params: an HpssParams."""
+    check(lib().mgx_hpss_device(ctypes.c_void_p(rows_ptr or 0), num_frames, cols, ctypes.c_void_p(offsets_ptr or 0), num_signals,
+                                None if params is None else ctypes.byref(params), ctypes.c_void_p(harmonic_ptr or 0),
+                                ctypes.c_void_p(percussive_ptr or 0), ctypes.c_void_p(stream or 0)))
+
+
+def hpss_torch(rows, frame_offsets=None, kernel_size=None, mode=None, margin=None, power=None, harmonic=True, percussive=True,
+               stream=None, out_harmonic=None, out_percussive=None):
+    """The harmonic / percussive split of `rows`, a (F, cols) float32 CUDA tensor, within each signal: the median
+    along time and the median along frequency under the IEEE total order, with reflected ends, and the masks of
+    include/meyda_gpu.h (hpss_params of kernel_size, mode or power, margin; mode "medians": the two medians). Signal
+    s owns rows [frame_offsets[s], frame_offsets[s + 1]) (an int64 CUDA tensor, or anything numpy turns into one;
+    None: one signal, every row). Returns (harmonic, percussive), (F, cols) float32 tensors (the `out_` ones when
+    given, written where a row belongs to a signal; else rows of no signal are 0), None for a part not asked for."""
+    import torch
+    assert rows.is_cuda and rows.is_contiguous() and rows.dim() == 2 and rows.dtype == torch.float32
+    params = hpss_params(kernel_size, mode, margin, power)
+    F, cols = rows.shape
+    S = 0
+    if frame_offsets is not None:
+        if not torch.is_tensor(frame_offsets):
+            frame_offsets = torch.from_numpy(np.ascontiguousarray(frame_offsets, dtype=np.uint64).view(np.int64)).to(rows.device)
+        assert frame_offsets.is_cuda and frame_offsets.dtype == torch.int64 and frame_offsets.is_contiguous()
+        assert frame_offsets.dim() == 1 and frame_offsets.shape[0] >= 1
+        S = frame_offsets.shape[0] - 1
+    outs = []
+    for want, out in ((harmonic, out_harmonic), (percussive, out_percussive)):
+        if out is None and want:
+            out = torch.zeros((F, cols), dtype=torch.float32, device=rows.device)
+        if out is not None:
+            assert out.is_cuda and out.is_contiguous() and out.dtype == torch.float32 and out.shape == (F, cols)
+        outs.append(out)
+    if stream is None:
+        stream = torch.cuda.current_stream(rows.device).cuda_stream
+    hpss_device(rows.data_ptr(), F, cols, None if frame_offsets is None else frame_offsets.data_ptr(), S, params,
+                None if outs[0] is None else outs[0].data_ptr(), None if outs[1] is None else outs[1].data_ptr(), stream)
+    return outs[0], outs[1]
 
 
 def tempogram_window(win_length):

@@ -4730,6 +4730,289 @@ hipError_t launch_beats(const void* env, uint64_t num_frames, bool f64, const ui
   return hipGetLastError();
 }
 
+// ---- HPSS (mgx_hpss_device, mgx_hpss_host): the median along time, the median along frequency and the masks ----
+// A 2-D neighbourhood selection (include/meyda_gpu.h). A workgroup owns a tile of kHpssTileRows rows x
+// kHpssTileCols columns of the array. The rows of a tile are cut into segments of one signal each (the row's signal
+// is looked up as delta_kernel looks it up, once per row), and a segment is staged in LDS as order keys with a halo
+// of ht rows and hf columns whose reflected indices are resolved by the load: a window is then 2 h + 1 consecutive
+// LDS rows or columns, whatever the clip's length, and never holds another clip's row. The row stride is odd, so the
+// walk down a column (lanes on consecutive columns) and the walk along a row (lanes on consecutive rows) both touch
+// 32 distinct banks per half wave.
+// A thread slides a sorted window of SLOTS keys held in registers (HpssWindow: every index is a compile-time
+// constant): one branch-free sweep of a compare, a select, a minimum and a maximum per slot deletes the key that
+// leaves and inserts the key that enters; a thread's first window is sorted by a merge-exchange network. A kernel K
+// below SLOTS pads the window with (SLOTS - K) / 2 keys 0 and as
+// many keys 0xFFFFFFFF, which are at or beyond every key: the middle slot is then the median of the K real keys, so
+// one instance serves every odd K up to its SLOTS. Both medians go to LDS as float bits, and a last pass over the
+// tile's elements in row-major order forms the masks in float64 and stores both outputs coalesced.
+namespace {
+
+constexpr uint32_t kHpssTileRows = MGX_HPSS_TILE_ROWS, kHpssTileCols = MGX_HPSS_TILE_COLS;
+constexpr uint32_t kHpssAhead = 4;  // rows a wave stages at a time, their loads in flight together
+static_assert(kHpssTileRows == 64 && kHpssTileCols == 64, "hpss_kernel: 256 threads as 64 x 4 in both passes");
+
+struct HpssArgs {
+  const float* rows;
+  uint32_t* harmonic;    // either may be null
+  uint32_t* percussive;
+  const uint64_t* table;  // null: one signal, rows [0, num_frames)
+  uint64_t num_signals, num_frames;
+  uint32_t row_tiles;  // tiles along the rows
+  uint32_t cols, kt, kf, mode;
+  float mh, mp;
+};
+
+__device__ __forceinline__ uint32_t hpss_key(uint32_t bits) { return (bits & 0x80000000u) ? ~bits : bits | 0x80000000u; }
+__device__ __forceinline__ uint32_t hpss_unkey(uint32_t key) { return (key & 0x80000000u) ? key ^ 0x80000000u : ~key; }
+
+// r(u, m) of the definition, the half-sample symmetric extension repeated as often as u needs, for the indices a
+// tile asks for: -16 <= u < m + 192 (a halo of at most 15 before the first element, a tile and a halo after the last;
+// m >= 1). A long axis reflects once at most; a short one takes u mod 2m in 32 bits.
+__device__ __forceinline__ uint64_t hpss_reflect(int64_t u, uint64_t m) {
+  if (m >= 256) return u < 0 ? (uint64_t)(-1 - u) : (uint64_t)u >= m ? 2 * m - 1 - (uint64_t)u : (uint64_t)u;
+  const uint32_t p = 2 * (uint32_t)m;
+  const uint32_t q = (uint32_t)((int32_t)u + (int32_t)(16 * p)) % p;  // (16 p >= 32: the sum is not negative)
+  return q < (uint32_t)m ? q : p - 1 - q;
+}
+
+// the median of three unsigned values (the compiler forms v_med3_u32 only around constants)
+__device__ __forceinline__ uint32_t hpss_med3(uint32_t a, uint32_t b, uint32_t c) {
+  uint32_t r;
+  asm("v_med3_u32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
+  return r;
+}
+
+template <int SLOTS>
+struct HpssWindow {
+  uint32_t w[SLOTS];
+  // `in` enters, then one instance of `out` (which the window holds) leaves. u, SLOTS + 1 keys, is the window with
+  // `in`: u[i] is the median of w[i - 1] <= w[i] and `in`. Without `out` slot i is u[i] where u[i] < out and u[i + 1]
+  // from there on, which is the one of the two that clamping `out` between them does not give: out <= u[i] clamps to
+  // u[i], and an `out` above u[i] is at or above u[i + 1], being one of u. No comparison is kept in a scalar register
+  // pair (31 of them at once spilled), and the sweep is two v_med3_u32 and an exclusive or of three per slot.
+  __device__ __forceinline__ void slide(uint32_t out, uint32_t in) {
+    uint32_t u[SLOTS + 1];
+    u[0] = w[0] < in ? w[0] : in;
+#pragma unroll
+    for (int i = 1; i < SLOTS; ++i) u[i] = hpss_med3(w[i - 1], w[i], in);
+    u[SLOTS] = w[SLOTS - 1] > in ? w[SLOTS - 1] : in;
+#pragma unroll
+    for (int i = 0; i < SLOTS; ++i) w[i] = u[i] ^ u[i + 1] ^ hpss_med3(u[i], u[i + 1], out);
+  }
+  // The first window: the K keys `step` words apart from src on, between the padding, sorted by Batcher's merge
+  // exchange (186 compare-exchanges of a minimum and a maximum at 31 slots, 59 at 15, every index a constant: about
+  // three sweeps' work where sliding K - 1 keys in, one by one, is K - 1 sweeps).
+  __device__ __forceinline__ void load(const uint32_t* src, uint32_t step, uint32_t K) {
+    uint32_t pad = ((uint32_t)SLOTS - K) / 2;
+    // (pad in a vector register, set here: as a uniform value its 2 SLOTS comparisons are hoisted out of the segment
+    // loop into as many scalar register pairs, which spill)
+    asm volatile("" : "+v"(pad));
+#pragma unroll
+    for (uint32_t i = 0; i < SLOTS; ++i) {
+      const uint32_t r = i - pad;  // (wraps below the padding: not below K then)
+      const uint32_t key = src[(r < K ? r : 0u) * step];
+      w[i] = r < K ? key : i < pad ? 0u : 0xFFFFFFFFu;
+    }
+#pragma unroll
+    for (int p = 1; p < SLOTS; p *= 2) {
+#pragma unroll
+      for (int k = p; k >= 1; k /= 2) {
+#pragma unroll
+        for (int j = k % p; j <= SLOTS - 1 - k; j += 2 * k) {
+#pragma unroll
+          for (int i = 0; i <= (k - 1 < SLOTS - j - k - 1 ? k - 1 : SLOTS - j - k - 1); ++i) {
+            if ((i + j) / (2 * p) == (i + j + k) / (2 * p)) {
+              const uint32_t a = w[i + j], b = w[i + j + k];
+              w[i + j] = a < b ? a : b;
+              w[i + j + k] = a < b ? b : a;
+            }
+          }
+        }
+      }
+    }
+  }
+  __device__ __forceinline__ uint32_t median() const { return w[SLOTS / 2]; }
+};
+
+// The medians of `count` consecutive windows of K keys, `step` words apart in LDS from `src` on; window j starts
+// at src + j step. dst: where median j goes, dstep words apart.
+template <int SLOTS>
+__device__ __forceinline__ void hpss_run(const uint32_t* src, uint32_t step, uint32_t K, uint32_t count, uint32_t* dst, uint32_t dstep) {
+  if (count == 0) return;
+  HpssWindow<SLOTS> win;
+  win.load(src, step, K);
+  dst[0] = hpss_unkey(win.median());
+  for (uint32_t j = 1; j < count; ++j) {
+    win.slide(src[(j - 1) * step], src[(j - 1 + K) * step]);
+    dst[j * dstep] = hpss_unkey(win.median());
+  }
+}
+
+// One output of the definition's masks from the element x and the two medians, A the output's own
+__device__ __forceinline__ uint32_t hpss_mask(uint32_t mode, float x, float own, float other, float margin, bool unit) {
+  const double A = __builtin_fabs((double)own);
+  const double R = __builtin_fabs((double)other) * (double)margin;
+  if (mode == MGX_HPSS_HARD) return A > R ? __float_as_uint(x) : 0u;
+  const double hp = mode == MGX_HPSS_SOFT2 ? A * A : A, rp = mode == MGX_HPSS_SOFT2 ? R * R : R;
+  const double den = hp + rp;
+  const double mask = den == 0.0 ? (unit ? 0.5 : 0.0) : hp / den;
+  const double y = (double)x * mask;
+  return __float_as_uint((float)y);
+}
+
+template <int ST, int SF>
+__global__ __launch_bounds__(256) void hpss_kernel(HpssArgs g) {
+  constexpr uint32_t TR = kHpssTileRows, TC = kHpssTileCols;
+  constexpr uint32_t LR = TR + ST - 1, LS = (TC + SF - 1) | 1u, MS = TC + 1;
+  __shared__ uint32_t keys[LR * LS];
+  __shared__ uint32_t med_h[TR * MS], med_p[TR * MS];
+  __shared__ uint64_t sig_a[TR], sig_b[TR];
+  const uint32_t tid = threadIdx.x, lane = tid & 63u, quarter = tid >> 6;
+  const uint32_t ht = g.kt / 2, hf = g.kf / 2;
+  const uint64_t cols = g.cols, F = g.num_frames;
+  // a workgroup per tile: the grid's x is the tile along the columns, y and z together the tile along the rows
+  const uint64_t c0 = (uint64_t)blockIdx.x * TC;
+  const uint32_t rt = blockIdx.z * gridDim.y + blockIdx.y;
+  if (rt < g.row_tiles) {
+    const uint64_t r0 = (uint64_t)rt * TR;
+    const uint32_t nr = F - r0 < TR ? (uint32_t)(F - r0) : TR;
+    const uint32_t wc = cols - c0 < TC ? (uint32_t)(cols - c0) : TC;
+    if (tid < nr) {
+      // the row's signal, as delta_kernel finds it: the last s with table[s] <= t; [a, b) empty when it has none
+      const uint64_t t = r0 + tid;
+      uint64_t a = 0, b = F;
+      if (g.table) {
+        uint64_t lo = 0, hi = g.num_signals + 1;
+        while (lo < hi) {
+          const uint64_t mid = lo + (hi - lo) / 2;
+          if (g.table[mid] <= t) lo = mid + 1;
+          else hi = mid;
+        }
+        a = b = 0;
+        if (lo > 0 && lo <= g.num_signals) {
+          a = g.table[lo - 1];
+          b = g.table[lo];
+          a = a < F ? a : F;
+          b = b < F ? b : F;
+        }
+      }
+      sig_a[tid] = a;
+      sig_b[tid] = b;
+    }
+    // the source columns of the lane's LDS columns lane and lane + 64: the same for every row of the tile
+    const uint32_t lcols = wc + 2 * hf;  // <= TC + SF - 1 < 128
+    const uint64_t sc0 = hpss_reflect((int64_t)c0 + (int64_t)lane - (int64_t)hf, cols);
+    const uint64_t sc1 = hpss_reflect((int64_t)c0 + (int64_t)lane + 64 - (int64_t)hf, cols);
+    __syncthreads();
+    uint32_t i = 0;
+    while (i < nr) {  // (every thread walks the same segments: they are read from LDS)
+      const uint64_t a = sig_a[i], b = sig_b[i];
+      uint32_t e = i + 1;
+      while (e < nr && sig_a[e] == a && sig_b[e] == b) ++e;
+      const uint32_t sr = e - i;  // the segment: rows [r0 + i, r0 + e) of the signal [a, b)
+      const uint64_t t0 = r0 + i;
+      if (b > a && t0 >= a && t0 + sr <= b) {  // (a <= t < b <= num_frames for every row from here on)
+        const uint64_t n = b - a;
+        // stage: LDS row lr is the signal's row r(t0 - a + lr - ht, n), LDS column lc the row's column r(c0 + lc - hf, cols)
+        const uint32_t lrows = sr + 2 * ht;
+        // (a wave takes every fourth LDS row, kHpssAhead of them at a time: their loads are all issued before the first
+        // is used -- one after another, each behind its row's reflection, the 31 x 31 launch took a quarter longer)
+        for (uint32_t lr0 = quarter; lr0 < lrows; lr0 += 4 * kHpssAhead) {
+          uint32_t v0[kHpssAhead], v1[kHpssAhead];
+#pragma unroll
+          for (uint32_t u = 0; u < kHpssAhead; ++u) {
+            const uint32_t lr = lr0 + 4 * u;
+            v0[u] = v1[u] = 0;
+            if (lr < lrows) {
+              const uint64_t srow = a + hpss_reflect((int64_t)(t0 - a) + (int64_t)lr - (int64_t)ht, n);
+              const float* const x = g.rows + srow * cols;
+              if (lane < lcols) v0[u] = __float_as_uint(x[sc0]);
+              if (lane + 64 < lcols) v1[u] = __float_as_uint(x[sc1]);
+            }
+          }
+#pragma unroll
+          for (uint32_t u = 0; u < kHpssAhead; ++u) {
+            const uint32_t lr = lr0 + 4 * u;
+            if (lr < lrows) {
+              if (lane < lcols) keys[lr * LS + lane] = hpss_key(v0[u]);
+              if (lane + 64 < lcols) keys[lr * LS + lane + 64] = hpss_key(v1[u]);
+            }
+          }
+        }
+        __syncthreads();
+        // the harmonic median: the lane's column, the quarter's rows; the window of LDS rows p .. p + 2 ht
+        {
+          const uint32_t per = (sr + 3) / 4, p0 = quarter * per;
+          const uint32_t cnt = lane < wc && p0 < sr ? (sr - p0 < per ? sr - p0 : per) : 0;
+          hpss_run<ST>(keys + p0 * LS + hf + lane, LS, g.kt, cnt, med_h + p0 * MS + lane, MS);
+        }
+        // the percussive median: the lane's row, the quarter's columns; the window of LDS columns p .. p + 2 hf
+        {
+          const uint32_t per = (wc + 3) / 4, p0 = quarter * per;
+          const uint32_t cnt = lane < sr && p0 < wc ? (wc - p0 < per ? wc - p0 : per) : 0;
+          hpss_run<SF>(keys + (lane + ht) * LS + p0, 1, g.kf, cnt, med_p + lane * MS + p0, 1);
+        }
+        __syncthreads();
+        for (uint32_t row = quarter; row < sr; row += 4) {
+          if (lane < wc) {
+            const uint32_t hb = med_h[row * MS + lane], pb = med_p[row * MS + lane];
+            const uint64_t at = (t0 + row) * cols + c0 + lane;
+            if (g.mode == MGX_HPSS_MEDIANS) {
+              if (g.harmonic) g.harmonic[at] = hb;
+              if (g.percussive) g.percussive[at] = pb;
+            } else {
+              const float x = __uint_as_float(hpss_unkey(keys[(row + ht) * LS + hf + lane]));
+              const float H = __uint_as_float(hb), P = __uint_as_float(pb);
+              const bool unit = g.mh == 1.0f && g.mp == 1.0f;
+              if (g.harmonic) g.harmonic[at] = hpss_mask(g.mode, x, H, P, g.mh, unit);
+              if (g.percussive) g.percussive[at] = hpss_mask(g.mode, x, P, H, g.mp, unit);
+            }
+          }
+        }
+      }
+      __syncthreads();
+      i = e;
+    }
+  }
+}
+
+}  // namespace
+
+hipError_t launch_hpss(const float* rows, uint64_t num_frames, uint32_t cols, const uint64_t* table, uint64_t num_signals,
+                       const mgx_hpss_params& p, float* harmonic, float* percussive, hipStream_t stream) {
+  if (num_frames == 0) return hipSuccess;
+  if (cols == 0 || !(p.kernel_time & 1) || !(p.kernel_freq & 1) || p.kernel_time > MGX_HPSS_MAX_KERNEL ||
+      p.kernel_freq > MGX_HPSS_MAX_KERNEL || p.mode >= MGX_NUM_HPSS_MODES || !rows || (!harmonic && !percussive))
+    return hipErrorInvalidValue;
+  HpssArgs g{};
+  g.rows = rows;
+  g.harmonic = reinterpret_cast<uint32_t*>(harmonic);
+  g.percussive = reinterpret_cast<uint32_t*>(percussive);
+  g.table = table;
+  g.num_signals = num_signals;
+  g.num_frames = num_frames;
+  const uint64_t row_tiles = (num_frames + kHpssTileRows - 1) / kHpssTileRows;
+  if (row_tiles > 0xFFFFFFFFull) return hipErrorInvalidValue;
+  g.row_tiles = (uint32_t)row_tiles;
+  const uint32_t col_tiles = (uint32_t)(((uint64_t)cols + kHpssTileCols - 1) / kHpssTileCols);
+  g.cols = cols;
+  g.kt = p.kernel_time;
+  g.kf = p.kernel_freq;
+  g.mode = p.mode;
+  g.mh = p.margin_harmonic;
+  g.mp = p.margin_percussive;
+  const uint32_t gy = g.row_tiles < 32768 ? g.row_tiles : 32768, gz = (g.row_tiles + gy - 1) / gy;
+  if (gz > 65535) return hipErrorInvalidValue;  // (2^37 rows)
+  const dim3 grid(col_tiles, gy, gz);
+  // the smallest instance whose windows hold the kernels (15 or 31 slots each)
+  const bool st = g.kt > 15, sf = g.kf > 15;
+  if (st && sf) hipLaunchKernelGGL((hpss_kernel<31, 31>), grid, dim3(256), 0, stream, g);
+  else if (st) hipLaunchKernelGGL((hpss_kernel<31, 15>), grid, dim3(256), 0, stream, g);
+  else if (sf) hipLaunchKernelGGL((hpss_kernel<15, 31>), grid, dim3(256), 0, stream, g);
+  else hipLaunchKernelGGL((hpss_kernel<15, 15>), grid, dim3(256), 0, stream, g);
+  return hipGetLastError();
+}
+
 }  // namespace mgx
 
 #if MGX_WAVE_TIMES

@@ -282,6 +282,12 @@ uint64_t beats_workspace_bytes(uint64_t num_frames, uint64_t num_signals, BeatLa
 hipError_t launch_beats(const void* env, uint64_t num_frames, bool f64, const uint64_t* table, uint64_t num_signals,
                         const uint32_t* period, uint32_t max_period, uint32_t trim, const float* gauss, const double* penalty,
                         double* local_score, double* cum_score, const mgx_peak_outputs& o, void* workspace, hipStream_t stream);
+// HPSS (mgx_hpss_device, mgx_hpss_host; kernels.hip hpss_kernel): the harmonic and percussive parts of rows (num_frames
+// x cols float32) under p (checked by the caller), each median within the row's signal, the table as launch_delta reads
+// it (null: one signal, every row). harmonic, percussive: the rows' shape, either may be null. Rows that belong to no
+// signal are not written. One launch, asynchronous.
+hipError_t launch_hpss(const float* rows, uint64_t num_frames, uint32_t cols, const uint64_t* table, uint64_t num_signals,
+                       const mgx_hpss_params& p, float* harmonic, float* percussive, hipStream_t stream);
 size_t extract_lds_bytes(int n, int ncoef, int nfilt, bool chain);
 size_t lds_image_bytes(int n, int ncoef, int nfilt);  // DevTables::lds_image, a multiple of 16
 hipError_t launch_lds_image(int n, int precision, int mode, const KernelArgs& a, void* image, hipStream_t stream);

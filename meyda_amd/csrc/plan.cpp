@@ -506,6 +506,9 @@ struct mgx_plan {
   // allocation, grown when a call needs more)
   unsigned char* s_chroma = nullptr;
   size_t s_chroma_bytes = 0;
+  // mgx_hpss_host: the call's amplitude rows, the two parts and what the requests behind them need
+  unsigned char* s_hpss = nullptr;
+  size_t s_hpss_bytes = 0;
   // mgx_tempo_host: the window, the prior, the workspace of mgx_tempo_device and the lags (one allocation, grown
   // when a call needs more)
   unsigned char* s_tempo = nullptr;
@@ -863,6 +866,7 @@ int mgx_plan_destroy(mgx_plan* p) {
   if (p->s_delta) (void)hipFree(p->s_delta);
   if (p->s_flux) (void)hipFree(p->s_flux);
   if (p->s_chroma) (void)hipFree(p->s_chroma);
+  if (p->s_hpss) (void)hipFree(p->s_hpss);
   if (p->s_tempo) (void)hipFree(p->s_tempo);
   if (p->s_copy) (void)hipStreamDestroy(p->s_copy);
   if (p->s_comp) (void)hipStreamDestroy(p->s_comp);
@@ -2975,6 +2979,216 @@ int mgx_chroma_host(mgx_plan* p, const float* samples, uint64_t num_samples, con
   const hipError_t es = hipStreamSynchronize(p->s_comp);
   if (e == hipSuccess) e = es;
   return e == hipSuccess ? MGX_OK : hip_fail(e, "chroma and summary kernels and copies");
+}
+
+void mgx_hpss_params_init(mgx_hpss_params* h) {
+  if (!h) return;
+  memset(h, 0, sizeof *h);
+  h->struct_size = sizeof *h;
+  h->kernel_time = MGX_HPSS_MAX_KERNEL;
+  h->kernel_freq = MGX_HPSS_MAX_KERNEL;
+  h->mode = MGX_HPSS_SOFT2;
+  h->margin_harmonic = 1.0f;
+  h->margin_percussive = 1.0f;
+}
+
+void mgx_hpss_tile(uint32_t* tile_rows, uint32_t* tile_cols) {
+  if (tile_rows) *tile_rows = MGX_HPSS_TILE_ROWS;
+  if (tile_cols) *tile_cols = MGX_HPSS_TILE_COLS;
+}
+
+static int check_hpss_params(const mgx_hpss_params* hp) {
+  if (!hp) return fail(MGX_E_INVALID_ARGUMENT, "params is NULL");
+  if (hp->struct_size != sizeof(mgx_hpss_params))
+    return fail(MGX_E_INVALID_ARGUMENT, "mgx_hpss_params.struct_size is %u, expected %zu", hp->struct_size, sizeof(mgx_hpss_params));
+  const uint32_t k[2] = {hp->kernel_time, hp->kernel_freq};
+  for (int i = 0; i < 2; ++i)
+    if (!(k[i] & 1u) || k[i] > MGX_HPSS_MAX_KERNEL)
+      return fail(MGX_E_INVALID_ARGUMENT, "mgx_hpss_params.kernel_%s is %u, expected an odd value in 1..%d", i ? "freq" : "time", k[i],
+                  MGX_HPSS_MAX_KERNEL);
+  if (hp->mode >= MGX_NUM_HPSS_MODES)
+    return fail(MGX_E_INVALID_ARGUMENT, "mgx_hpss_params.mode is %u, expected 0..%d", hp->mode, MGX_NUM_HPSS_MODES - 1);
+  const float m[2] = {hp->margin_harmonic, hp->margin_percussive};
+  for (int i = 0; i < 2; ++i)
+    if (!std::isfinite(m[i]) || !(m[i] >= 1.0f))
+      return fail(MGX_E_INVALID_ARGUMENT, "mgx_hpss_params.margin_%s is %g, expected a finite value >= 1", i ? "percussive" : "harmonic",
+                  (double)m[i]);
+  return MGX_OK;
+}
+
+int mgx_hpss_device(const float* rows, uint64_t num_frames, uint32_t cols, const uint64_t* frame_offsets, uint64_t num_signals,
+                    const mgx_hpss_params* params, float* harmonic, float* percussive, void* stream) {
+  const int rc = check_hpss_params(params);
+  if (rc) return rc;
+  if (cols == 0) return fail(MGX_E_INVALID_ARGUMENT, "cols is 0");
+  if (!harmonic && !percussive) return fail(MGX_E_INVALID_ARGUMENT, "harmonic and percussive are both NULL");
+  if (harmonic == percussive) return fail(MGX_E_INVALID_ARGUMENT, "harmonic and percussive are the same array");
+  if (rows && (harmonic == rows || percussive == rows)) return fail(MGX_E_INVALID_ARGUMENT, "an output is the rows' own array");
+  if (num_signals > 0 && !frame_offsets) return fail(MGX_E_INVALID_ARGUMENT, "frame_offsets is NULL");
+  if (num_frames == 0) return MGX_OK;
+  if (!rows) return fail(MGX_E_INVALID_ARGUMENT, "rows is NULL");
+  // (frame_offsets with num_signals = 0: a table of one entry, no signal, nothing written)
+  const hipError_t e = mgx::launch_hpss(rows, num_frames, cols, frame_offsets, num_signals, *params, harmonic, percussive, (hipStream_t)stream);
+  return e == hipSuccess ? MGX_OK : hip_fail(e, "hpss kernel launch");
+}
+
+int mgx_hpss_host(mgx_plan* p, const float* samples, uint64_t num_samples, const uint64_t* starts, uint64_t nframes,
+                  const uint64_t* frame_offsets, uint64_t nsignals, const mgx_hpss_params* params, const mgx_chroma_request* chroma,
+                  const mgx_flux_request* flux, float* harmonic, float* percussive) {
+  int rc = check_hpss_params(params);
+  if (rc) return rc;
+  if (!chroma && !flux && !harmonic && !percussive)
+    return fail(MGX_E_INVALID_ARGUMENT, "harmonic_chroma, percussive_flux, harmonic and percussive are all NULL");
+  if (harmonic && harmonic == percussive) return fail(MGX_E_INVALID_ARGUMENT, "harmonic and percussive are the same array");
+  if (chroma) {
+    if (chroma->struct_size != sizeof(mgx_chroma_request))
+      return fail(MGX_E_INVALID_ARGUMENT, "mgx_chroma_request.struct_size is %u, expected %zu", chroma->struct_size, sizeof(mgx_chroma_request));
+    if (chroma->num_chroma < 1 || chroma->num_chroma > MGX_CHROMA_MAX_BINS)
+      return fail(MGX_E_INVALID_ARGUMENT, "mgx_chroma_request.num_chroma is %u, expected 1..%d", chroma->num_chroma, MGX_CHROMA_MAX_BINS);
+    if (chroma->norm >= MGX_NUM_CHROMA_NORMS)
+      return fail(MGX_E_INVALID_ARGUMENT, "mgx_chroma_request.norm is %u, expected 0..%d", chroma->norm, MGX_NUM_CHROMA_NORMS - 1);
+    if (!chroma->weights) return fail(MGX_E_INVALID_ARGUMENT, "mgx_chroma_request.weights is NULL");
+    if (!chroma->per_frame && !chroma->summary)
+      return fail(MGX_E_INVALID_ARGUMENT, "mgx_chroma_request.per_frame and .summary are both NULL");
+    if (chroma->summary && nsignals == 0) return fail(MGX_E_INVALID_ARGUMENT, "mgx_chroma_request.summary is set with num_signals = 0");
+  }
+  FluxReq fq;
+  if (flux) {
+    if ((rc = flux_request(nullptr, flux, 1, nsignals, &fq))) return rc;
+    if (flux->field != MGX_AMPLITUDE_SPECTRUM)
+      return fail(MGX_E_UNSUPPORTED, "mgx_flux_request.field is %u: the percussive rows are amplitude rows (MGX_AMPLITUDE_SPECTRUM)", flux->field);
+  }
+  if (!p) return fail(MGX_E_INVALID_ARGUMENT, "plan is NULL");
+  if ((rc = summary_inputs(p, samples, num_samples, starts, nframes, frame_offsets, nsignals))) return rc;
+  // (the host sees both tables: they are checked here, before any copy, as mgx_chroma_host checks them)
+  const uint64_t n = (uint64_t)p->n;
+  for (uint64_t f = 0; f < nframes; ++f)
+    if (starts[f] > num_samples - n)
+      return fail(MGX_E_INVALID_ARGUMENT, "starts[%llu] = %llu: a buffer of %d leaves the %llu samples", (unsigned long long)f,
+                  (unsigned long long)starts[f], p->n, (unsigned long long)num_samples);
+  for (uint64_t s = 0; s < nsignals; ++s)
+    if (frame_offsets[s + 1] < frame_offsets[s])
+      return fail(MGX_E_INVALID_ARGUMENT, "frame_offsets[%llu] = %llu is below frame_offsets[%llu] = %llu", (unsigned long long)(s + 1),
+                  (unsigned long long)frame_offsets[s + 1], (unsigned long long)s, (unsigned long long)frame_offsets[s]);
+  if (nsignals > 0 && frame_offsets[nsignals] > nframes)
+    return fail(MGX_E_INVALID_ARGUMENT, "frame_offsets[%llu] = %llu is above the %llu buffers", (unsigned long long)nsignals,
+                (unsigned long long)frame_offsets[nsignals], (unsigned long long)nframes);
+  const mgx_outputs none{};
+  mgx::Outputs x;  // (no per-frame field crosses back)
+  if ((rc = make_outputs(p, &none, nullptr, &x))) return rc;
+  resident_stop(p);
+  const uint32_t cols = (uint32_t)(n / 2), C = chroma ? chroma->num_chroma : 0;
+  const uint64_t cstats = nsignals * MGX_NUM_STATS * C, fstats = nsignals * MGX_NUM_STATS;
+  if (nframes == 0) {
+    // no buffers: every signal is empty, NaN in all four (nothing for the device to do)
+    if (chroma && chroma->summary) std::fill_n(chroma->summary, cstats, std::nan(""));
+    if (flux && flux->summary) std::fill_n(flux->summary, fstats, std::nan(""));
+    return MGX_OK;
+  }
+  // the rows the operator writes and the copies back cover: the signals' own, or every row without a table
+  const bool has_table = frame_offsets != nullptr;
+  const uint64_t w0 = has_table ? (nsignals ? std::min(frame_offsets[0], nframes) : 0) : 0;
+  const uint64_t w1 = has_table ? (nsignals ? std::min(frame_offsets[nsignals], nframes) : 0) : nframes;
+  const bool need_h = harmonic || chroma, need_p = percussive || flux;
+  const bool cpool = chroma && chroma->summary, fpool = flux && flux->summary;
+  const uint64_t parts = nframes / mgx::kSummaryBlock + nsignals + 1;
+  uint64_t total = 0;
+  auto take = [&total](uint64_t bytes) {
+    const uint64_t at = total;
+    total += (bytes + 255) / 256 * 256;
+    return at;
+  };
+  const uint64_t row_bytes = nframes * cols * sizeof(float);
+  const uint64_t at_amp = take(row_bytes), at_h = need_h ? take(row_bytes) : 0, at_p = need_p ? take(row_bytes) : 0;
+  const uint64_t at_table = has_table ? take((nsignals + 1) * sizeof(uint64_t)) : 0;
+  const uint64_t at_bank = chroma ? take((uint64_t)C * cols * sizeof(float)) : 0, at_crows = chroma ? take(nframes * C * sizeof(float)) : 0;
+  const uint64_t at_cshift = cpool ? take(nsignals * C * sizeof(double)) : 0;
+  const uint64_t at_cpart = cpool ? take(parts * mgx::kSummaryWords * C * sizeof(double)) : 0, at_cres = cpool ? take(cstats * sizeof(double)) : 0;
+  const uint64_t at_fcol = flux ? take(nframes * sizeof(float)) : 0, at_fshift = fpool ? take(nsignals * sizeof(double)) : 0;
+  const uint64_t at_fpart = fpool ? take(parts * mgx::kSummaryWords * sizeof(double)) : 0, at_fres = fpool ? take(fstats * sizeof(double)) : 0;
+  hipError_t e = hipSetDevice(p->d.device);
+  if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
+  if ((rc = ensure_host_staging(p, 1, mgx::kOutLayoutSlack))) return rc;
+  if (p->s_hpss_bytes < total) {
+    if (p->s_hpss) (void)hipFree(p->s_hpss);
+    p->s_hpss = nullptr;
+    p->s_hpss_bytes = 0;
+    e = hipMalloc(reinterpret_cast<void**>(&p->s_hpss), total);
+    if (e != hipSuccess) {
+      p->s_hpss = nullptr;
+      return hip_fail(e, "hipMalloc(hpss rows)");  // (MGX_E_OUT_OF_MEMORY when the device has no room)
+    }
+    p->s_hpss_bytes = total;
+  }
+  unsigned char* const buf = p->s_hpss;
+  float* const amp = reinterpret_cast<float*>(buf + at_amp);
+  float* const dh = need_h ? reinterpret_cast<float*>(buf + at_h) : nullptr;
+  float* const dp = need_p ? reinterpret_cast<float*>(buf + at_p) : nullptr;
+  const uint64_t* const table = has_table ? reinterpret_cast<const uint64_t*>(buf + at_table) : nullptr;
+  if (has_table) e = hipMemcpyAsync(buf + at_table, frame_offsets, (nsignals + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, p->s_comp);
+  if (e == hipSuccess && chroma)
+    e = hipMemcpyAsync(buf + at_bank, chroma->weights, (uint64_t)C * cols * sizeof(float), hipMemcpyHostToDevice, p->s_comp);
+  if (e != hipSuccess) {
+    (void)hipStreamSynchronize(p->s_comp);
+    return hip_fail(e, "hipMemcpyAsync(frame_offsets, weights)");
+  }
+  ChunkHook hook;
+  hook.pooled = MGX_OUT_AMPLITUDE_SPECTRUM;
+  hook.after = [&](uint64_t f0, uint64_t cnt, const mgx::Outputs& d) {
+    // the chunk's amplitude rows into the call's array before the slot is reused
+    const hipError_t ke =
+        hipMemcpyAsync(amp + f0 * cols, d.amplitude_spectrum, cnt * cols * sizeof(float), hipMemcpyDeviceToDevice, p->s_comp);
+    return ke == hipSuccess ? (int)MGX_OK : hip_fail(ke, "hipMemcpyAsync(amplitude rows)");
+  };
+  if ((rc = gather_host_chunked(p, samples, starts, nframes, &x, &hook))) return rc;
+  hipStream_t st = p->s_comp;
+  e = mgx::launch_hpss(amp, nframes, cols, table, nsignals, *params, dh, dp, st);
+  const uint64_t wn = w1 > w0 ? w1 - w0 : 0;
+  if (e == hipSuccess && harmonic && wn)
+    e = hipMemcpyAsync(harmonic + w0 * cols, dh + w0 * cols, wn * cols * sizeof(float), hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess && percussive && wn)
+    e = hipMemcpyAsync(percussive + w0 * cols, dp + w0 * cols, wn * cols * sizeof(float), hipMemcpyDeviceToHost, st);
+  auto pool = [&](const float* src, uint32_t width, uint64_t at_shift, uint64_t at_part, uint64_t at_res, double* dst, uint64_t count) {
+    mgx::SummaryArgs a{};
+    a.nfields = 1;
+    a.cols = width;
+    a.f[0].src = src;
+    a.f[0].dst = reinterpret_cast<double*>(buf + at_res);
+    a.f[0].width = width;
+    a.table = table;
+    a.num_signals = nsignals;
+    a.num_frames = nframes;
+    a.rows = nframes;
+    a.nslots = nframes / mgx::kSummaryBlock + nsignals;
+    a.shift = reinterpret_cast<double*>(buf + at_shift);
+    a.part = reinterpret_cast<double*>(buf + at_part);
+    hipError_t pe = mgx::launch_summary_partial(a, st);
+    if (pe == hipSuccess) pe = mgx::launch_summary_final(a, st);
+    if (pe == hipSuccess) pe = hipMemcpyAsync(dst, a.f[0].dst, count * sizeof(double), hipMemcpyDeviceToHost, st);
+    return pe;
+  };
+  if (e == hipSuccess && chroma && wn) {
+    // chroma of the harmonic rows of the signals (a row of no signal holds nothing the operator wrote)
+    float* const crows = reinterpret_cast<float*>(buf + at_crows);
+    e = mgx::launch_chroma(dh + w0 * cols, wn, cols, reinterpret_cast<const float*>(buf + at_bank), C, chroma->norm, crows + w0 * C, st);
+    if (e == hipSuccess && chroma->per_frame)
+      e = hipMemcpyAsync(chroma->per_frame + w0 * C, crows + w0 * C, wn * C * sizeof(float), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && cpool) e = pool(crows, C, at_cshift, at_cpart, at_cres, chroma->summary, cstats);
+  } else if (e == hipSuccess && cpool) {
+    std::fill_n(chroma->summary, cstats, std::nan(""));
+  }
+  if (e == hipSuccess && flux && wn) {
+    float* const fcol = reinterpret_cast<float*>(buf + at_fcol);
+    e = mgx::launch_flux(dp, nullptr, fcol, 0, nframes, nframes, cols, false, table, nsignals, flux->mode, flux->lag, st);
+    if (e == hipSuccess && flux->per_frame)
+      e = hipMemcpyAsync(flux->per_frame + w0, fcol + w0, wn * sizeof(float), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && fpool) e = pool(fcol, 1, at_fshift, at_fpart, at_fres, flux->summary, fstats);
+  } else if (e == hipSuccess && fpool) {
+    std::fill_n(flux->summary, fstats, std::nan(""));
+  }
+  const hipError_t es = hipStreamSynchronize(st);
+  if (e == hipSuccess) e = es;
+  return e == hipSuccess ? MGX_OK : hip_fail(e, "hpss, chroma, flux and summary kernels and copies");
 }
 
 void mgx_tempo_params_init(mgx_tempo_params* t) {

@@ -40,6 +40,14 @@
 //                                   frameOffsets[, summaries]}
 //   Meyda.chromaFilterBank(bufferSize, sampleRate[, options])
 //                                   the numChroma x bufferSize / 2 chroma filter bank (host only)
+//   getSignalHpss(signals, hopSize, {kernelSize | [kernelTime, kernelFreq], power: 1 | 2 | Infinity,
+//                                    margin | [marginHarmonic, marginPercussive], chroma: {getSignalChroma's options},
+//                                    flux: {mode, lag, summary}, harmonic, percussive}) / getSignalHpssAsync(...)
+//                                   the median-filter harmonic / percussive split of every signal's amplitude spectra
+//                                   (librosa.decompose.hpss), on the device from spectra that stay there: the chroma of
+//                                   the harmonic part, the flux of the percussive part (the onset envelope), the two
+//                                   parts themselves where asked for; {frameOffsets[, harmonic][, percussive][, chroma,
+//                                   numChroma[, chromaSummaries]][, flux[, fluxSummaries]]}
 //   getSignalTempo(signals, {hopSize, feature, mode, lag, winLength, numLags, norm, gain, startBpm, stdOctaves,
 //                            maxBpm, window, prior, mean, envelope}) / getSignalTempoAsync(...)
 //                                   the tempo of every signal: the autocorrelation tempogram of a feature's spectral
@@ -616,6 +624,28 @@ class Meyda {
       .then((r) => chromaResult(r, c.frameOffsets));
   }
 
+  // The harmonic / percussive separation of getBatchSignals' signals by median filtering (Fitzgerald;
+  // librosa.decompose.hpss) as include/meyda_gpu.h states it: per signal, the median of every bin over kernelTime
+  // buffers and the median of every buffer over kernelFreq bins (odd, 1 to 31; kernelSize: one number for both or
+  // [kernelTime, kernelFreq]; 31), the masks of power 1, 2 (the default) or Infinity (the hard mask) under margin (one
+  // number or [marginHarmonic, marginPercussive], each >= 1; 1). What is asked of the parts: chroma: getSignalChroma's
+  // options, for the chroma of the harmonic part (chroma, numChroma, with summary: true chromaSummaries); flux: {mode:
+  // 'rectified', lag: 1, summary: false}, for the flux of the percussive part (flux, a Float32Array of one value per
+  // buffer: the onset envelope; with summary fluxSummaries); harmonic: true, percussive: true for the parts themselves,
+  // Float32Arrays of bufferSize / 2 values per buffer. Only what is asked for crosses back.
+  getSignalHpss(signals, hopSize, options) {
+    const o = hpssOptions(options, this.bufferSize, this.sampleRate);
+    const c = this._concatSignals(signals, hopSize);
+    return hpssResult(addon.hpssGather(this._plan(), c.samples, c.starts, c.frameOffsets, o), c.frameOffsets);
+  }
+
+  getSignalHpssAsync(signals, hopSize, options) {
+    const o = hpssOptions(options, this.bufferSize, this.sampleRate);
+    const c = this._concatSignals(signals, hopSize);
+    return this._runAsync((plan) => addon.hpssGatherAsync(plan, c.samples, c.starts, c.frameOffsets, o))
+      .then((r) => hpssResult(r, c.frameOffsets));
+  }
+
   // The chroma filter bank of librosa.filters.chroma (later Meyda's createChromaFilterBank) as include/meyda_gpu.h
   // states it: a Float32Array of numChroma x bufferSize / 2, row-major; options {numChroma: 12, a440: 440,
   // centerOctave: 5, octaveWidth: 2 (0: no octave weighting), baseC: true (row 0 is C; false: A)}. Host only.
@@ -1071,6 +1101,76 @@ function chromaResult(raw, frameOffsets) {
       for (let s = 0; s < S; ++s) r.summaries[k].set(raw.summary.subarray((s * STATS.length + j) * w, (s * STATS.length + j + 1) * w), s * w);
     });
   }
+  return r;
+}
+
+// getSignalHpss' options as the addon takes them
+const HPSS_MODES = { 1: 1, 2: 2, Infinity: 3 };  // power -> mgx_hpss_mode (0: the medians themselves)
+function pairOf(v, dflt, what) {
+  if (v === undefined || v === null) return [dflt, dflt];
+  if (Array.isArray(v)) {
+    if (v.length !== 2) throw new TypeError(what + ' must be one number or a pair');
+    return [v[0], v[1]];
+  }
+  return [v, v];
+}
+function hpssOptions(options, bufferSize, sampleRate) {
+  if (options === undefined || options === null || typeof options !== 'object') {
+    throw new TypeError('options must be an object: {kernelSize, power, margin, chroma, flux, harmonic, percussive}');
+  }
+  const [kernelTime, kernelFreq] = pairOf(options.kernelSize, 31, 'kernelSize');
+  for (const k of [kernelTime, kernelFreq]) {
+    if (!Number.isInteger(k) || k < 1 || k > 31 || k % 2 !== 1) throw new RangeError('kernelSize must be odd integers from 1 to 31');
+  }
+  const power = options.power === undefined ? 2 : options.power;
+  if (typeof power !== 'number') throw new TypeError('power must be 1, 2 or Infinity');
+  if (!Object.prototype.hasOwnProperty.call(HPSS_MODES, power)) throw new RangeError('power must be 1, 2 or Infinity');
+  const [marginHarmonic, marginPercussive] = pairOf(options.margin, 1, 'margin');
+  for (const m of [marginHarmonic, marginPercussive]) {
+    if (typeof m !== 'number') throw new TypeError('margin must be numbers');
+    if (!Number.isFinite(m) || !(m >= 1)) throw new RangeError('margin must be finite numbers, 1 or above');
+  }
+  const o = { kernelTime, kernelFreq, mode: HPSS_MODES[power], marginHarmonic, marginPercussive,
+    harmonic: !!options.harmonic, percussive: !!options.percussive };
+  if (options.chroma !== undefined && options.chroma !== null && options.chroma !== false) {
+    const c = chromaOptions(options.chroma === true ? {} : options.chroma, bufferSize, sampleRate);
+    o.chroma = { weights: c.weights, numChroma: c.numChroma, norm: c.norm, perFrame: true, summary: c.summary };
+  }
+  if (options.flux !== undefined && options.flux !== null && options.flux !== false) {
+    const f = options.flux === true ? {} : options.flux;
+    if (typeof f !== 'object') throw new TypeError('flux must be an object: {mode, lag, summary}');
+    const mode = f.mode === undefined ? 'rectified' : f.mode;
+    if (!Object.prototype.hasOwnProperty.call(FLUX_MODES, mode)) throw new RangeError("flux mode must be 'rectified', 'l1' or 'l2'");
+    const lag = f.lag === undefined ? 1 : f.lag;
+    if (!Number.isInteger(lag) || lag < 1 || lag > 8) throw new RangeError('flux lag must be an integer from 1 to 8');
+    o.flux = { mode: FLUX_MODES[mode], lag, perFrame: true, summary: !!f.summary };
+  }
+  if (!o.harmonic && !o.percussive && !o.chroma && !o.flux) {
+    throw new TypeError('nothing asked for: one of chroma, flux, harmonic, percussive');
+  }
+  return o;
+}
+
+function hpssResult(raw, frameOffsets) {
+  const S = frameOffsets.length - 1;
+  const r = { frameOffsets };
+  const stats = (flat, w) => {
+    const out = {};
+    STATS.forEach((k, j) => {
+      out[k] = new Float64Array(S * w);
+      for (let s = 0; s < S; ++s) out[k].set(flat.subarray((s * STATS.length + j) * w, (s * STATS.length + j + 1) * w), s * w);
+    });
+    return out;
+  };
+  if (raw.harmonic) r.harmonic = raw.harmonic;
+  if (raw.percussive) r.percussive = raw.percussive;
+  if (raw.chroma) {
+    r.chroma = raw.chroma;
+    r.numChroma = raw.numChroma;
+  }
+  if (raw.chromaSummary) r.chromaSummaries = stats(raw.chromaSummary, raw.numChroma);
+  if (raw.flux) r.flux = raw.flux;
+  if (raw.fluxSummary) r.fluxSummaries = stats(raw.fluxSummary, 1);
   return r;
 }
 

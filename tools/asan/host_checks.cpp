@@ -10,6 +10,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <limits>
 #include <random>
 #include <vector>
 
@@ -398,10 +399,100 @@ static void beat_tables() {
   printf("beat tables: %ld entries\n", n);
 }
 
+// mgx_hpss_params_init, and every refusal of mgx_hpss_device and mgx_hpss_host that comes before a device is touched
+static void hpss_refusals() {
+  mgx_hpss_params hp;
+  memset(&hp, 0xFF, sizeof hp);
+  mgx_hpss_params_init(&hp);
+  CHECK(hp.struct_size == sizeof hp && hp.kernel_time == 31 && hp.kernel_freq == 31 && hp.mode == MGX_HPSS_SOFT2);
+  CHECK(hp.margin_harmonic == 1.0f && hp.margin_percussive == 1.0f);
+  mgx_hpss_params_init(nullptr);
+  uint32_t tr = 0, tc = 0;
+  mgx_hpss_tile(&tr, &tc);
+  mgx_hpss_tile(nullptr, nullptr);
+  CHECK(tr == MGX_HPSS_TILE_ROWS && tc == MGX_HPSS_TILE_COLS);
+  float block[12];
+  float *rows = block, *h = block + 4, *p = block + 8;  // (never read: every call below is refused or has no rows)
+  auto dev = [&](const mgx_hpss_params* q) { return mgx_hpss_device(rows, 4, 1, nullptr, 0, q, h, p, nullptr); };
+  auto host = [&](const mgx_hpss_params* q) {
+    return mgx_hpss_host(nullptr, nullptr, 0, nullptr, 0, nullptr, 1, q, nullptr, nullptr, h, nullptr);
+  };
+  long n = 0;
+  auto both = [&](mgx_hpss_params q, const char* why) {
+    CHECK(dev(&q) == MGX_E_INVALID_ARGUMENT && strstr(mgx_last_error(), why) != nullptr);
+    CHECK(host(&q) == MGX_E_INVALID_ARGUMENT && strstr(mgx_last_error(), why) != nullptr);
+    ++n;
+  };
+  mgx_hpss_params q = hp;
+  q.struct_size = 20; both(q, "struct_size"); q = hp;
+  for (uint32_t k : {0u, 2u, 30u, 33u, 0x80000001u}) {
+    q.kernel_time = k; both(q, "kernel_time"); q = hp;
+    q.kernel_freq = k; both(q, "kernel_freq"); q = hp;
+  }
+  for (uint32_t m : {4u, 0x80000000u}) { q.mode = m; both(q, "mode"); q = hp; }
+  for (float m : {0.5f, -1.0f, std::numeric_limits<float>::infinity(), std::numeric_limits<float>::quiet_NaN()}) {
+    q.margin_harmonic = m; both(q, "margin_harmonic"); q = hp;
+    q.margin_percussive = m; both(q, "margin_percussive"); q = hp;
+  }
+  CHECK(dev(nullptr) == MGX_E_INVALID_ARGUMENT && host(nullptr) == MGX_E_INVALID_ARGUMENT);
+  CHECK(mgx_hpss_device(rows, 4, 0, nullptr, 0, &hp, h, p, nullptr) == MGX_E_INVALID_ARGUMENT);
+  CHECK(mgx_hpss_device(rows, 4, 1, nullptr, 0, &hp, nullptr, nullptr, nullptr) == MGX_E_INVALID_ARGUMENT);
+  CHECK(mgx_hpss_device(rows, 4, 1, nullptr, 0, &hp, h, h, nullptr) == MGX_E_INVALID_ARGUMENT);
+  CHECK(mgx_hpss_device(rows, 4, 1, nullptr, 0, &hp, rows, p, nullptr) == MGX_E_INVALID_ARGUMENT);
+  CHECK(mgx_hpss_device(rows, 4, 1, nullptr, 0, &hp, h, rows, nullptr) == MGX_E_INVALID_ARGUMENT);
+  CHECK(mgx_hpss_device(rows, 4, 1, nullptr, 1, &hp, h, p, nullptr) == MGX_E_INVALID_ARGUMENT);
+  CHECK(mgx_hpss_device(nullptr, 4, 1, nullptr, 0, &hp, h, p, nullptr) == MGX_E_INVALID_ARGUMENT);
+  CHECK(mgx_hpss_device(nullptr, 0, 1, nullptr, 0, &hp, h, nullptr, nullptr) == MGX_OK);
+  // the host call: its own refusals and the requests', all ahead of the plan
+  CHECK(mgx_hpss_host(nullptr, nullptr, 0, nullptr, 0, nullptr, 1, &hp, nullptr, nullptr, nullptr, nullptr) == MGX_E_INVALID_ARGUMENT);
+  CHECK(strstr(mgx_last_error(), "all NULL") != nullptr);
+  CHECK(mgx_hpss_host(nullptr, nullptr, 0, nullptr, 0, nullptr, 1, &hp, nullptr, nullptr, h, h) == MGX_E_INVALID_ARGUMENT);
+  float w[2] = {1.0f, 1.0f}, pf[2];
+  double sm[8];
+  mgx_chroma_request cr{};
+  cr.struct_size = sizeof cr;
+  cr.num_chroma = 1;
+  cr.norm = MGX_CHROMA_NORM_MAX;
+  cr.weights = w;
+  cr.per_frame = pf;
+  auto with_chroma = [&](mgx_chroma_request c, uint64_t S) {
+    return mgx_hpss_host(nullptr, nullptr, 0, nullptr, 0, nullptr, S, &hp, &c, nullptr, nullptr, nullptr);
+  };
+  mgx_chroma_request c = cr;
+  c.struct_size = 32; CHECK(with_chroma(c, 1) == MGX_E_INVALID_ARGUMENT); c = cr;
+  c.num_chroma = MGX_CHROMA_MAX_BINS + 1; CHECK(with_chroma(c, 1) == MGX_E_INVALID_ARGUMENT); c = cr;
+  c.norm = MGX_NUM_CHROMA_NORMS; CHECK(with_chroma(c, 1) == MGX_E_INVALID_ARGUMENT); c = cr;
+  c.weights = nullptr; CHECK(with_chroma(c, 1) == MGX_E_INVALID_ARGUMENT); c = cr;
+  c.per_frame = nullptr; CHECK(with_chroma(c, 1) == MGX_E_INVALID_ARGUMENT); c = cr;
+  c.summary = sm; CHECK(with_chroma(c, 0) == MGX_E_INVALID_ARGUMENT); c = cr;
+  CHECK(with_chroma(cr, 1) == MGX_E_INVALID_ARGUMENT && strstr(mgx_last_error(), "plan is NULL") != nullptr);
+  mgx_flux_request fr{};
+  fr.struct_size = sizeof fr;
+  fr.field = MGX_AMPLITUDE_SPECTRUM;
+  fr.mode = MGX_FLUX_RECTIFIED;
+  fr.lag = 1;
+  fr.per_frame = pf;
+  auto with_flux = [&](mgx_flux_request f, uint64_t S) {
+    return mgx_hpss_host(nullptr, nullptr, 0, nullptr, 0, nullptr, S, &hp, nullptr, &f, nullptr, nullptr);
+  };
+  mgx_flux_request f = fr;
+  f.struct_size = 24; CHECK(with_flux(f, 1) == MGX_E_INVALID_ARGUMENT); f = fr;
+  f.mode = MGX_NUM_FLUX_MODES; CHECK(with_flux(f, 1) == MGX_E_INVALID_ARGUMENT); f = fr;
+  f.lag = 0; CHECK(with_flux(f, 1) == MGX_E_INVALID_ARGUMENT); f = fr;
+  f.lag = MGX_FLUX_MAX_LAG + 1; CHECK(with_flux(f, 1) == MGX_E_INVALID_ARGUMENT); f = fr;
+  f.per_frame = nullptr; CHECK(with_flux(f, 1) == MGX_E_INVALID_ARGUMENT); f = fr;
+  f.summary = sm; CHECK(with_flux(f, 0) == MGX_E_INVALID_ARGUMENT); f = fr;
+  f.field = MGX_MFCC; CHECK(with_flux(f, 1) == MGX_E_UNSUPPORTED); f = fr;
+  f.field = MGX_RMS; CHECK(with_flux(f, 1) == MGX_E_UNSUPPORTED); f = fr;
+  CHECK(with_flux(fr, 1) == MGX_E_INVALID_ARGUMENT && strstr(mgx_last_error(), "plan is NULL") != nullptr);
+  printf("hpss refusals: %ld parameter sets through both calls\n", n);
+}
+
 int main() {
   wav_fuzz();
   host_tables();
   beat_tables();
+  hpss_refusals();
   arithmetic();
   frame_starts();
   out_fields();
