@@ -119,7 +119,22 @@ typedef enum mgx_precision {
   /* FP64 butterflies, every radix-2 stage rounded to float32 as jsfft stores it
    * (lib/jsfft/fft.js:153-161 + Float32Array storage). Parity default. */
   MGX_PRECISION_FAITHFUL = 0,
-  /* float32 butterflies: HBM-bound, matches the reference only on broadband input. */
+  /* float32 butterflies, float32 twiddles, float32 amplitude sqrtf(re^2 + im^2): HBM-bound. What it promises
+   * (tests/test_gpu_fast.py holds every buffer size and route to it; measured in profiles/fast_precision.txt):
+   *  - amplitudeSpectrum and complexSpectrum lie within (7 log2 N + 2) 2^-24 of the exact transform of the
+   *    windowed frame, X = fft(float32(x w)) / sqrt(N), in relative 2-norm per frame (3.5e-6 at N = 256,
+   *    5.1e-6 at N = 4096: the bound of a float32 radix-2 FFT; measured 0.05-0.08 of it), and the amplitudes
+   *    within 1e-5 ||ref||_inf of the reference's; powerSpectrum is the float32 square of the amplitudes;
+   *  - every feature behind the spectrum is the reference's feature of THAT spectrum within 1e-5; rms, energy
+   *    and zcr are the faithful precision's bits.
+   * What it does not promise: the reference's own value of a feature that takes the logarithm of small bins
+   * or bands (spectralFlatness, mfcc, melBands, loudness) on tonal, steep or impulsive frames. The spectrum's
+   * error is absolute in the frame's norm, about 3e-7 ||X||, so a bin that far below the frame's largest has
+   * no correct digit left: profiles/fast_precision.txt lists the deviation per feature and kind of frame.
+   * Magnitude range: a bin with |X| >= 2^64 is returned as Inf, one below 2^-63 with a few significant bits,
+   * one below 2^-75 as 0 (the squares are float32), where the faithful precision returns every float32
+   * amplitude; |X| <= sqrt(N) / 2 of the largest sample. Inside the range a frame scaled by 2^k gives the same
+   * spectra scaled by 2^k, bit for bit. */
   MGX_PRECISION_FAST = 1
 } mgx_precision;
 
